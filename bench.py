@@ -2,6 +2,7 @@
 """Headline benchmark of the bi-TAI hot path on MI355X.
 
   python bench.py --gpus N --steps K --warmup W        (N > 1: this process starts the N rank processes itself)
+  python bench.py ... --dump-outputs DIR               (also writes the last timed step's outputs: DIR/<key>.npy)
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
 Metric (BASELINE.json): inpainted frames/sec at 128x128, K=F=5, T=5.  Workload = configs[1]: TAI_gray inference, batch
@@ -692,6 +693,32 @@ def train_step_dist_leg(device, rank, world, B=32, timed=3, rehearsal=False):
     return out if rank == 0 else None
 
 
+DUMP_BYTES = 64 * 10 ** 6       # --dump-outputs: all arrays together stay under 64 MB
+DUMP_SEED = 1234
+
+
+def dump_outputs(out, directory):
+    """--dump-outputs: the arrays the timed forward returned in its last step (the caller's output dict), one float32
+    DIR/<key>.npy each.  The arrays share DUMP_BYTES equally; a larger one is written as a fixed sample of its flattened
+    elements (indices drawn from a generator seeded by DUMP_SEED and the shape, sorted), the same on every run.  At the
+    default batch of 32 clips every array is written whole.  Returns {key: what was written}."""
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    keys = sorted(out)
+    budget = DUMP_BYTES // (4 * len(keys))          # float32 elements per array
+    written = {}
+    for k in keys:
+        a = out[k].detach().float().cpu().numpy()
+        rec = {'shape': list(a.shape), 'dtype': 'float32'}
+        if a.size > budget:
+            idx = np.sort(np.random.RandomState([DUMP_SEED] + list(a.shape)).choice(a.size, budget, replace=False))
+            a = a.reshape(-1)[idx]
+            rec['sample'] = '%d of %d elements, seeded, sorted flat indices' % (budget, out[k].numel())
+        np.save(os.path.join(directory, k + '.npy'), np.ascontiguousarray(a, dtype=np.float32))
+        written[k] = rec
+    return written
+
+
 def _free_port():
     s = socket.socket()
     s.bind(('127.0.0.1', 0))
@@ -782,7 +809,11 @@ def main():
     ap.add_argument('--train-leg-timeout', type=int, default=420, help='seconds the multi-rank training leg may take before rank 0 prints the line without it')
     ap.add_argument('--no-extras', action='store_true', help='skip the secondary-config and training-update legs (extra keys of the line)')
     ap.add_argument('--cpu-threads', type=int, default=None, help='threads of the cpu_baseline leg (default: see host_cpu_share)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help="write the last timed step's outputs (rank 0's clips) as DIR/<key>.npy, float32, at most 64 MB in all")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error('--steps must be at least 1')
 
     if args.gpus > 1 and 'RANK' not in os.environ:
         sys.exit(launch_ranks(args.gpus, sys.argv[1:]))
@@ -838,10 +869,15 @@ def main():
     log('warm-up done')
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        step()
+        out = step()
     fence()
     dt = time.perf_counter() - t0
     log('timed %d steps: %.3f s' % (args.steps, dt))
+    dumped = None
+    if args.dump_outputs and rank == 0:     # copied out now: the graph's static outputs are not kept past this point
+        dumped = dump_outputs(out, args.dump_outputs)
+        log('outputs of the last timed step written to %s' % args.dump_outputs)
+    del out
     if world > 1:
         t = torch.tensor([dt], dtype=torch.float64, device='cpu' if backend == 'gloo' else device)
         torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
@@ -864,6 +900,8 @@ def main():
                                    'kernel network and the merge residuals and on the 5x5 / 7x7 MotionEnc layers as 3x3 blocks (each with '
                                    '>= %d workgroups), F(2x2,3x3) on the others (conv_ops.set_winograd_tile)' % conv_ops_threshold()},
     }
+    if dumped is not None:
+        line['dumped_outputs'] = {'dir': args.dump_outputs, 'arrays': dumped}
     if args.rehearse_one_gpu:
         line['rehearsal'] = 'all %d ranks on one GPU, gloo control plane: NOT a measurement' % world
     if rank == 0:

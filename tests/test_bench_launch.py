@@ -56,3 +56,24 @@ def test_the_multi_rank_training_leg_runs_over_gloo_and_keeps_replicas_identical
     assert rec['allreduce_bytes_per_update']['generator'] > 0 and rec['allreduce_bytes_per_update']['discriminator'] > 0
     assert rec['ms_per_update'] > 0 and rec['losses_finite'] is True
     assert 'REHEARSAL' in rec['workload']
+
+
+def test_dump_outputs_writes_float32_arrays_within_the_budget_and_samples_reproducibly(tmp_path, monkeypatch):
+    """--dump-outputs: one float32 <key>.npy per output; an array over its share of the budget becomes a fixed seeded sample,
+    the same elements on every run."""
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    monkeypatch.setattr(bench, 'DUMP_BYTES', 2 * 4 * 1000)          # 1000 float32 elements per array for two arrays
+    g = torch.Generator().manual_seed(0)
+    out = {'pred': torch.randn(2, 3, 1, 8, 8, generator=g), 'big': torch.randn(4, 5, 1, 32, 32, generator=g, dtype=torch.float64)}
+    rec = bench.dump_outputs(out, str(tmp_path / 'a'))
+    bench.dump_outputs(out, str(tmp_path / 'b'))
+    pred, big = np.load(tmp_path / 'a' / 'pred.npy'), np.load(tmp_path / 'a' / 'big.npy')
+    assert pred.dtype == np.float32 and big.dtype == np.float32
+    np.testing.assert_array_equal(pred, out['pred'].numpy())          # within its share: written whole
+    assert big.shape == (1000,) and 'sample' in rec['big'] and rec['big']['shape'] == [4, 5, 1, 32, 32]
+    assert np.isin(big, out['big'].float().numpy().reshape(-1)).all()
+    np.testing.assert_array_equal(big, np.load(tmp_path / 'b' / 'big.npy'))
+    assert sum(f.stat().st_size for f in (tmp_path / 'a').iterdir()) <= bench.DUMP_BYTES + 2 * 128     # + the .npy headers

@@ -182,7 +182,7 @@ def test_capi_library_exports_every_declared_symbol():
     assert L.tai_sepconv_version() >= 100
 
 
-def test_options_surface():
+def test_options_surface(monkeypatch):
     o = options.TestOptions().parse(['--K', '5', '--T', '5', '--F', '5', '--model_key', 'TAI_gray', '--qual_result_root',
                                      'r', '--image_size', '128', '--c_dim', '1'], require_gpu=False)
     assert o.image_size == [128, 128] and o.padding_size == [0, 0] and o.snapshot_file_name == 'model_best.ckpt'
@@ -191,8 +191,14 @@ def test_options_surface():
                                       '80'], require_gpu=False)
     assert (t.lr, t.beta1, t.alpha, t.beta, t.df_dim, t.Ip, t.disc_window_size) == (1e-4, 0.5, 1.0, 0.02, 64, 3, 3)
     assert t.image_size == [64, 80]
+    # without require_gpu=False, parse() refuses a machine without a GPU (the path has no CPU implementation); the GPU's
+    # presence is pinned, so the check means the same on a machine with one
+    args = ['--K', '5', '--T', '5', '--F', '5', '--model_key', 'x', '--qual_result_root', 'r']
+    monkeypatch.setattr(options.torch.cuda, 'is_available', lambda: False)
     with pytest.raises(AssertionError):
-        options.TestOptions().parse(['--K', '5', '--T', '5', '--F', '5', '--model_key', 'x', '--qual_result_root', 'r'])
+        options.TestOptions().parse(args)
+    monkeypatch.setattr(options.torch.cuda, 'is_available', lambda: True)
+    assert options.TestOptions().parse(args).model_key == 'x'
 
 
 def test_sn_discriminator_semantics():
