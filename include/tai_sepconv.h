@@ -124,6 +124,11 @@ int tai_conv_shift_stack(const float* x, float* out, int N, int C, int H, int W,
  *              grad_scaled = grad_z * inv_scale[window]  (what flows into the input gradient through w0). */
 int tai_window_scale_bias_lrelu(float* y, const float* bias, const float* inv_scale, int nw, int B, int C, int HW, float slope,
                                 void* hip_stream);
+/* The same two passes for any HW >= 1, one element per thread (the 10 x 13 output of the last layer at 160 x 208 frames). */
+int tai_window_scale_bias_lrelu_scalar(float* y, const float* bias, const float* inv_scale, int nw, int B, int C, int HW, float slope,
+                                       void* hip_stream);
+int tai_window_scale_lrelu_backward_scalar(const float* grad_y, const float* y, const float* inv_scale, float* grad_z, float* grad_scaled,
+                                           int nw, int B, int C, int HW, float slope, void* hip_stream);
 int tai_window_scale_lrelu_backward(const float* grad_y, const float* y, const float* inv_scale, float* grad_z, float* grad_scaled,
                                     int nw, int B, int C, int HW, float slope, void* hip_stream);
 
@@ -149,7 +154,9 @@ int tai_act_maxpool2x2_backward(const float* grad_y, const float* grad_ypool, co
  *   dw [K, C, 3, 3] = sum over n, y, x of dy[n, k, y, x] * x[n, c, y + a - 1, x + b - 1]      (zero padding)
  * and, when dbias is not NULL, the bias gradient dbias [K] = sum over n, y, x of dy[n, k, y, x] (the output gradient
  * passes through the kernel anyway).
- * x [N, C, H, W], dy [N, K, H, W] fp32 contiguous, H even, W % 16 == 0, each tensor below 2 GiB.  workspace: device memory
+ * x [N, C, H, W], dy [N, K, H, W] fp32 contiguous, any H, W >= 1, each tensor below 2 GiB.  Shapes other than even H with
+ * W % 16 == 0 are computed on both planes zero-extended to an even number of rows and roundup(W, 16) columns (inside the
+ * kernel, no copy; exact: the added output-gradient pixels are zeros).  workspace: device memory
  * of tai_conv3x3_wino_wrw_workspace_floats(...) floats (-1: shape not supported), overwritten.  Partial sums of the
  * workgroups are combined in a fixed order: the results are reproducible from call to call. */
 long long tai_conv3x3_wino_wrw_workspace_floats(int N, int C, int K, int H, int W);
@@ -157,7 +164,8 @@ int tai_conv3x3_wino_wrw(const float* x, const float* dy, float* dw, float* dbia
                          int W, void* hip_stream);
 /* ... with x given as a plane of in_h x in_w per channel whose pixel (in_oy, in_ox) lies under output pixel (0, 0): an input
  * that carries its own halo (the shifted-copy stack of the 5x5 / 7x7 layers, tai_conv_shift_stack: (H + 2, W + 4, 1, 2)) is
- * read inside it, zero padding applies outside the plane only.  dw is then the gradient of the blocked 3x3 weight. */
+ * read inside it, zero padding applies outside the plane only.  dw is then the gradient of the blocked 3x3 weight.  Any H, W
+ * as above; columns past the plane read as zeros. */
 int tai_conv3x3_wino_wrw_window(const float* x, const float* dy, float* dw, float* dbias, float* workspace, int N, int C, int K,
                                 int H, int W, int in_h, int in_w, int in_oy, int in_ox, void* hip_stream);
 /* Load scheme of the weight-gradient kernel when W % 32 == 0: 1 (default) = chunk pairs over 16 consecutive tiles, whole
@@ -180,8 +188,11 @@ int tai_conv3x3_wino_wrw_set_tile(int tile);
 int tai_sn_power_iteration(float* weight, float* u, float* scratch, float* sigma_out, int out_rows, int in_cols, int Ip,
                            void* hip_stream);
 
-/* 3x3 stride-1 zero-padded ("same") convolution + bias + activation, fp32 NCHW contiguous, H and W even, computed as
- * Winograd F(2x2,3x3) on the fp32 MFMA pipe.  Replaces nn.Conv2d(C, K, 3, padding=1) [+ ReLU] of the generator and the
+/* 3x3 stride-1 zero-padded ("same") convolution + bias + activation, fp32 NCHW contiguous, any H, W >= 1, computed as
+ * Winograd F(2x2,3x3) on the fp32 MFMA pipe.  An odd H or W is taken by _parts and by _ex without pooled output, unpooling
+ * epilogue, input window or shift_k, with the fp32 arithmetic (ceil(H / 2) x ceil(W / 2) tiles; row H and column W are the zero
+ * padding); tai_conv3x3_wino_forward, the other forms and the split-bf16 buffers need H and W even and refuse the rest with
+ * TAI_SEPCONV_EINVAL.  Replaces nn.Conv2d(C, K, 3, padding=1) [+ ReLU] of the generator and the
  * kernel network (src/models/mcnet/mcnet.py:79-118,131-152,165-170,271; src/models/tai/tai.py:248-286) and, after the
  * transpose-and-flip of the weight, nn.ConvTranspose2d(C, K, 3, padding=1) of DecCnn (mcnet.py:198-224).
  *   tai_conv3x3_wino_weight_floats      number of floats of the transformed-weight buffer U for a [K,C,3,3] weight
@@ -192,12 +203,12 @@ int tai_conv3x3_wino_transform_weights(const float* weight, float* U, int K, int
 int tai_conv3x3_wino_forward(const float* x, const float* U, const float* bias, float* y, int N, int C, int K, int H, int W,
                              int act, void* hip_stream);
 /* The same convolution, also writing ypool [N,K,H/2,W/2] = 2x2 max pool of the activated output (nn.Conv2d + ReLU +
- * nn.MaxPool2d(2): src/models/mcnet/mcnet.py:84-88, 96-100, 110-114; the un-pooled output is the residual, :118). */
+ * nn.MaxPool2d(2): src/models/mcnet/mcnet.py:84-88, 96-100, 110-114; the un-pooled output is the residual, :118).  H and W even. */
 int tai_conv3x3_wino_forward_maxpool(const float* x, const float* U, const float* bias, float* y, float* ypool, int N, int C,
                                      int K, int H, int W, int act, void* hip_stream);
 /* The same convolution on an input plane of in_h x in_w that holds output pixel (0, 0) at (in_oy, in_ox) (in_ox and in_w
  * even): the zero padding applies outside that plane only, so an input that carries its own halo (tai_conv_shift_stack)
- * is convolved without padding.  ypool may be NULL (no pooled output). */
+ * is convolved without padding.  ypool may be NULL (no pooled output).  H and W even unless the plane is exactly H x W at (0, 0). */
 int tai_conv3x3_wino_forward_window(const float* x, const float* U, const float* bias, float* y, float* ypool, int N, int C,
                                     int K, int H, int W, int in_h, int in_w, int in_oy, int in_ox, int act, void* hip_stream);
 /* The same convolution with the input given as `nparts` (1..4) contiguous [N, C / nparts, H, W] tensors, the operands of

@@ -229,6 +229,10 @@ def lib():
     L.tai_window_scale_bias_lrelu.restype = I
     L.tai_window_scale_lrelu_backward.argtypes = [P, P, P, P, P, I, I, I, I, ctypes.c_float, V]
     L.tai_window_scale_lrelu_backward.restype = I
+    L.tai_window_scale_bias_lrelu_scalar.argtypes = [P, P, P, I, I, I, I, ctypes.c_float, V]
+    L.tai_window_scale_bias_lrelu_scalar.restype = I
+    L.tai_window_scale_lrelu_backward_scalar.argtypes = [P, P, P, P, P, I, I, I, I, ctypes.c_float, V]
+    L.tai_window_scale_lrelu_backward_scalar.restype = I
     L.tai_thin_conv_wrw.argtypes = [P, P, P, P, P, I, I, I, I, I, V]
     L.tai_thin_conv_wrw.restype = I
     L.tai_act_maxpool2x2_forward.argtypes = [P, P, P, ctypes.c_longlong, I, I, I, V]

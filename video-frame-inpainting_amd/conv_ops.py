@@ -414,17 +414,37 @@ def _kxk_ok(N, Ci, Co, H, W, kh, kw, padding):
 # differed by 1.5e-6 from replay to replay; without it 1,500 replays of the whole forward are bit-identical (tools/soak_forward.py).
 WINO_MIN_WORKGROUPS = 72
 
+# Planes with an odd side on the F(2x2, 3x3) kernel, the weight-gradient kernel on any row length, the discriminator's space-to-depth
+# route on even (not only multiple-of-4) inputs and the 3-channel layers under autograd (min_ci 2 in _conv_bias_act's training branch):
+# False restores the routes of before (MIOpen for those shapes) -- A/B timing (tools/published_shapes_bench.py)
+RAGGED_ROUTES = [True]
+
+
+def set_ragged_routes(on):
+    """Switch the odd-plane / any-row-length routes on or off; returns the previous setting."""
+    prev = RAGGED_ROUTES[0]
+    RAGGED_ROUTES[0] = bool(on)
+    return prev
+
+
 # Training: convolutions of a tuple of channel parts go through _WinoConv3x3Parts (no torch.cat in the forward, one contiguous input
 # gradient per part); False restores the concatenating path (A/B, tests)
 PARTS_UNDER_AUTOGRAD = True
 
 
-def _wino_ok(N, Ci, Co, H, W, kh, kw, padding, min_ci=8):
+def _wino_ok(N, Ci, Co, H, W, kh, kw, padding, min_ci=8, ragged=False):
     """``min_ci``: the kernel pads the input channels to a multiple of 8 with zero weights, so fewer than 8 work -- at the cost of a
     whole chunk; the inference paths take that down to 2 (TAI_color's first ContentEnc layer, 3 -> 64 at 256 x 256: 276 us against
-    MIOpen's 620), the training path does not (its input gradient would run 64 rows of MFMA for 3 output channels)."""
-    return (kh == kw == 3 and padding == 1 and H % 2 == 0 and W % 2 == 0 and Ci >= min_ci and N * max(Ci, Co) * H * W < 2 ** 29
-            and ((N * (H // 2) * (W // 2) + 63) // 64) * ((Co + 63) // 64) >= WINO_MIN_WORKGROUPS)
+    MIOpen's 620), and so does the single-tensor training path (_WinoConv3x3: the 3-channel layers of c_dim 3, whose input or output
+    gradient then runs one 64-row block of MFMA for 3 channels -- in exchange for an update without MIOpen's atomics).
+    ``ragged=True`` (the callers of the plain convolution of plain or part-wise inputs): an odd H or W is taken as well (ceil(H / 2) x
+    ceil(W / 2) tiles, row H and column W are padding); the default keeps even planes, which the other variants need -- pooled or
+    unpooled epilogues, input windows, displaced reads -- and the split-bf16 arithmetic has even planes only."""
+    even = H % 2 == 0 and W % 2 == 0
+    if not even and not (ragged and RAGGED_ROUTES[0] and _WINO_ARITH[0] == 0):
+        return False
+    return (kh == kw == 3 and padding == 1 and Ci >= min_ci and N * max(Ci, Co) * H * W < 2 ** 29
+            and ((N * ((H + 1) // 2) * ((W + 1) // 2) + 63) // 64) * ((Co + 63) // 64) >= WINO_MIN_WORKGROUPS)
 
 
 def _usable_out(out, shape, like):
@@ -432,12 +452,21 @@ def _usable_out(out, shape, like):
             and out.device == like.device)
 
 
+def _wino_forward(L, x, U, bias, y, N, Ci, Co, H, W, act, stream):
+    """tai_conv3x3_wino_forward; a plane with an odd side through the general entry (tai_conv3x3_wino_forward_ex), which takes it"""
+    if H % 2 == 0 and W % 2 == 0:
+        _native.check(L.tai_conv3x3_wino_forward(x.data_ptr(), U.data_ptr(), bias.data_ptr(), y.data_ptr(), N, Ci, Co, H, W, _ACT[act],
+                                                 stream), 'tai_conv3x3_wino_forward')
+    else:
+        xs = (ctypes.c_void_p * 1)(x.data_ptr())
+        _native.check(L.tai_conv3x3_wino_forward_ex(xs, 1, 0, U.data_ptr(), bias.data_ptr(), y.data_ptr(), None, 0, 0, 0, 0, None, None,
+                                                   N, Ci, Co, H, W, H, W, 0, 0, _ACT[act], stream), 'tai_conv3x3_wino_forward_ex')
+
+
 def _wino_launch(x, U, bias, N, Ci, Co, H, W, act):
     y = torch.empty((N, Co, H, W), dtype=x.dtype, device=x.device)
     with torch.cuda.device(x.device):
-        _native.check(_native.lib().tai_conv3x3_wino_forward(x.data_ptr(), U.data_ptr(), bias.data_ptr(), y.data_ptr(), N, Ci, Co,
-                                                            H, W, _ACT[act], torch.cuda.current_stream(x.device).cuda_stream),
-                      'tai_conv3x3_wino_forward')
+        _wino_forward(_native.lib(), x, U, bias, y, N, Ci, Co, H, W, act, torch.cuda.current_stream(x.device).cuda_stream)
     return y
 
 
@@ -470,7 +499,7 @@ def wino_conv3x3_plain(x, weight, transposed=False):
     Co = weight.shape[1] if transposed else weight.shape[0]
     if (weight.shape[0] if transposed else weight.shape[1]) != Ci or tuple(weight.shape[2:]) != (3, 3):
         raise ValueError('wino_conv3x3_plain: weight %s does not fit input %s' % (tuple(weight.shape), tuple(x.shape)))
-    if not ((WINO43_UNDER_AUTOGRAD and _wino43_ok(N, Ci, Co, H, W, 1, weight)) or _wino_ok(N, Ci, Co, H, W, 3, 3, 1)):
+    if not ((WINO43_UNDER_AUTOGRAD and _wino43_ok(N, Ci, Co, H, W, 1, weight)) or _wino_ok(N, Ci, Co, H, W, 3, 3, 1, ragged=True)):
         return None
     return _conv3x3_autograd_launch(x, weight, transposed, _zero_bias(Co, x.device), N, Ci, Co, H, W, None)
 
@@ -511,10 +540,12 @@ class _GrowingWorkspace(object):
 _WRW_WORKSPACE = _GrowingWorkspace()
 
 
-def wino_weight_grad(x, grad_out, with_bias=False, window=None):
+def wino_weight_grad(x, grad_out, with_bias=False, window=None, ragged=False):
     """dL/dw [Co, Ci, 3, 3] of y = conv2d(x, w, padding=1) from x [N, Ci, H, W] and dL/dy [N, Co, H, W], by
-    ``tai_conv3x3_wino_wrw`` (Winograd-domain weight gradient on the fp32 MFMA pipe); None if the shape is not supported
-    (odd H, W above 16 and not a multiple of 16, a tensor of 2 GiB or more; rows of fewer than 16 pixels are widened with zeros).  ``with_bias``: returns (dw, dbias), the bias gradient
+    ``tai_conv3x3_wino_wrw`` (Winograd-domain weight gradient on the fp32 MFMA pipe); None if the shape is not supported (odd H,
+    W above 16 and not a multiple of 16, a tensor of 2 GiB or more; rows of fewer than 16 pixels are widened with zeros).
+    ``ragged=True`` (the autograd paths): every shape but tensors of 2 GiB or more -- the shapes off the kernel's native grid are
+    extended inside the kernel to an even number of rows and a multiple of 16 columns, the way the widening here does it.  ``with_bias``: returns (dw, dbias), the bias gradient
     summed by the same kernel.  ``window`` = (in_oy, in_ox): x is a plane [N, Ci, in_h, in_w] that carries its own halo,
     with the pixel under output (0, 0) at (in_oy, in_ox) (the shifted-copy stack of the 5x5 / 7x7 layers).  The workspace
     (partial sums per workgroup) is kept per device and grows to the largest request."""
@@ -526,6 +557,8 @@ def wino_weight_grad(x, grad_out, with_bias=False, window=None):
         # widened to 16 columns with zeros -- the added output-gradient columns contribute nothing, the added input columns are the zero
         # padding the last real column sees anyway -- instead of ATen's weight gradient, whose summation order changes from run to run
         x, grad_out, W = F.pad(x, (0, 16 - W)), F.pad(grad_out, (0, 16 - W)), 16
+    if not (ragged and RAGGED_ROUTES[0]) and (H % 2 or W % 16):
+        return None
     floats = L.tai_conv3x3_wino_wrw_workspace_floats(N, Ci, Co, H, W)
     if floats < 0 or N * Ci * x.shape[2] * x.shape[3] >= 2 ** 29:
         return None
@@ -579,11 +612,11 @@ class _WinoConv3x3(torch.autograd.Function):
             gw_eff = None
             if g.dtype == torch.float32 and x.dtype == torch.float32:
                 if ctx.needs_input_grad[2]:
-                    both = wino_weight_grad(x, g, with_bias=True)
+                    both = wino_weight_grad(x, g, with_bias=True, ragged=True)
                     if both is not None:
                         gw_eff, gb = both
                 else:
-                    gw_eff = wino_weight_grad(x, g)
+                    gw_eff = wino_weight_grad(x, g, ragged=True)
             if gw_eff is None:                                    # shapes the Winograd weight-gradient kernel does not take
                 w_eff = _as_conv_weight(weight, ctx.transposed)
                 gw_eff = torch.ops.aten.convolution_backward(g, x, w_eff, [Co], [1, 1], [1, 1], [1, 1], False, [0, 0], 1,
@@ -654,7 +687,7 @@ class _WinoConv3x3Parts(torch.autograd.Function):
             want_bias = ctx.needs_input_grad[1]
             pieces = []
             for i in range(n):
-                r = wino_weight_grad(parts[i], g, with_bias=(want_bias and i == 0))
+                r = wino_weight_grad(parts[i], g, with_bias=(want_bias and i == 0), ragged=True)
                 if r is None:
                     pieces = None
                     break
@@ -743,7 +776,7 @@ class _WinoConvKxK(torch.autograd.Function):
                     _native.check(_native.lib().tai_conv_shift_stack(x.data_ptr(), stack.data_ptr(), N, Ci, H, W, k,
                                                                      torch.cuda.current_stream(x.device).cuda_stream), 'tai_conv_shift_stack')
             # the weight gradient of the blocked 3x3 form over the stack (it carries its halo: origin (1, 2)), then un-blocked
-            both = wino_weight_grad(stack, g, with_bias=True, window=(1, 2))
+            both = wino_weight_grad(stack, g, with_bias=True, window=(1, 2), ragged=True)
             if both is not None:
                 gw, gb = _unblock3x3_weight(both[0], Ci, k), both[1]
             else:
@@ -968,11 +1001,12 @@ def _conv_bias_act(x, weight, bias, padding, act, transposed, out):
         direct = (len(parts) <= 4 and x0.is_cuda and x0.dtype == torch.float32 and bias is not None and Cp % 8 == 0
                   and Cp * len(parts) == Ci and all(p.shape == x0.shape and p.is_contiguous() and p.dtype == x0.dtype for p in parts)
                   and not (torch.is_grad_enabled() and (weight.requires_grad or bias.requires_grad or any(p.requires_grad for p in parts)))
-                  and _wino_ok(N, Ci, Co, H, W, kh, kw, padding))
+                  and _wino_ok(N, Ci, Co, H, W, kh, kw, padding, ragged=True))
         if not direct:
             if (len(parts) <= 4 and x0.is_cuda and x0.dtype == torch.float32 and bias is not None and Cp % 8 == 0 and Cp * len(parts) == Ci
                     and kh == kw == 3 and all(p.shape == x0.shape and p.is_contiguous() and p.dtype == x0.dtype for p in parts)
-                    and torch.is_grad_enabled() and _wino_ok(N, Ci, Co, H, W, 3, 3, padding) and _wino_ok(N, Co, Cp, H, W, 3, 3, padding)
+                    and torch.is_grad_enabled() and _wino_ok(N, Ci, Co, H, W, 3, 3, padding, ragged=True)
+                    and _wino_ok(N, Co, Cp, H, W, 3, 3, padding, ragged=True)
                     and PARTS_UNDER_AUTOGRAD):
                 return _WinoConv3x3Parts.apply(weight, bias, act, transposed, *parts)     # training: the parts are read where they lie
             return _conv_bias_act(torch.cat(parts, dim=1), weight, bias, padding, act, transposed, out)
@@ -997,7 +1031,10 @@ def _conv_bias_act(x, weight, bias, padding, act, transposed, out):
         if x.is_cuda and x.dtype == torch.float32 and bias is not None and weight.shape[2] == weight.shape[3] == 3:
             Co, Ci = (weight.shape[1], weight.shape[0]) if transposed else (weight.shape[0], weight.shape[1])
             N, _, H, W = x.shape
-            if _wino_ok(N, Ci, Co, H, W, 3, 3, padding) and _wino_ok(N, Co, Ci, H, W, 3, 3, padding):
+            # (min_ci 2: the 3-channel layers of c_dim 3 -- ContentEnc's first, DecCnn's last -- run in-tree too: their input / output
+            # gradient is a convolution with 3 output / input channels, padded to one 64-channel block; MIOpen's kernels sum with atomics)
+            mc = 2 if RAGGED_ROUTES[0] else 8
+            if _wino_ok(N, Ci, Co, H, W, 3, 3, padding, min_ci=mc, ragged=True) and _wino_ok(N, Co, Ci, H, W, 3, 3, padding, min_ci=mc, ragged=True):
                 return _WinoConv3x3.apply(x, weight, bias, act, transposed)      # training: autograd through the HIP kernel
         if (x.is_cuda and x.dtype == torch.float32 and bias is not None and not transposed and weight.shape[2] == weight.shape[3]
                 and weight.shape[2] in (5, 7)):
@@ -1036,7 +1073,7 @@ def _conv_bias_act(x, weight, bias, padding, act, transposed, out):
         return y
     if not transposed and _kxk_ok(N, Ci, Co, H, W, kh, kw, padding):
         return _kxk_as_wino(x, weight, bias, act, False)
-    if _wino_ok(N, Ci, Co, H, W, kh, kw, padding, min_ci=2):
+    if _wino_ok(N, Ci, Co, H, W, kh, kw, padding, min_ci=2, ragged=True):
         # Winograd F(2x2,3x3) on the fp32 MFMA pipe (csrc/wino_conv.hip.inc)
         x = x.contiguous()
         y = out if _usable_out(out, (N, Co, H, W), x) else torch.empty((N, Co, H, W), dtype=x.dtype, device=x.device)
@@ -1047,8 +1084,7 @@ def _conv_bias_act(x, weight, bias, padding, act, transposed, out):
                                                            H, W, _ACT[act], stream), 'tai_conv3x3_wino43_forward')
                 return y
             U = _wino_weights(weight, transposed)
-            _native.check(L.tai_conv3x3_wino_forward(x.data_ptr(), U.data_ptr(), bias.data_ptr(), y.data_ptr(), N, Ci, Co,
-                                                     H, W, _ACT[act], stream), 'tai_conv3x3_wino_forward')
+            _wino_forward(L, x, U, bias, y, N, Ci, Co, H, W, act, stream)
         return y
     w = _cached(weight, ('direct', transposed), lambda: _as_conv_weight(weight.detach(), transposed).contiguous()) \
         if transposed else weight

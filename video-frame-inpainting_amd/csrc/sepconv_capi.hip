@@ -528,6 +528,33 @@ int tai_window_scale_lrelu_backward(const float* grad_y, const float* y, const f
     return check_launch("window_scale_lrelu_backward");
 }
 
+// The same two passes on any plane, one element per thread (a 4-element group would straddle two channels where HW % 4 != 0)
+int tai_window_scale_bias_lrelu_scalar(float* y, const float* bias, const float* inv_scale, int nw, int B, int C, int HW, float slope,
+                                       void* hip_stream) {
+    g_err[0] = 0;
+    if (!y || !bias || !inv_scale) return fail(TAI_SEPCONV_EINVAL, "%s", "null pointer");
+    if (nw <= 0 || B <= 0 || C <= 0 || HW <= 0 || (long long)nw * B * C >= (1LL << 31))
+        return fail(TAI_SEPCONV_EINVAL, "%s", "window_scale_bias_lrelu_scalar: bad dimensions");
+    const int planes = nw * B * C;
+    const int blocks = planes < 16384 ? planes : 16384;
+    hipLaunchKernelGGL(snorm::window_scale_bias_lrelu_scalar, dim3(blocks), dim3(256), 0, static_cast<hipStream_t>(hip_stream), y, bias,
+                       inv_scale, planes, HW, C, B, slope);
+    return check_launch("window_scale_bias_lrelu_scalar");
+}
+
+int tai_window_scale_lrelu_backward_scalar(const float* grad_y, const float* y, const float* inv_scale, float* grad_z, float* grad_scaled,
+                                           int nw, int B, int C, int HW, float slope, void* hip_stream) {
+    g_err[0] = 0;
+    if (!grad_y || !y || !inv_scale || !grad_z || !grad_scaled) return fail(TAI_SEPCONV_EINVAL, "%s", "null pointer");
+    if (nw <= 0 || B <= 0 || C <= 0 || HW <= 0 || (long long)nw * B * C >= (1LL << 31))
+        return fail(TAI_SEPCONV_EINVAL, "%s", "window_scale_lrelu_backward_scalar: bad dimensions");
+    const int planes = nw * B * C;
+    const int blocks = planes < 16384 ? planes : 16384;
+    hipLaunchKernelGGL(snorm::window_scale_lrelu_backward_scalar, dim3(blocks), dim3(256), 0, static_cast<hipStream_t>(hip_stream), grad_y,
+                       y, inv_scale, grad_z, grad_scaled, planes, HW, C, B, slope);
+    return check_launch("window_scale_lrelu_backward_scalar");
+}
+
 int tai_thin_conv_wrw(const float* big, const float* thin, float* dw, float* dbias, float* workspace, int N, int Cb, int H, int W,
                       int k, void* hip_stream) {
     g_err[0] = 0;
@@ -820,19 +847,24 @@ int tai_conv3x3_wino43_forward_blocks(const float* x, int shift_k, const float* 
 }
 
 // Split of the weight-gradient kernel's reduction (the tiles) over workgroups: about one workgroup per CU in total.
-struct WrwPlan { int kblocks, cblocks, nchunks, chunks_per_split, splits, pair; };
+// ragged: any other H and W than even H with W % 16 == 0 -- the kernel's variant over the planes zero-extended to an even number
+// of rows and roundup(W, 16) columns (wino::wrw::WRW_RAGGED); the shapes the kernel took before keep their plan.
+struct WrwPlan { int kblocks, cblocks, nchunks, chunks_per_split, splits, pair, ragged; };
 static bool wrw_plan(int N, int C, int K, int H, int W, WrwPlan& p, int in_h = 0, int in_w = 0) {
-    if (N <= 0 || C <= 0 || K <= 0 || H <= 0 || W <= 0 || H % 2 != 0 || W % 16 != 0) return false;
+    if (N <= 0 || C <= 0 || K <= 0 || H <= 0 || W <= 0) return false;
     if (in_h <= 0) { in_h = H; in_w = W; }
     if ((long long)N * C * in_h * in_w * 4 >= (1LL << 31) || (long long)N * K * H * W * 4 >= (1LL << 31)) return false;
+    p.ragged = H % 2 != 0 || W % 16 != 0;
+    const int Hx = (H + 1) / 2 * 2, Wx = (W + 15) / 16 * 16;          // the extended planes (H, W unless ragged)
+    if ((long long)N * (Hx / 2) * (Wx / 2) / wino::wrw::CT >= (1LL << 31)) return false;
     p.kblocks = (K + 63) / 64;
     p.cblocks = (C + 63) / 64;
-    p.nchunks = (int)((long long)N * (H / 2) * (W / 2) / wino::wrw::CT);
+    p.nchunks = (int)((long long)N * (Hx / 2) * (Wx / 2) / wino::wrw::CT);
     int want = 256 / (p.kblocks * p.cblocks);
     if (want < 1) want = 1;
     if (want > p.nchunks) want = p.nchunks;
     p.chunks_per_split = (p.nchunks + want - 1) / want;
-    p.pair = W % 32 == 0;                         // chunk pairs over 16 consecutive tiles: whole 128-byte lines per load
+    p.pair = !p.ragged && W % 32 == 0;            // chunk pairs over 16 consecutive tiles: whole 128-byte lines per load
     if (p.pair && (p.chunks_per_split & 1)) ++p.chunks_per_split;      // (the chunk count is even when W % 32 == 0)
     p.splits = (p.nchunks + p.chunks_per_split - 1) / p.chunks_per_split;
     return true;
@@ -901,7 +933,9 @@ static int wino_wrw_impl(const float* x, const float* dy, float* dw, float* dbia
     if (in_oy < 0 || in_ox < 0 || in_oy + H > in_h || in_ox + W > in_w)
         return fail(TAI_SEPCONV_EINVAL, "%s", "conv3x3_wino_wrw: output window outside the input plane");
     if (!wrw_plan(N, C, K, H, W, p, in_h, in_w))
-        return fail(TAI_SEPCONV_EINVAL, "%s", "conv3x3_wino_wrw: needs even H, W % 16 == 0 and tensors below 2 GiB");
+        return fail(TAI_SEPCONV_EINVAL, "%s", "conv3x3_wino_wrw: needs positive dimensions and tensors below 2 GiB");
+    if (p.ragged && stamps)
+        return fail(TAI_SEPCONV_EINVAL, "%s", "conv3x3_wino_wrw: timeline stamps need even H and W % 16 == 0");
     hipStream_t stream = static_cast<hipStream_t>(hip_stream);
     WrwPlan q;
     if (g_wrw_tile.load(std::memory_order_relaxed) == 4 && !stamps && wrw43_plan(N, C, K, H, W, q, in_h, in_w, in_oy, in_ox)) {
@@ -929,6 +963,7 @@ static int wino_wrw_impl(const float* x, const float* dy, float* dw, float* dbia
     } while (0)
     const bool pair = p.pair && g_wrw_pair.load(std::memory_order_relaxed);
     if (stamps) { if (pair) TAI_LAUNCH_WRW(2, true); else TAI_LAUNCH_WRW(2, false); }
+    else if (p.ragged) TAI_LAUNCH_WRW(wino::wrw::WRW_RAGGED, false);
     else { if (pair) TAI_LAUNCH_WRW(0, true); else TAI_LAUNCH_WRW(0, false); }
 #undef TAI_LAUNCH_WRW
     if (int rc = check_launch("conv3x3_wino_wrw")) return rc;
@@ -982,6 +1017,8 @@ int tai_conv3x3_wino_timeline_skip(int level) {
 
 int tai_conv3x3_wino_forward(const float* x, const float* U, const float* bias, float* y, int N, int C, int K, int H, int W,
                              int act, void* hip_stream) {
+    // (this entry keeps its even-plane contract; odd planes go through tai_conv3x3_wino_forward_ex / _parts)
+    if (H % 2 || W % 2) { g_err[0] = 0; return fail(TAI_SEPCONV_EINVAL, "%s", "conv3x3_wino_forward: needs even H and W (odd planes: _forward_ex, _forward_parts)"); }
     const float* xs[4] = {x, x, x, x};
     return wino_forward_impl(xs, 1, U, bias, y, N, C, K, H, W, act, hip_stream, nullptr);
 }
@@ -1071,15 +1108,21 @@ static int wino_forward_impl(const float* const* xs, int nparts, const float* U,
     // displaced reads stay inside the plane: rows up to H + in_oy + 3 (S - 1), columns up to W + 1 + in_ox + 3 (S - 1)
     if (S && (in_oy < 1 || in_ox < 2 || in_h < H + in_oy + 1 + 3 * (S - 1) || in_w < W + in_ox + 2 + 3 * (S - 1)))
         return fail(TAI_SEPCONV_EINVAL, "%s", "conv3x3_wino_ex: the input plane does not hold the halo of the displaced reads");
-    if (N <= 0 || C <= 0 || K <= 0 || H <= 0 || W <= 0 || H % 2 || W % 2 || act < 0 || act > 2)
-        return fail(TAI_SEPCONV_EINVAL, "%s", "conv3x3_wino: needs even H and W, act in {0, 1, 2}");
-    if (in_h < H + in_oy || in_w < W + in_ox || in_oy < 0 || in_ox < 0 || in_ox % 2 || in_w % 2)
+    if (N <= 0 || C <= 0 || K <= 0 || H <= 0 || W <= 0 || act < 0 || act > 2)
+        return fail(TAI_SEPCONV_EINVAL, "%s", "conv3x3_wino: bad dimensions, act in {0, 1, 2}");
+    // an odd side (the ragged-plane variant, EPI 3 of wino::conv3x3): plain input and output planes only
+    const bool ragged = H % 2 != 0 || W % 2 != 0;
+    if (ragged && (ypool || S || ex.addx || stamps || in_h != H || in_w != W || in_oy != 0 || in_ox != 0))
+        return fail(TAI_SEPCONV_EINVAL, "%s", "conv3x3_wino: needs even H and W for a pooled output, the unpooling epilogue, an input "
+                    "window or displaced reads (odd H or W: plain input and output only)");
+    if (in_h < H + in_oy || in_w < W + in_ox || in_oy < 0 || in_ox < 0 || in_ox % 2 || (!ragged && in_w % 2))
         return fail(TAI_SEPCONV_EINVAL, "%s", "conv3x3_wino: bad input window");
     if ((long long)N * C * in_h * in_w >= (1LL << 29) || (long long)N * K * H * W >= (1LL << 29))   // byte offsets < 2^31
         return fail(TAI_SEPCONV_EINVAL, "%s", "conv3x3_wino: tensor too large (2^29 elements or more)");
     const int Kpad = (K + wino::TM - 1) / wino::TM * wino::TM, Cpad = (C + wino::KC - 1) / wino::KC * wino::KC;
     const int kblocks = Kpad / wino::TM, nchunks = Cpad / wino::KC;
-    const long long tiles = (long long)N * (H / 2) * (W / 2);
+    const int th = (H + 1) / 2, tw_all = (W + 1) / 2;           // tiles per column / row (ceil: H / 2, W / 2 on even planes)
+    const long long tiles = (long long)N * th * tw_all;
     const long long tblocks = (tiles + wino::TN - 1) / wino::TN;
     hipStream_t s = static_cast<hipStream_t>(hip_stream);
     // A buffer made in split arithmetic (tai_conv3x3_wino_set_arithmetic(1)) takes the split-bf16 kernel where that kernel has the
@@ -1087,6 +1130,8 @@ static int wino_forward_impl(const float* const* xs, int nparts, const float* U,
     {
         bool split_buf;
         { std::lock_guard<std::mutex> lk(g_split_mu); split_buf = g_split_bufs.count(U) != 0; }
+        if (split_buf && ragged)
+            return fail(TAI_SEPCONV_EINVAL, "%s", "conv3x3_wino: the split-bf16 arithmetic needs even H and W");
         const int tw = W / 2;
         const bool tw_ok = tw % 16 == 0 || (tw >= 2 && (tw & (tw - 1)) == 0);
         const int epi_s = ex.addx ? (ex.y2 ? 1 : 2) : 0;
@@ -1147,8 +1192,8 @@ static int wino_forward_impl(const float* const* xs, int nparts, const float* U,
         m = (unsigned)((num + (unsigned __int128)d - 1) / (unsigned __int128)d);
     };
     wino::DivMagic dvF, dvT;
-    magic((long long)(H / 2) * (W / 2), dvF.m_tpi, dvF.s_tpi);
-    magic(W / 2, dvF.m_tw, dvF.s_tw);
+    magic((long long)th * tw_all, dvF.m_tpi, dvF.s_tpi);
+    magic(tw_all, dvF.m_tw, dvF.s_tw);
     magic(kblocks, dvF.m_kb, dvF.s_kb);
     dvT = dvF;
     magic(Kpad / wino::TTM > 0 ? Kpad / wino::TTM : 1, dvT.m_kb, dvT.s_kb);
@@ -1167,11 +1212,11 @@ static int wino_forward_impl(const float* const* xs, int nparts, const float* U,
                                TAI_WINO_ARGS, kblocks, TAI_WINO_TAIL, dvF);                                            \
         }                                                                                                              \
     } while (0)
-#define TAI_LAUNCH_WINO_ACT(D, SK, Q)                                   \
+#define TAI_LAUNCH_WINO_ACT(D, SK, Q, E)                                \
     do {                                                                \
-        if (act == 0) TAI_LAUNCH_WINO(0, D, SK, Q, 0);                  \
-        else if (act == 1) TAI_LAUNCH_WINO(1, D, SK, Q, 0);             \
-        else TAI_LAUNCH_WINO(2, D, SK, Q, 0);                           \
+        if (act == 0) TAI_LAUNCH_WINO(0, D, SK, Q, E);                  \
+        else if (act == 1) TAI_LAUNCH_WINO(1, D, SK, Q, E);             \
+        else TAI_LAUNCH_WINO(2, D, SK, Q, E);                           \
     } while (0)
     // the instantiations the path uses: the second-output / sum epilogues come without activation (Residual's last
     // convolution) on one tensor or cat operands; the displaced reads come with ReLU (MotionEnc)
@@ -1198,8 +1243,10 @@ static int wino_forward_impl(const float* const* xs, int nparts, const float* U,
     else if (epi == 2 && pmode == 1) TAI_LAUNCH_WINO(0, 0, 0, 1, 2);
     else if (epi == 2) TAI_LAUNCH_WINO(0, 0, 0, 0, 2);
     else if (pmode == 2) TAI_LAUNCH_WINO(1, 0, 0, 2, 0);
-    else if (pmode == 1) TAI_LAUNCH_WINO_ACT(0, 0, 1);
-    else TAI_LAUNCH_WINO_ACT(0, 0, 0);
+    else if (ragged && pmode == 1) TAI_LAUNCH_WINO_ACT(0, 0, 1, 3);       // odd H or W
+    else if (ragged) TAI_LAUNCH_WINO_ACT(0, 0, 0, 3);
+    else if (pmode == 1) TAI_LAUNCH_WINO_ACT(0, 0, 1, 0);
+    else TAI_LAUNCH_WINO_ACT(0, 0, 0, 0);
 #undef TAI_LAUNCH_WINO_ACT
 #undef TAI_LAUNCH_WINO
 #undef TAI_WINO_TAIL

@@ -115,7 +115,7 @@ void finish(float* __restrict__ W, const float* __restrict__ t_raw, float* __res
 // and backwards, from the gradient g of that output and the output itself,
 //   gz = g * (y > 0 ? 1 : slope)     -- the gradient of the layer's pre-activation: weight and bias gradients take it as it is
 //   gs = gz * inv_scale[window]      -- what flows on into the input gradient (through w0)
-// ATen ran these as three and two passes over [13 B, C, H, W].  x: [nw * B, C, HW] contiguous, HW % 4 == 0.
+// ATen ran these as three and two passes over [13 B, C, H, W].  x: [nw * B, C, HW] contiguous, HW % 4 == 0 (any HW: the _scalar forms).
 __global__ __launch_bounds__(256)
 void window_scale_bias_lrelu(float* __restrict__ y, const float* __restrict__ bias, const float* __restrict__ inv_scale,
                              long long n4, int chw4, int hw4, int C, int B, float slope) {
@@ -141,6 +141,37 @@ void window_scale_lrelu_backward(const float* __restrict__ g, const float* __res
         z.z = o.z > 0.f ? a.z : a.z * slope; z.w = o.w > 0.f ? a.w : a.w * slope;
         reinterpret_cast<float4*>(gz)[i] = z;
         reinterpret_cast<float4*>(gs)[i] = make_float4(z.x * s, z.y * s, z.z * s, z.w * s);
+    }
+}
+
+// The same two passes one element per thread, for planes with HW % 4 != 0 (the 10 x 13 output of the last layer at 160 x 208
+// frames), where a 4-element group would straddle two channels.  A workgroup walks whole planes (plane = (window, image, channel)):
+// the window's factor and the channel's bias are found once per plane, the pixels of a plane are 32-bit offsets.  The arithmetic
+// per element is the one above.
+__global__ __launch_bounds__(256)
+void window_scale_bias_lrelu_scalar(float* __restrict__ y, const float* __restrict__ bias, const float* __restrict__ inv_scale,
+                                    int planes, int hw, int C, int B, float slope) {
+    for (int p = blockIdx.x; p < planes; p += gridDim.x) {
+        const float s = inv_scale[p / (C * B)], b = bias[p % C];
+        float* yp = y + (long long)p * hw;
+        for (int i = threadIdx.x; i < hw; i += 256) {
+            const float v = yp[i] * s + b;
+            yp[i] = v > 0.f ? v : v * slope;
+        }
+    }
+}
+
+__global__ __launch_bounds__(256)
+void window_scale_lrelu_backward_scalar(const float* __restrict__ g, const float* __restrict__ y, const float* __restrict__ inv_scale,
+                                        float* __restrict__ gz, float* __restrict__ gs, int planes, int hw, int C, int B, float slope) {
+    for (int p = blockIdx.x; p < planes; p += gridDim.x) {
+        const float s = inv_scale[p / (C * B)];
+        const long long o = (long long)p * hw;
+        for (int i = threadIdx.x; i < hw; i += 256) {
+            const float z = y[o + i] > 0.f ? g[o + i] : g[o + i] * slope;
+            gz[o + i] = z;
+            gs[o + i] = z * s;
+        }
     }
 }
 

@@ -221,6 +221,11 @@ __device__ __forceinline__ int xcd_block(int bid, int n) { return (n % 8 == 0) ?
 // run-time branches inside the 16-channel store loop they cost every layer 3,400 cycles of epilogue (tools/wino_timeline.py)
 // (DecCnn's unpool + residual add, mcnet.py:234-236, in the epilogue of the Residual block's last convolution: a tile
 // is exactly one unpooling cell).
+// EPI 3: no second output, and a plane with an odd side (H or W odd; plain input and output planes, no pooled output): the tile
+// grid is ceil(H / 2) x ceil(W / 2), row H and column W are the zero padding -- read as 0, never stored.  Row starts are then only
+// 4-byte aligned and column W is the next row's first pixel in memory, so a patch row's middle pair is two 4-byte loads (the
+// second out of range past column W - 1) and an output row two 4-byte stores (the second dropped past column W - 1).  A variant
+// of its own, so that the even-plane instantiations keep their instruction streams (and their counted waits) exactly.
 // SKIP (timeline builds only; results are then wrong): 1 no patch transform; 4 that and no patch loads; 2 that and no V
 // writes; 5 that and no output stores.
 template <int ACT, int DBG = 0, int SKIP = 0, int PARTS = 0, bool TALL = false, int EPI = 0>
@@ -257,7 +262,8 @@ void conv3x3(const float* __restrict__ x, const float* __restrict__ x1, const fl
     };
     const int bid = xcd_block(blockIdx.x, (int)grid_n);
     const int tb = (int)__builtin_amdgcn_readfirstlane(fdiv((unsigned)bid, (unsigned)dv.m_kb, (unsigned)dv.s_kb)), kb = bid - tb * kblocks;
-    const int TH = H >> 1, TW = W >> 1;
+    constexpr bool RAGGED = EPI == 3, ADDX = EPI == 1 || EPI == 2;
+    const int TH = RAGGED ? (H + 1) >> 1 : H >> 1, TW = RAGGED ? (W + 1) >> 1 : W >> 1;
     const int tiles_per_image = TH * TW;
     const int tiles_total = N * tiles_per_image;             // < 2^29 / 4
     const long long plane = (long long)H * W;             // output plane
@@ -302,6 +308,7 @@ void conv3x3(const float* __restrict__ x, const float* __restrict__ x1, const fl
                 mask_right = (pvalid && ptx < TW - 1 && !(TALL && last_lane)) ? 1.f : 0.f;
     const bool left_own = left_in && (ptx == 0 || first_lane), right_own = right_in && (ptx == TW - 1 || last_lane);
     unsigned off_mid[4], off_left[4], off_right[4];     // byte offsets from the channel plane of image 0
+    unsigned off_mid1[4];                               // RAGGED: the middle pair's second value (out of range at column W)
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
         const int yy = 2 * pty - 1 + i + in_oy;
@@ -311,6 +318,7 @@ void conv3x3(const float* __restrict__ x, const float* __restrict__ x1, const fl
                            : OUT_OF_RANGE;
         off_left[i] = (rowok && left_own) ? off_mid[i] - 4u : OUT_OF_RANGE;
         off_right[i] = (rowok && right_own) ? off_mid[i] + 8u : OUT_OF_RANGE;
+        off_mid1[i] = (rowok && 2 * ptx + 1 < W) ? off_mid[i] + 4u : OUT_OF_RANGE;      // (RAGGED: in_w == W, in_ox == 0)
     }
 
     // The bias rides in the accumulators: transform position (1, 1) enters all four outputs of a tile with coefficient +1
@@ -386,7 +394,14 @@ void conv3x3(const float* __restrict__ x, const float* __restrict__ x1, const fl
             xrsrc = xrsrc0;
             soff = (int)((long long)cc * plane_in * 4);
         }
-        if (what != 2) dm[buf][p][i] = __builtin_bit_cast(float2, __builtin_amdgcn_raw_buffer_load_b64(xrsrc, off_mid[i], soff, 0));
+        if (what != 2) {
+            if constexpr (RAGGED) {
+                dm[buf][p][i].x = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(xrsrc, off_mid[i], soff, 0));
+                dm[buf][p][i].y = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(xrsrc, off_mid1[i], soff, 0));
+            } else {
+                dm[buf][p][i] = __builtin_bit_cast(float2, __builtin_amdgcn_raw_buffer_load_b64(xrsrc, off_mid[i], soff, 0));
+            }
+        }
         // own outer values (first / last tile of a tile row, lanes 0 / 63); every other lane is out of range: no memory access
         if (what != 1) {
             dlr[buf][p][i].x = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(xrsrc, off_left[i], soff, 0));
@@ -568,8 +583,10 @@ void conv3x3(const float* __restrict__ x, const float* __restrict__ x1, const fl
     // (x1-x3 only where they are used: for a single input tensor the compiler does not keep them in registers but RE-LOADS them from
     // the kernel-argument segment in front of every such statement and waits for the scalar load -- 110-240 cycles per chunk on the
     // 128 x 32 shape, found as a 4 % regression of its chunk loop in tools/wino_timeline.py)
-    if constexpr (PARTS == 1) asm volatile("s_waitcnt vmcnt(%0)\n\ts_waitcnt lgkmcnt(0)\n\ts_barrier" : : "n"(NP * 4), "s"(x), "s"(x1), "s"(x2), "s"(x3) : "memory");
-    else asm volatile("s_waitcnt vmcnt(%0)\n\ts_waitcnt lgkmcnt(0)\n\ts_barrier" : : "n"(NP * 4), "s"(x) : "memory");
+    // (RAGGED: two loads per middle pair)
+    constexpr int MIDS = RAGGED ? 2 * NP * 4 : NP * 4;
+    if constexpr (PARTS == 1) asm volatile("s_waitcnt vmcnt(%0)\n\ts_waitcnt lgkmcnt(0)\n\ts_barrier" : : "n"(MIDS), "s"(x), "s"(x1), "s"(x2), "s"(x3) : "memory");
+    else asm volatile("s_waitcnt vmcnt(%0)\n\ts_waitcnt lgkmcnt(0)\n\ts_barrier" : : "n"(MIDS), "s"(x) : "memory");
     __builtin_amdgcn_sched_barrier(0);
 
     if (DBG) t_pro = __builtin_readcyclecounter();
@@ -679,9 +696,14 @@ void conv3x3(const float* __restrict__ x, const float* __restrict__ x1, const fl
             if (DBG == 2 && ch < 2 && tid == 0) stamps[64 * (long long)blockIdx.x + 30 + 16 * ch + j] = __builtin_readcyclecounter();
         }
         // the last weight DMA (group 11) is older than the 12 patch loads of groups 12-15: at most 12 outstanding <=>
-        // the weights have landed
-        if constexpr (PARTS == 1) asm volatile("s_waitcnt vmcnt(12)\n\ts_waitcnt lgkmcnt(0)\n\ts_barrier" : : "s"(x), "s"(x1), "s"(x2), "s"(x3) : "memory");
-        else asm volatile("s_waitcnt vmcnt(12)\n\ts_waitcnt lgkmcnt(0)\n\ts_barrier" : : "s"(x) : "memory");
+        // the weights have landed (RAGGED: 16, four loads per patch row)
+        if constexpr (RAGGED) {
+            if constexpr (PARTS == 1) asm volatile("s_waitcnt vmcnt(16)\n\ts_waitcnt lgkmcnt(0)\n\ts_barrier" : : "s"(x), "s"(x1), "s"(x2), "s"(x3) : "memory");
+            else asm volatile("s_waitcnt vmcnt(16)\n\ts_waitcnt lgkmcnt(0)\n\ts_barrier" : : "s"(x) : "memory");
+        } else {
+            if constexpr (PARTS == 1) asm volatile("s_waitcnt vmcnt(12)\n\ts_waitcnt lgkmcnt(0)\n\ts_barrier" : : "s"(x), "s"(x1), "s"(x2), "s"(x3) : "memory");
+            else asm volatile("s_waitcnt vmcnt(12)\n\ts_waitcnt lgkmcnt(0)\n\ts_barrier" : : "s"(x) : "memory");
+        }
         if (DBG && tid == 0 && ch < 26) stamps[64 * (long long)blockIdx.x + 4 + ch] = __builtin_readcyclecounter();
     };
     const std::integral_constant<bool, true> FIRST_CHUNK;
@@ -711,7 +733,10 @@ void conv3x3(const float* __restrict__ x, const float* __restrict__ x1, const fl
     const __amdgpu_buffer_rsrc_t yrsrc = uniform_rsrc(y, (int)((long long)N * K * plane * 4));
     const unsigned voff0 = evalid ? ((unsigned)(eimg * K + 4 * half) * (unsigned)plane + (unsigned)((2 * ety) * W + 2 * etx)) * 4u
                                   : OUT_OF_RANGE;
-    const unsigned voff1 = evalid ? voff0 + (unsigned)W * 4u : OUT_OF_RANGE;
+    // (RAGGED: the second row and the second column of the plane's last tile row / column are row H / column W: dropped)
+    const unsigned voff1 = (evalid && (!RAGGED || 2 * ety + 1 < H)) ? voff0 + (unsigned)W * 4u : OUT_OF_RANGE;
+    const bool col1 = !RAGGED || 2 * etx + 1 < W;
+    const unsigned voff0r = (evalid && col1) ? voff0 + 4u : OUT_OF_RANGE, voff1r = (voff1 != OUT_OF_RANGE && col1) ? voff1 + 4u : OUT_OF_RANGE;
     // optional second output: the 2x2 max pool of the activated output (nn.MaxPool2d(2) of ContentEnc, mcnet.py:86-117).
     // A tile IS a pooling window, so the pooled value is the max of the lane's four outputs.
     const long long pplane = (long long)pool_h * pool_w;      // (TH x TW with the origin at (0, 0) for a plain pooled tensor)
@@ -720,7 +745,7 @@ void conv3x3(const float* __restrict__ x, const float* __restrict__ x1, const fl
                                  : OUT_OF_RANGE;
     // optional third output: y2 = y + fixed_unpooling(addx); the lane's tile is one unpooling cell, addx lands on its (0, 0) pixel
     const long long aplane = plane >> 2;
-    const __amdgpu_buffer_rsrc_t arsrc = uniform_rsrc(EPI ? addx : y, EPI ? (int)((long long)N * K * aplane * 4) : 0);
+    const __amdgpu_buffer_rsrc_t arsrc = uniform_rsrc(ADDX ? addx : y, ADDX ? (int)((long long)N * K * aplane * 4) : 0);
     const __amdgpu_buffer_rsrc_t y2rsrc = uniform_rsrc(EPI == 1 ? y2 : y, EPI == 1 ? (int)((long long)N * K * plane * 4) : 0);
     const unsigned aoff = evalid ? ((unsigned)(eimg * K + 4 * half) * (unsigned)aplane + (unsigned)(ety * TW + etx)) * 4u : OUT_OF_RANGE;
     const int klim = K - 4 * half;                           // this lane's channel is k_lo + 4 * half
@@ -728,7 +753,7 @@ void conv3x3(const float* __restrict__ x, const float* __restrict__ x1, const fl
     // the values to add (EPI): all 16 loads issued here, ahead of the inverse transform that hides their latency -- left inside
     // the store loop each one was waited for where it was used (SQ_WAIT_ANY 25-31 % of the wave cycles on these instances)
     float axv[16];
-    if (EPI) {
+    if (ADDX) {
 #pragma unroll
         for (int j = 0; j < 16; ++j) {
             const int k_lo = k_base + 8 * (j >> 2) + (j & 3);
@@ -785,10 +810,15 @@ void conv3x3(const float* __restrict__ x, const float* __restrict__ x1, const fl
             if (ACT == 2) { r00 = tanhf(r00); r01 = tanhf(r01); r10 = tanhf(r10); r11 = tanhf(r11); }
             const bool kok = MASKED ? k_lo < klim : true;
             const int soff = (int)((long long)k_lo * plane * 4);
-            const float ax = EPI ? axv[j] : 0.f;
+            const float ax = ADDX ? axv[j] : 0.f;
             if (EPI == 2) r00 += ax;             // only the sum is wanted: it IS the output
             r00v[j] = r00; r01v[j] = r01; r10v[j] = r10; r11v[j] = r11;
-            if (SKIP < 5 || r00 == 12345.f) {
+            if (RAGGED) {
+                __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(int, r00), yrsrc, kok ? voff0 : OUT_OF_RANGE, soff, 0);
+                __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(int, r01), yrsrc, kok ? voff0r : OUT_OF_RANGE, soff, 0);
+                __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(int, r10), yrsrc, kok ? voff1 : OUT_OF_RANGE, soff, 0);
+                __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(int, r11), yrsrc, kok ? voff1r : OUT_OF_RANGE, soff, 0);
+            } else if (SKIP < 5 || r00 == 12345.f) {
                 __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(v2i, make_float2(r00, r01)), yrsrc, kok ? voff0 : OUT_OF_RANGE, soff, 0);
                 __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(v2i, make_float2(r10, r11)), yrsrc, kok ? voff1 : OUT_OF_RANGE, soff, 0);
                 if (EPI == 1) {
@@ -797,7 +827,7 @@ void conv3x3(const float* __restrict__ x, const float* __restrict__ x1, const fl
                 }
             }
         }
-        if (ypool && SKIP < 5) {      // wave-uniform
+        if (!RAGGED && ypool && SKIP < 5) {      // wave-uniform
 #pragma unroll
             for (int j = 0; j < 16; ++j) {
                 const int k_lo = k_base + 8 * (j >> 2) + (j & 3);

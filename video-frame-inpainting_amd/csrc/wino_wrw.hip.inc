@@ -39,19 +39,31 @@ constexpr int CT = 8;                        // tiles per chunk
 // 3.4x the algorithmic bytes on the 64-channel 128 x 128 layers (plane strides of 64 KB land the channels in the same sets;
 // profiles/r02_wrw_counters.txt) and the kernel ran at the memory system's pace.  One register buffer holds a pair: its
 // odd-tile half is transformed one chunk after its even-tile half, then the next pair's loads start.
+// DBG & WRW_RAGGED: any H and W (wrw_plan sends there every shape but even H with W % 16 == 0).  The kernel computes what the
+// host-side widening computes: both planes zero-extended to an even number of rows and roundup(W, 16) columns, so every chunk of
+// 8 tiles still lies in one tile row.  Nothing is copied: rows past H and columns past W (past the input plane, for x) are
+// out-of-range offsets of the patch and output-gradient loads, i.e. zeros; row starts are then only 4-byte aligned, so the
+// 8-byte loads become two 4-byte loads.  The extension is exact: the added output-gradient pixels are zeros and contribute
+// nothing, the added input pixels are the convolution's own zero padding.  (A flag of DBG, not a third template parameter: the
+// even-shape instantiations keep their names and their instruction streams; the remaining bits of DBG are the stamp level.)
+constexpr int WRW_RAGGED = 4;
 template <int DBG, bool PAIR>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1)))
 void conv3x3_wrw(const float* __restrict__ x, const float* __restrict__ dy, float* __restrict__ ws, float* __restrict__ wsb, int N,
                  int C, int K, int H, int W, int in_h, int in_w, int in_oy, int in_ox, int kblocks, int cblocks,
                  int chunks_per_split, int nchunks_total, long long* __restrict__ stamps) {
+    constexpr bool RAGGED = (DBG & WRW_RAGGED) != 0;
+    constexpr int STAMPS = DBG & 3;
+    static_assert(!(RAGGED && PAIR), "the ragged form reads single chunks");
     long long t_entry = 0, t_pro = 0, t_loop = 0;
-    if (DBG) t_entry = __builtin_readcyclecounter();
+    if (STAMPS) t_entry = __builtin_readcyclecounter();
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wm = wave & 1, wn = wave >> 1;
     const int bid = blockIdx.x;
     const int kb = bid % kblocks, cb = (bid / kblocks) % cblocks, sp = bid / (kblocks * cblocks);
-    const int TH = H >> 1, TW = W >> 1;
+    // (RAGGED: the tile grid of the zero-extended planes, H + 1 rows for an odd H, W rounded up to 16 columns)
+    const int TH = RAGGED ? (H + 1) >> 1 : H >> 1, TW = RAGGED ? ((W + 15) & ~15) >> 1 : W >> 1;
     const long long plane = (long long)H * W;
     // The input plane is in_h x in_w with the pixel under output (0, 0) at (in_oy, in_ox): (H, W, 0, 0) for an ordinary tensor,
     // whose border is the zero padding; a tensor that carries its own halo (the shifted-copy stack of the 5x5 / 7x7 layers,
@@ -140,14 +152,28 @@ void conv3x3_wrw(const float* __restrict__ x, const float* __restrict__ dy, floa
         const unsigned vm = rowok ? vmid[p] : OUT_OF_RANGE;
         const unsigned vl = (rowok && col > 0) ? vleft[p] : OUT_OF_RANGE;
         const unsigned vr = (rowok && col + 2 * CT < in_w) ? vright[p] : OUT_OF_RANGE;
-        dm[buf][p][i] = __builtin_bit_cast(float2, __builtin_amdgcn_raw_buffer_load_b64(xrsrc, vm, soff, 0));
+        if constexpr (RAGGED) {        // columns past the input plane read as zeros
+            const unsigned vm0 = col + 2 * t < in_w ? vm : OUT_OF_RANGE, vm1 = col + 2 * t + 1 < in_w ? vm + 4u : OUT_OF_RANGE;
+            dm[buf][p][i].x = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(xrsrc, vm0, soff, 0));
+            dm[buf][p][i].y = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(xrsrc, vm1, soff, 0));
+        } else {
+            dm[buf][p][i] = __builtin_bit_cast(float2, __builtin_amdgcn_raw_buffer_load_b64(xrsrc, vm, soff, 0));
+        }
         dlr[buf][p][i].x = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(xrsrc, vl, col > 0 ? soff - 4 : soff, 0));
         dlr[buf][p][i].y = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(xrsrc, vr, soff, 0));
     };
     auto load_dy_row = [&](auto buf_c, int p, int r) {
         constexpr int buf = decltype(buf_c)::value;
         const int soff = (int)((((long long)ln * K) * plane + (long long)(2 * lty + r) * W + 2 * ltx) * 4);
-        gy[buf][p][r] = __builtin_bit_cast(float2, __builtin_amdgcn_raw_buffer_load_b64(yrsrc, loaded <= last ? vdy[p] : OUT_OF_RANGE, soff, 0));
+        if constexpr (RAGGED) {        // rows past H and columns past W read as zeros
+            const bool ok = loaded <= last && 2 * lty + r < H;
+            const int c0 = 2 * ltx + 2 * t;
+            const unsigned v0 = (ok && c0 < W) ? vdy[p] : OUT_OF_RANGE, v1 = (ok && c0 + 1 < W) ? vdy[p] + 4u : OUT_OF_RANGE;
+            gy[buf][p][r].x = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(yrsrc, v0, soff, 0));
+            gy[buf][p][r].y = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(yrsrc, v1, soff, 0));
+        } else {
+            gy[buf][p][r] = __builtin_bit_cast(float2, __builtin_amdgcn_raw_buffer_load_b64(yrsrc, loaded <= last ? vdy[p] : OUT_OF_RANGE, soff, 0));
+        }
     };
     auto load_all = [&](auto buf_c) {
 #pragma unroll
@@ -298,7 +324,7 @@ void conv3x3_wrw(const float* __restrict__ x, const float* __restrict__ dy, floa
 #pragma unroll
     for (int f = 0; f < 16; ++f) asm volatile("" : "+a"(acc[f]));
     asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-    if (DBG) t_pro = __builtin_readcyclecounter();
+    if (STAMPS) t_pro = __builtin_readcyclecounter();
 
     // LDS byte addresses (dynamic LDS starts at address 0) of the lane's operand rows: [kk = lane / 32][h = 0][row], one base
     // register per operand and stage, every group's block an immediate offset (< 64 KB).  Kept opaque to the optimiser:
@@ -360,18 +386,18 @@ void conv3x3_wrw(const float* __restrict__ x, const float* __restrict__ dy, floa
                 if (j == 3) { transform_x_cols(1); transform_dy(nb_c, 0); transform_dy(nb_c, 1); }
             }
             __builtin_amdgcn_sched_barrier(0);
-            if (DBG == 2 && ch >= 2 && ch < 4 && tid == 0) stamps[64 * (long long)blockIdx.x + 30 + 16 * (ch - 2) + j] = __builtin_readcyclecounter();
+            if (STAMPS == 2 && ch >= 2 && ch < 4 && tid == 0) stamps[64 * (long long)blockIdx.x + 30 + 16 * (ch - 2) + j] = __builtin_readcyclecounter();
         }
         if (!PAIR || nb == 1) advance();
         asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-        if (DBG && tid == 0 && ch < 26) stamps[64 * (long long)blockIdx.x + 4 + ch] = __builtin_readcyclecounter();
+        if (STAMPS && tid == 0 && ch < 26) stamps[64 * (long long)blockIdx.x + 4 + ch] = __builtin_readcyclecounter();
     };
     for (int ch = 0; ch < nch; ch += 2) {       // (a separate tail chunk makes the allocator route accumulators through scratch)
         chunk(ch, B0, B1);
         chunk(ch + 1, B1, B0);
     }
     asm volatile("s_nop 15\n\ts_nop 15" ::: "memory");
-    if (DBG) t_loop = __builtin_readcyclecounter();
+    if (STAMPS) t_loop = __builtin_readcyclecounter();
 
     // ---- epilogue: G^T m G per lane.  acc[4r + col][j]: transform position (r, col) of (k, c) with
     // k = 8 (j / 4) + 4 (lane / 32) + j % 4, c = lane % 32 of the wave's block; positions of row 3 or column 3 (not both)
@@ -411,7 +437,7 @@ void conv3x3_wrw(const float* __restrict__ x, const float* __restrict__ dy, floa
             if (t == 0) wsb[(long long)sp * Kpad + kb * 64 + 16 * wave + 8 * p + cl] = v;
         }
     }
-    if (DBG && tid == 0) {
+    if (STAMPS && tid == 0) {
         long long* st = stamps + 64 * (long long)blockIdx.x;
         st[0] = t_entry; st[1] = t_pro; st[2] = t_loop; st[3] = __builtin_readcyclecounter();
     }

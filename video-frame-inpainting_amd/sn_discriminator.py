@@ -111,10 +111,12 @@ def _conv_ops():
 # dimension, so tap t of the 4-tap filter sits at (T, r) with 2 T + r = t + 1 and the two other (T, r) slots hold zeros.  That 3x3 layer
 # runs on the in-tree Winograd kernels -- F(4x4, 3x3) hands the fp32 MFMA 36 / 16 x 4 C = 9 C multiply-adds per output and filter
 # where the direct form has 16 C -- forward, input gradient (the same kernels with the weight transposed) and weight gradient
-# (tai_conv3x3_wino_wrw, then folded back to [K, C, 4, 4]); bit-reproducible, which MIOpen's backward kernels are not.
+# (tai_conv3x3_wino_wrw, then folded back to [K, C, 4, 4]); bit-reproducible, which MIOpen's backward kernels are not.  Even H and W
+# suffice: the space-to-depth plane may then have an odd side, which both kernels take (the last layer at 160 x 208 frames: 10 x 13).
 def _s2d_applies(x, w, stride, padding):
+    m = 2 if _conv_ops().RAGGED_ROUTES[0] else 4          # (conv_ops.RAGGED_ROUTES off: multiples of 4, as before)
     return (x.is_cuda and x.dtype == torch.float32 and tuple(w.shape[2:]) == (4, 4) and tuple(stride) == (2, 2) and tuple(padding) == (1, 1)
-            and x.shape[2] % 4 == 0 and x.shape[3] % 4 == 0)
+            and x.shape[2] % m == 0 and x.shape[3] % m == 0)
 
 
 def _s2d_weight(w):
@@ -180,10 +182,12 @@ class _WindowScaledConvLReLU(torch.autograd.Function):
             xs = w3 = None
             y = F.conv2d(x, w0, None, stride, padding).contiguous()
         N, Co, H, W = y.shape
+        # (HW % 4 != 0: the one-element-per-thread form, e.g. the last layer's 10 x 13 output at 160 x 208 frames)
+        tail = 'tai_window_scale_bias_lrelu' if (H * W) % 4 == 0 else 'tai_window_scale_bias_lrelu_scalar'
         with torch.cuda.device(y.device):
-            _native.check(_native.lib().tai_window_scale_bias_lrelu(
+            _native.check(getattr(_native.lib(), tail)(
                 y.data_ptr(), bias.data_ptr(), inv_scale.data_ptr(), nw, N // nw, Co, H * W, float(slope),
-                torch.cuda.current_stream(y.device).cuda_stream), 'tai_window_scale_bias_lrelu')
+                torch.cuda.current_stream(y.device).cuda_stream), tail)
         ctx.s2d = xs is not None
         if ctx.s2d:
             ctx.save_for_backward(x, w0, inv_scale, y, xs, w3)
@@ -201,15 +205,16 @@ class _WindowScaledConvLReLU(torch.autograd.Function):
         g = g.contiguous()
         N, Co, H, W = g.shape
         gz, gs = torch.empty_like(g), torch.empty_like(g)
+        tail = 'tai_window_scale_lrelu_backward' if (H * W) % 4 == 0 else 'tai_window_scale_lrelu_backward_scalar'
         with torch.cuda.device(g.device):
-            _native.check(_native.lib().tai_window_scale_lrelu_backward(
+            _native.check(getattr(_native.lib(), tail)(
                 g.data_ptr(), y.data_ptr(), inv_scale.data_ptr(), gz.data_ptr(), gs.data_ptr(), nw, N // nw, Co, H * W, slope,
-                torch.cuda.current_stream(g.device).cuda_stream), 'tai_window_scale_lrelu_backward')
+                torch.cuda.current_stream(g.device).cuda_stream), tail)
         gx = gw = gb = None
         conv_bwd = torch.ops.aten.convolution_backward
         if ctx.needs_input_grad[1]:
             if ctx.s2d:                 # the 3x3 layer's Winograd-domain weight gradient (and the bias gradient with it), folded back to 4x4
-                both = _conv_ops().wino_weight_grad(xs, gz, with_bias=bool(ctx.needs_input_grad[3]))
+                both = _conv_ops().wino_weight_grad(xs, gz, with_bias=bool(ctx.needs_input_grad[3]), ragged=True)
                 if both is not None:
                     g3, gb = both if ctx.needs_input_grad[3] else (both, None)
                     gw = _s2d_weight_grad(g3, x.shape[1])
@@ -328,7 +333,8 @@ class SNDiscriminator(nn.Module):
                 nxt = layers[i + 1] if i + 1 < len(layers) else None
                 oh = (x.shape[2] + 2 * layer.padding[0] - layer.kernel_size[0]) // layer.stride[0] + 1
                 ow = (x.shape[3] + 2 * layer.padding[1] - layer.kernel_size[1]) // layer.stride[1] + 1
-                if isinstance(nxt, nn.LeakyReLU) and layer.bias is not None and (oh * ow) % 4 == 0:
+                # (any plane: the tail has a one-element-per-thread form; conv_ops.RAGGED_ROUTES off: as before, HW % 4 == 0 only)
+                if isinstance(nxt, nn.LeakyReLU) and layer.bias is not None and (_conv_ops().RAGGED_ROUTES[0] or (oh * ow) % 4 == 0):
                     x = _WindowScaledConvLReLU.apply(x, layer.weight, w0, layer.bias, inv_scale, nw, layer.stride, layer.padding,
                                                      nxt.negative_slope)
                     i += 2
