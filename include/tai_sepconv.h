@@ -275,6 +275,22 @@ int tai_conv3x3_wino43_set_waves(int waves);
  * run of tile blocks (forward) / whole splits (weight gradient); 0 = the plain dispatch order of rounds 4-5.  Same results; for A/B timing.
  * Returns the previous value. */
 int tai_conv3x3_wino43_set_placement(int xcd_aware);
+/* The F(4x4, 3x3) forward with a split of its reduction over the input channels on small grids: workgroup (split, tile block, channel
+ * block) runs a contiguous run of the 4-channel chunks and writes its partial output tiles to ``workspace``; a second kernel sums them
+ * in split order (the same bits on every run and replay) and applies bias, activation and the second outputs of
+ * tai_conv3x3_wino43_forward_ex (same arguments).  The split count comes from the grid: 1 where the grid already fills the chip, and
+ * then the call is tai_conv3x3_wino43_forward_ex exactly.  ``workspace`` holds at least tai_conv3x3_wino43_workspace_floats(N, C, K, H,
+ * W, nparts) floats (0: none needed, NULL allowed); the caller allocates it (no allocation inside, e.g. under graph capture). */
+int tai_conv3x3_wino43_forward_ws(const float* const* xs, int nparts, const float* U, const float* bias, float* y, float* ypool,
+                                  const float* addx, float* y2, float* workspace, long long workspace_floats, int N, int C, int K, int H,
+                                  int W, int act, void* hip_stream);
+long long tai_conv3x3_wino43_workspace_floats(int N, int C, int K, int H, int W, int nparts);
+/* The split count tai_conv3x3_wino43_forward_ws uses for this layer (1: none); *chunks_per_split (if not NULL): the 4-channel chunks of
+ * each split but the last, which may hold fewer. */
+int tai_conv3x3_wino43_splits(int N, int C, int K, int H, int W, int nparts, int* chunks_per_split);
+/* Split over input channels on (1, default) or off (0: tai_conv3x3_wino43_forward_ws never splits; round 5's dispatch), process-wide.
+ * A graph captured before a switch keeps what it captured.  For A/B timing.  Returns the previous value. */
+int tai_conv3x3_wino43_set_splitc(int on);
 /* ... with the input given as 1 to 4 equal channel parts (contiguous [N, C / nparts, H, W] tensors; C / nparts a multiple of 4): the
  * operands of a torch.cat along the channels that is never materialised (tai_conv3x3_wino_forward_parts' counterpart). */
 int tai_conv3x3_wino43_forward_parts(const float* const* xs, int nparts, const float* U, const float* bias, float* y, int N, int C, int K,

@@ -223,6 +223,14 @@ def lib():
     L.tai_conv3x3_wino_wrw_set_paired.restype = I
     L.tai_conv3x3_wino43_set_placement.argtypes = [I]
     L.tai_conv3x3_wino43_set_placement.restype = I
+    L.tai_conv3x3_wino43_set_splitc.argtypes = [I]
+    L.tai_conv3x3_wino43_set_splitc.restype = I
+    L.tai_conv3x3_wino43_splits.argtypes = [I] * 6 + [P]
+    L.tai_conv3x3_wino43_splits.restype = I
+    L.tai_conv3x3_wino43_workspace_floats.argtypes = [I] * 6
+    L.tai_conv3x3_wino43_workspace_floats.restype = ctypes.c_longlong
+    L.tai_conv3x3_wino43_forward_ws.argtypes = [P, I, P, P, P, P, P, P, P, ctypes.c_longlong, I, I, I, I, I, I, V]
+    L.tai_conv3x3_wino43_forward_ws.restype = I
     L.tai_conv3x3_wino_wrw_set_tile.argtypes = [I]
     L.tai_conv3x3_wino_wrw_set_tile.restype = I
     L.tai_window_scale_bias_lrelu.argtypes = [P, P, P, I, I, I, I, ctypes.c_float, V]

@@ -74,6 +74,9 @@ WINO43_MIN_CHANNELS = 64         # F(4x4, 3x3) where both C and K are at least t
                                  # profiles/r05_wino_f43_points_study.txt, r05_wino43_min_channels.txt; 49.7 -> 46.75 ms on the configs[1] forward)
 WINO43_MIN_WORKGROUPS = 150      # ... and where its 64-channel x 32-tile workgroups occupy most of the chip (round 5's kernel, same box, the
                                  # replayed configs[1] forward: 400: 51.11 ms, 256: 50.78, 150: 50.57, 100: 51.32, 64: 51.75 -- tools/w43_threshold_ab.py)
+WINO43_SPLIT_MIN_WORKGROUPS = 150   # MC-Net's own layers take the split over input channels (_wino43_launch) only from this many unsplit
+                                 # workgroups: the layers the default dispatch puts on F(4x4, 3x3) by themselves.  A layer that is on it only
+                                 # because a caller lowered WINO43_MIN_WORKGROUPS keeps the unsplit kernel and its bits.
 
 
 def set_weight_gradient_tile(m):
@@ -115,11 +118,44 @@ def mark_outside_recurrence(module):
         p._tai_f43_any_width = True
 
 
-def _wino43_ok(N, Ci, Co, H, W, nparts=1, weight=None):
-    wide = (Ci >= WINO43_MIN_CHANNELS and Co >= WINO43_MIN_CHANNELS) or (Ci >= 16 and getattr(weight, '_tai_f43_any_width', False))
-    return (_WINO_TILE[0] == 4 and wide and H % 4 == 0 and W % 4 == 0
-            and Ci % nparts == 0 and ((Ci // nparts) % 4 == 0 or nparts == 1) and N * max(Ci, Co) * H * W < 2 ** 29
-            and ((N * (H // 4) * (W // 4) + 31) // 32) * ((Co + 63) // 64) >= WINO43_MIN_WORKGROUPS)
+def _wino43_ok(N, Ci, Co, H, W, nparts=1, weight=None, split=True):
+    """F(4x4, 3x3) for this layer?  ``split``: the caller launches through _wino43_launch (the split over input channels on small grids);
+    the autograd paths pass False: their launches never split, so a layer's training arithmetic does not depend on the batch size."""
+    any_width = getattr(weight, '_tai_f43_any_width', False)
+    wide = (Ci >= WINO43_MIN_CHANNELS and Co >= WINO43_MIN_CHANNELS) or (Ci >= 16 and any_width)
+    if not (_WINO_TILE[0] == 4 and wide and H % 4 == 0 and W % 4 == 0
+            and Ci % nparts == 0 and ((Ci // nparts) % 4 == 0 or nparts == 1) and N * max(Ci, Co) * H * W < 2 ** 29):
+        return False
+    groups = ((N * (H // 4) * (W // 4) + 31) // 32) * ((Co + 63) // 64)
+    if groups >= WINO43_MIN_WORKGROUPS:
+        return True
+    # below the threshold: a layer outside MC-Net's recurrence counts its workgroups after the split over input channels
+    # (tai_conv3x3_wino43_splits); MC-Net's own layers there keep F(2x2, 3x3), whose rounding the T = 10 parity margin was measured on
+    return split and bool(any_width) and groups * _native.lib().tai_conv3x3_wino43_splits(N, Ci, Co, H, W, nparts, None) >= WINO43_MIN_WORKGROUPS
+
+
+def _wino43_launch(ptrs, nparts, U, bias, y, N, C, K, H, W, act, stream, weight, ypool=None, addx=None, y2=None):
+    """One F(4x4, 3x3) forward (tai_conv3x3_wino43_forward_ws).  Where the library splits the input channels over more workgroups
+    (small grids) it needs a workspace for the partial tiles: allocated here with torch, so that under graph capture it comes
+    from the graph's pool.  ``ptrs``: a ctypes array of the nparts input pointers."""
+    L = _native.lib()
+    groups = ((N * (H // 4) * (W // 4) + 31) // 32) * ((K + 63) // 64)
+    if groups < WINO43_SPLIT_MIN_WORKGROUPS and not getattr(weight, '_tai_f43_any_width', False):
+        _native.check(L.tai_conv3x3_wino43_forward_ex(ptrs, nparts, U.data_ptr(), bias.data_ptr(), y.data_ptr(),
+                                                      ypool.data_ptr() if ypool is not None else None,
+                                                      addx.data_ptr() if addx is not None else None,
+                                                      y2.data_ptr() if y2 is not None else None, N, C, K, H, W, act, stream),
+                      'tai_conv3x3_wino43_forward_ex')
+        return
+    n = L.tai_conv3x3_wino43_workspace_floats(N, C, K, H, W, nparts)
+    _native.check(n if n < 0 else 0, 'tai_conv3x3_wino43_workspace_floats')
+    ws = torch.empty(n, dtype=torch.float32, device=y.device) if n > 0 else None
+    _native.check(L.tai_conv3x3_wino43_forward_ws(ptrs, nparts, U.data_ptr(), bias.data_ptr(), y.data_ptr(),
+                                                  ypool.data_ptr() if ypool is not None else None,
+                                                  addx.data_ptr() if addx is not None else None,
+                                                  y2.data_ptr() if y2 is not None else None,
+                                                  ws.data_ptr() if ws is not None else None, n, N, C, K, H, W, act, stream),
+                  'tai_conv3x3_wino43_forward_ws')
 
 
 def _cached(weight, tag, make):
@@ -390,9 +426,8 @@ def conv_bias_unpool_add(x, weight, bias, padding, addx, keep_plain=True):
     if _wino43_ok(N, Ci, Co, H, W, len(parts), weight):      # wide layer: F(4x4, 3x3) (set_winograd_tile): a tile holds four unpooling cells
         U = _wino43_weights(weight, False)
         with torch.cuda.device(x0.device):
-            _native.check(L.tai_conv3x3_wino43_forward_ex(ptrs, len(parts), U.data_ptr(), bias.data_ptr(), y.data_ptr(), None, addx.data_ptr(),
-                                                          y2.data_ptr() if keep_plain else None, N, Ci, Co, H, W, 0,
-                                                          torch.cuda.current_stream(x0.device).cuda_stream), 'tai_conv3x3_wino43_forward_ex')
+            _wino43_launch(ptrs, len(parts), U, bias, y, N, Ci, Co, H, W, 0, torch.cuda.current_stream(x0.device).cuda_stream, weight,
+                           addx=addx, y2=y2 if keep_plain else None)
         return (y, y2) if keep_plain else (None, y)
     U = _wino_weights(weight, False)
     with torch.cuda.device(x0.device):
@@ -478,7 +513,7 @@ WINO43_UNDER_AUTOGRAD = True
 
 def _conv3x3_autograd_launch(x, weight, eff_transposed, bias, N, Ci, Co, H, W, act):
     """conv(x, w_eff) with w_eff = the weight in orientation ``eff_transposed``: F(4x4, 3x3) where _wino43_ok says so, else F(2x2, 3x3)."""
-    if WINO43_UNDER_AUTOGRAD and _wino43_ok(N, Ci, Co, H, W, 1, weight):
+    if WINO43_UNDER_AUTOGRAD and _wino43_ok(N, Ci, Co, H, W, 1, weight, split=False):
         y = torch.empty((N, Co, H, W), dtype=x.dtype, device=x.device)
         with torch.cuda.device(x.device):
             _native.check(_native.lib().tai_conv3x3_wino43_forward(x.data_ptr(), _wino43_weights(weight, eff_transposed).data_ptr(), bias.data_ptr(),
@@ -499,7 +534,7 @@ def wino_conv3x3_plain(x, weight, transposed=False):
     Co = weight.shape[1] if transposed else weight.shape[0]
     if (weight.shape[0] if transposed else weight.shape[1]) != Ci or tuple(weight.shape[2:]) != (3, 3):
         raise ValueError('wino_conv3x3_plain: weight %s does not fit input %s' % (tuple(weight.shape), tuple(x.shape)))
-    if not ((WINO43_UNDER_AUTOGRAD and _wino43_ok(N, Ci, Co, H, W, 1, weight)) or _wino_ok(N, Ci, Co, H, W, 3, 3, 1, ragged=True)):
+    if not ((WINO43_UNDER_AUTOGRAD and _wino43_ok(N, Ci, Co, H, W, 1, weight, split=False)) or _wino_ok(N, Ci, Co, H, W, 3, 3, 1, ragged=True)):
         return None
     return _conv3x3_autograd_launch(x, weight, transposed, _zero_bias(Co, x.device), N, Ci, Co, H, W, None)
 
@@ -646,7 +681,7 @@ class _WinoConv3x3Parts(torch.autograd.Function):
         y = torch.empty((N, Co, H, W), dtype=x0.dtype, device=x0.device)
         ptrs = (ctypes.c_void_p * len(parts))(*[p.data_ptr() for p in parts])
         with torch.cuda.device(x0.device):
-            if WINO43_UNDER_AUTOGRAD and _wino43_ok(N, Ci, Co, H, W, len(parts), weight):
+            if WINO43_UNDER_AUTOGRAD and _wino43_ok(N, Ci, Co, H, W, len(parts), weight, split=False):
                 _native.check(L.tai_conv3x3_wino43_forward_parts(ptrs, len(parts), _wino43_weights(weight, transposed).data_ptr(), bias.data_ptr(),
                                                                  y.data_ptr(), N, Ci, Co, H, W, _ACT[act],
                                                                  torch.cuda.current_stream(x0.device).cuda_stream), 'tai_conv3x3_wino43_forward_parts')
@@ -672,7 +707,7 @@ class _WinoConv3x3Parts(torch.autograd.Function):
         gparts = [None] * n
         for i in range(n):
             if ctx.needs_input_grad[4 + i]:
-                if WINO43_UNDER_AUTOGRAD and _wino43_ok(N, Co, Cp, H, W, 1, weight):
+                if WINO43_UNDER_AUTOGRAD and _wino43_ok(N, Co, Cp, H, W, 1, weight, split=False):
                     gparts[i] = torch.empty((N, Cp, H, W), dtype=g.dtype, device=g.device)
                     with torch.cuda.device(g.device):
                         _native.check(_native.lib().tai_conv3x3_wino43_forward(
@@ -959,8 +994,7 @@ def conv_bias_act_maxpool(x, weight, bias, padding, act):
                 elif kh == kw == 3 and padding == 1 and _wino43_ok(N, Ci, Co, H, W, 1, weight):      # wide layer: F(4x4, 3x3): a tile is four pooling windows
                     U = _wino43_weights(weight, False)
                     xs = (ctypes.c_void_p * 1)(x.data_ptr())
-                    _native.check(L.tai_conv3x3_wino43_forward_ex(xs, 1, U.data_ptr(), bias.data_ptr(), y.data_ptr(), yp.data_ptr(), None, None,
-                                                                  N, Ci, Co, H, W, _ACT[act], stream), 'tai_conv3x3_wino43_forward_ex')
+                    _wino43_launch(xs, 1, U, bias, y, N, Ci, Co, H, W, _ACT[act], stream, weight, ypool=yp)
                 else:
                     U = _wino_weights(weight, False)
                     _native.check(L.tai_conv3x3_wino_forward_maxpool(x.data_ptr(), U.data_ptr(), bias.data_ptr(), y.data_ptr(),
@@ -1016,9 +1050,8 @@ def _conv_bias_act(x, weight, bias, padding, act, transposed, out):
         with torch.cuda.device(x0.device):
             if _wino43_ok(N, Ci, Co, H, W, len(parts), weight):      # wide layer: F(4x4, 3x3) (set_winograd_tile)
                 U = _wino43_weights(weight, transposed)
-                _native.check(L.tai_conv3x3_wino43_forward_parts(ptrs, len(parts), U.data_ptr(), bias.data_ptr(), y.data_ptr(), N, Ci,
-                                                                 Co, H, W, _ACT[act], torch.cuda.current_stream(x0.device).cuda_stream),
-                              'tai_conv3x3_wino43_forward_parts')
+                _wino43_launch(ptrs, len(parts), U, bias, y, N, Ci, Co, H, W, _ACT[act], torch.cuda.current_stream(x0.device).cuda_stream,
+                               weight)
                 return y
             U = _wino_weights(weight, transposed)
             _native.check(L.tai_conv3x3_wino_forward_parts(ptrs, len(parts), U.data_ptr(), bias.data_ptr(), y.data_ptr(), N, Ci,
@@ -1080,8 +1113,7 @@ def _conv_bias_act(x, weight, bias, padding, act, transposed, out):
         with torch.cuda.device(x.device):
             if _wino43_ok(N, Ci, Co, H, W, 1, weight):       # wide layer: F(4x4, 3x3) (set_winograd_tile)
                 U = _wino43_weights(weight, transposed)
-                _native.check(L.tai_conv3x3_wino43_forward(x.data_ptr(), U.data_ptr(), bias.data_ptr(), y.data_ptr(), N, Ci, Co,
-                                                           H, W, _ACT[act], stream), 'tai_conv3x3_wino43_forward')
+                _wino43_launch((ctypes.c_void_p * 1)(x.data_ptr()), 1, U, bias, y, N, Ci, Co, H, W, _ACT[act], stream, weight)
                 return y
             U = _wino_weights(weight, transposed)
             _wino_forward(L, x, U, bias, y, N, Ci, Co, H, W, act, stream)

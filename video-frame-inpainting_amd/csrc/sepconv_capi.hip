@@ -728,8 +728,63 @@ int tai_conv3x3_wino43_set_waves(int waves) {
 static std::atomic<int> g_wino43_placement{1};
 int tai_conv3x3_wino43_set_placement(int xcd_aware) { return g_wino43_placement.exchange(xcd_aware ? 1 : 0, std::memory_order_relaxed); }
 
+// Split of the forward's reduction over input channels (tai_conv3x3_wino43_forward_ws, wino43::conv3x3_gen<..., SPLITC>): 1 (default) =
+// where the grid of 64-channel x 32-tile workgroups leaves CUs idle, 0 = never (the dispatch of round 5).  For A/B timing.
+static std::atomic<int> g_wino43_splitc{1};
+int tai_conv3x3_wino43_set_splitc(int on) { return g_wino43_splitc.exchange(on ? 1 : 0, std::memory_order_relaxed); }
+
+// The split count.  A workgroup holds a CU (108 KB of LDS), so a grid of B workgroups runs in ceil(B / 256) rounds; with S splits of c
+// chunks each it runs ceil(B S / 256) rounds of c chunks, and every split writes its partial tiles and the reduction reads them back.
+// Cost in chunk times of a full round: ceil(B S / 256) (c + 2) (+2: the loop's fill and the inverse transform) plus, for S > 1,
+// B (2 S + 1) / 64 (the partials of a workgroup, 128 KB, are ~1/64 of a chunk time of the whole chip in memory traffic, written once and
+// read once, plus the final write).  The cheapest S wins if it saves 5 % on S = 1; large grids keep S = 1.  Splits hold at least
+// W43_MIN_SPLIT_CHUNKS chunks and break on part boundaries (the chunks of a split lie in one part, or are whole parts).
+struct W43Split { int splits, chunks_per_split; };
+constexpr int W43_MIN_SPLIT_CHUNKS = 8, W43_MAX_SPLITS = 16;
+static W43Split wino43_split_plan(int N, int C, int K, int H, int W, int nparts) {
+    const int nchunks = C > 0 ? (C + wino43::KC - 1) / wino43::KC : 0;
+    const W43Split one{1, nchunks};
+    if (!g_wino43_splitc.load(std::memory_order_relaxed) || N <= 0 || C <= 0 || K <= 0 || H <= 0 || W <= 0 || H % 4 != 0 || W % 4 != 0 ||
+        nparts < 1 || nparts > 4 || C % nparts != 0 || (nparts > 1 && (C / nparts) % wino43::KC != 0))
+        return one;
+    const int cpp = nparts == 1 ? nchunks : C / nparts / wino43::KC;
+    const long long blocks = ((long long)N * (H / 4) * (W / 4) + wino43::TN - 1) / wino43::TN * ((K + wino43::TM - 1) / wino43::TM);
+    auto cost = [&](int sp, int cps) {
+        return (double)((blocks * sp + 255) / 256) * (cps + 2) + (sp > 1 ? (double)blocks * (2 * sp + 1) / 64.0 : 0.0);
+    };
+    const double c1 = cost(1, nchunks);
+    double best = c1;
+    W43Split pick = one;
+    for (int want = 2; want <= W43_MAX_SPLITS; ++want) {
+        int cps = (nchunks + want - 1) / want;
+        if (nparts > 1) {
+            if (cps < cpp) { while (cpp % cps != 0) ++cps; }       // a divisor of the part's chunks ...
+            else cps = (cps + cpp - 1) / cpp * cpp;                 // ... or whole parts
+        }
+        if (cps < W43_MIN_SPLIT_CHUNKS) break;
+        const int sp = (nchunks + cps - 1) / cps;
+        if (sp < 2) continue;
+        const double c = cost(sp, cps);
+        if (c < best) { best = c; pick = W43Split{sp, cps}; }
+    }
+    return best <= 0.95 * c1 ? pick : one;
+}
+
+int tai_conv3x3_wino43_splits(int N, int C, int K, int H, int W, int nparts, int* chunks_per_split) {
+    const W43Split sc = wino43_split_plan(N, C, K, H, W, nparts);
+    if (chunks_per_split) *chunks_per_split = sc.chunks_per_split;
+    return sc.splits;
+}
+
+long long tai_conv3x3_wino43_workspace_floats(int N, int C, int K, int H, int W, int nparts) {
+    const W43Split sc = wino43_split_plan(N, C, K, H, W, nparts);
+    return sc.splits > 1 ? (long long)sc.splits * N * K * H * W : 0;
+}
+
+// ws_floats < 0: the entry points without a workspace (never split); else tai_conv3x3_wino43_forward_ws
 static int wino43_forward_impl(const float* const* xs, int nparts, const float* U, const float* bias, float* y, int N, int C, int K, int H,
-                               int W, int act, void* hip_stream, float* ypool = nullptr, const float* addx = nullptr, float* y2 = nullptr) {
+                               int W, int act, void* hip_stream, float* ypool = nullptr, const float* addx = nullptr, float* y2 = nullptr,
+                               float* ws = nullptr, long long ws_floats = -1) {
     if (!xs || !xs[0] || !U || !bias || !y || N <= 0 || C <= 0 || K <= 0 || H <= 0 || W <= 0 || nparts < 1 || nparts > 4)
         return fail(TAI_SEPCONV_EINVAL, "%s", "conv3x3_wino43: bad argument (1 to 4 input parts)");
     // one tensor: any C (the transformed weights of the channels past C are zero and the loads of those channels past the tensor's end
@@ -777,6 +832,34 @@ static int wino43_forward_impl(const float* const* xs, int nparts, const float* 
     }
 #undef TAI_W43_LAUNCH_VAR
 #endif
+    const W43Split sc = ws_floats >= 0 ? wino43_split_plan(N, C, K, H, W, nparts) : W43Split{1, nchunks};
+    if (sc.splits > 1) {
+        if (!ws || ws_floats < (long long)sc.splits * N * K * H * W)
+            return fail(TAI_SEPCONV_EINVAL, "%s", "conv3x3_wino43_forward_ws: workspace missing or smaller than tai_conv3x3_wino43_workspace_floats");
+        wino43::Window win = plain_win;
+        win.splits = sc.splits;
+        win.chunks_per_split = sc.chunks_per_split;
+        auto kern = wino43::conv3x3_gen<0, 0, 0, false, true>;
+        if (int rc = allow_lds(kern, wino43::LDS_BYTES)) return rc;
+        hipLaunchKernelGGL(kern, dim3((unsigned)(tblocks * kblocks * sc.splits)), dim3(512), wino43::LDS_BYTES, s, p[0], p[1], p[2], p[3],
+                           cpart, U, bias, ws, N, C, K, H, W, Kpad, nchunks, kblocks, (float*)nullptr, (const float*)nullptr,
+                           (float*)nullptr, win);
+        if (int rc = check_launch("conv3x3_wino43 (split over input channels)")) return rc;
+        const long long work = (long long)N * K * (H / 4) * (W / 4);
+        const unsigned rblocks = (unsigned)((work + 255) / 256 < 65536 ? (work + 255) / 256 : 65536);
+#define TAI_W43_LAUNCH_REDUCE(A, E)                                                                                             \
+        hipLaunchKernelGGL((wino43::splitc_reduce<A, E>), dim3(rblocks), dim3(256), 0, s, ws, sc.splits, bias, y, N, K, H, W, ypool, \
+                           addx, y2);
+        if (ypool) {
+            if (act == 0) TAI_W43_LAUNCH_REDUCE(0, 1) else TAI_W43_LAUNCH_REDUCE(1, 1)
+        } else if (addx) {
+            if (y2) TAI_W43_LAUNCH_REDUCE(0, 2) else TAI_W43_LAUNCH_REDUCE(0, 3)
+        } else {
+            if (act == 0) TAI_W43_LAUNCH_REDUCE(0, 0) else if (act == 1) TAI_W43_LAUNCH_REDUCE(1, 0) else TAI_W43_LAUNCH_REDUCE(2, 0)
+        }
+#undef TAI_W43_LAUNCH_REDUCE
+        return check_launch("conv3x3_wino43_splitc_reduce");
+    }
     if (ypool) {
         if (act == 0) TAI_W43_LAUNCH_GEN(0, 1) else TAI_W43_LAUNCH_GEN(1, 1)
     } else if (addx) {
@@ -805,6 +888,14 @@ int tai_conv3x3_wino43_forward_ex(const float* const* xs, int nparts, const floa
                                   const float* addx, float* y2, int N, int C, int K, int H, int W, int act, void* hip_stream) {
     g_err[0] = 0;
     return wino43_forward_impl(xs, nparts, U, bias, y, N, C, K, H, W, act, hip_stream, ypool, addx, y2);
+}
+
+int tai_conv3x3_wino43_forward_ws(const float* const* xs, int nparts, const float* U, const float* bias, float* y, float* ypool,
+                                  const float* addx, float* y2, float* workspace, long long workspace_floats, int N, int C, int K, int H,
+                                  int W, int act, void* hip_stream) {
+    g_err[0] = 0;
+    if (workspace_floats < 0) return fail(TAI_SEPCONV_EINVAL, "%s", "conv3x3_wino43_forward_ws: negative workspace size");
+    return wino43_forward_impl(xs, nparts, U, bias, y, N, C, K, H, W, act, hip_stream, ypool, addx, y2, workspace, workspace_floats);
 }
 
 int tai_conv3x3_wino43_forward_blocks(const float* x, int shift_k, const float* U, const float* bias, float* y, float* ypool, int pool_h,

@@ -138,15 +138,22 @@ typedef unsigned u32x16 __attribute__((ext_vector_type(16)));
 // pixel under output (0, 0)'s centre tap of block (0, 0) at (in_oy, in_ox); C = S * S * cpart channels, channel block (a, b) = block
 // a * S + b reads the plane displaced by (3a, 3b) pixels: a k x k "same" convolution (k = 5, 7: MotionEnc, mcnet.py:36-47) with its
 // filter cut into S x S blocks of 3 x 3 taps, zero past k.  No bounds tests: the halo covers every read.
-struct Window { int in_h, in_w, in_oy, in_ox, S, pool_h, pool_w, pool_oy, pool_ox, zero_taps, dispatch_order; };   // zero_taps: 3 S > k (the last blocks carry zero taps); dispatch_order: A/B switch of the workgroup placement below
+struct Window { int in_h, in_w, in_oy, in_ox, S, pool_h, pool_w, pool_oy, pool_ox, zero_taps, dispatch_order, splits, chunks_per_split; };   // zero_taps: 3 S > k (the last blocks carry zero taps); dispatch_order: A/B switch of the workgroup placement below; splits, chunks_per_split: SPLITC below
 
-template <int ACT, int EPI = 0, int VAR = 0, bool BLOCKS = false>
+// SPLITC (split over input channels, small grids; tai_conv3x3_wino43_forward_ws): workgroup (split sp, tile block, channel block) runs the
+// same chunk loop over chunks sp * chunks_per_split ... (+ chunks_per_split, the last split fewer) and writes its un-biased 4 x 4 output
+// tiles, after the inverse transform, to y = the workspace [splits][N][K][H][W]; splitc_reduce sums them in split order and runs the
+// epilogue.  The host breaks splits on part boundaries (a split lies inside one part or covers whole parts), so the loop's per-part state
+// only starts at another part and a byte offset.  The other instantiations (SPLITC false) compile to the instruction stream they had.
+
+template <int ACT, int EPI = 0, int VAR = 0, bool BLOCKS = false, bool SPLITC = false>
 __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2)))
 void conv3x3_gen(const float* __restrict__ x, const float* __restrict__ x1, const float* __restrict__ x2, const float* __restrict__ x3,
                  int cpart, const float* __restrict__ U, const float* __restrict__ bias, float* __restrict__ y, int N,
                  int C, int K, int H, int W, int Kpad, int nchunks, int kblocks, float* __restrict__ ypool, const float* __restrict__ addx,
                  float* __restrict__ y2, Window win) {
     static_assert(TAI_W43_STAGE_BYTES == STAGE_FLOATS * 4, "generator and kernel disagree on the LDS stage");
+    static_assert(!(SPLITC && (BLOCKS || EPI != 0 || ACT != 0)), "the split form writes raw partial tiles of the plain form");
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wm = wave & 3, wn = wave >> 2, ch0 = wm * 16;
     // Workgroup -> (tile block tb, channel block kb).  The hardware deals consecutive workgroups to the 8 XCDs in turn (blockIdx % 8), each with
@@ -154,9 +161,23 @@ void conv3x3_gen(const float* __restrict__ x, const float* __restrict__ x1, cons
     // stay in that L2) and a CONTIGUOUS run of tile blocks (neighbouring tile rows share two of their six patch rows, and the run walks the
     // input like a stream); with 8, 16 ... channel blocks an XCD takes kblocks / 8 of them for every tile block.  Any placement gives the
     // same results (round 5; until then tb = blockIdx / kblocks, kb = blockIdx % kblocks).
-    int tb, kb;
+    int tb, kb, sp = 0;
     {
-        const int bid = blockIdx.x, nblk = gridDim.x, tblocks = nblk / kblocks, xcd = bid & 7, slot = bid >> 3;
+        int bid = blockIdx.x, nblk = gridDim.x;
+        if constexpr (SPLITC) {
+            // the splits of one (tile block, channel block) are consecutive workgroups of one XCD: the placement below then runs on the
+            // unsplit grid, the XCD's slot divided by the split count
+            nblk /= win.splits;
+            if (!win.dispatch_order && nblk % 8 == 0) {
+                const int s = bid >> 3;
+                sp = s % win.splits;
+                bid = (s / win.splits) * 8 + (bid & 7);
+            } else {
+                sp = bid % win.splits;
+                bid /= win.splits;
+            }
+        }
+        const int tblocks = nblk / kblocks, xcd = bid & 7, slot = bid >> 3;
         if (win.dispatch_order) {           // tai_conv3x3_wino43_set_placement(0): the placement of rounds 4-5 (A/B timing)
             tb = bid / kblocks;
             kb = bid - tb * kblocks;
@@ -210,18 +231,30 @@ void conv3x3_gen(const float* __restrict__ x, const float* __restrict__ x1, cons
     typedef int i32x16 __attribute__((ext_vector_type(16)));
     i32x16 sin;
     {
-        const unsigned long long b[4] = {reinterpret_cast<unsigned long long>(x), reinterpret_cast<unsigned long long>(x1),
-                                         reinterpret_cast<unsigned long long>(x2), reinterpret_cast<unsigned long long>(x3)};
+        unsigned long long b[4] = {reinterpret_cast<unsigned long long>(x), reinterpret_cast<unsigned long long>(x1),
+                                   reinterpret_cast<unsigned long long>(x2), reinterpret_cast<unsigned long long>(x3)};
+        int c0 = 0, nch = nchunks;            // this workgroup's chunks
+        if constexpr (SPLITC) {
+            c0 = sp * win.chunks_per_split;
+            nch = min(win.chunks_per_split, nchunks - c0);
+            // first part p0 at chunk o: the parts from p0 on move into slots 0.. (past the last part: never read), part p0's base moves
+            // o chunks on -- the same addresses and the same range check (the soffset is not in it) as the unsplit loop's at chunk c0
+            const int cpp = (cpart + KC - 1) / KC, p0 = c0 / cpp, o = c0 - p0 * cpp;
+            const unsigned long long q[4] = {b[0], b[1], b[2], b[3]};
+#pragma unroll
+            for (int i = 0; i < 4; ++i) b[i] = p0 + i == 1 ? q[1] : p0 + i == 2 ? q[2] : p0 + i == 3 ? q[3] : q[0];
+            b[0] += (unsigned long long)o * KC * plane * 4;
+        }
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             sin[2 * i] = __builtin_amdgcn_readfirstlane((int)(unsigned)b[i]);
             sin[2 * i + 1] = __builtin_amdgcn_readfirstlane((int)(unsigned)(b[i] >> 32));
         }
         const unsigned long long ub = reinterpret_cast<unsigned long long>(U) +
-            ((unsigned long long)kb * nchunks * (U_STAGE * 4) + (unsigned long long)(wave & 3) * 1024ull);
+            (((unsigned long long)kb * nchunks + c0) * (U_STAGE * 4) + (unsigned long long)(wave & 3) * 1024ull);
         sin[8] = __builtin_amdgcn_readfirstlane((int)((long long)N * cpart * plane * 4));      // bytes of a part (num_records)
         sin[9] = __builtin_amdgcn_readfirstlane((cpart + KC - 1) / KC);                         // chunks per part (one part: all of them)
-        sin[10] = __builtin_amdgcn_readfirstlane(nchunks);
+        sin[10] = __builtin_amdgcn_readfirstlane(nch);
         sin[11] = __builtin_amdgcn_readfirstlane((int)(KC * plane * 4));                        // bytes from one chunk's channels to the next
         sin[12] = __builtin_amdgcn_readfirstlane((int)(unsigned)ub);
         sin[13] = __builtin_amdgcn_readfirstlane((int)(unsigned)(ub >> 32));
@@ -275,8 +308,13 @@ void conv3x3_gen(const float* __restrict__ x, const float* __restrict__ x1, cons
         if (evalid && k < K) {                                                                                                  \
             const f4v raw[4] = {f4v{o[0], o[1], o[2], o[3]}, f4v{o[4], o[5], o[6], o[7]}, f4v{o[8], o[9], o[10], o[11]},        \
                                 f4v{o[12], o[13], o[14], o[15]}};                                                               \
-            finish_tile<ACT, EPI>(raw, k, eimg, ety, etx, bias, y, K, H, W, ypool, addx, y2, win.pool_h, win.pool_w, win.pool_oy,\
-                                  win.pool_ox);                                                                                 \
+            if constexpr (SPLITC) {                                                                                             \
+                float* wp = y + ((((long long)sp * N + eimg) * K + k) * H + 4 * ety) * W + 4 * etx;                             \
+                _Pragma("unroll") for (int i = 0; i < 4; ++i) *reinterpret_cast<f4v*>(wp + (long long)i * W) = raw[i];         \
+            } else {                                                                                                            \
+                finish_tile<ACT, EPI>(raw, k, eimg, ety, etx, bias, y, K, H, W, ypool, addx, y2, win.pool_h, win.pool_w,        \
+                                      win.pool_oy, win.pool_ox);                                                                \
+            }                                                                                                                   \
         }                                                                                                                       \
     }
     TAI_W43_INVERSE(0, TAI_W43_INVERSE_ASM_R0)
@@ -284,6 +322,33 @@ void conv3x3_gen(const float* __restrict__ x, const float* __restrict__ x1, cons
     TAI_W43_INVERSE(2, TAI_W43_INVERSE_ASM_R2)
     TAI_W43_INVERSE(3, TAI_W43_INVERSE_ASM_R3)
 #undef TAI_W43_INVERSE
+}
+
+// ---- SPLITC's second step: the partial tiles [splits][N][K][H][W] summed in split order (s = 0, 1, ...: the same bits on every run),
+// then finish_tile's bias, activation and second outputs.  One thread per (image, channel, 4 x 4 tile), the tile column fastest.
+template <int ACT, int EPI>
+__global__ __launch_bounds__(256) void splitc_reduce(const float* __restrict__ ws, int splits, const float* __restrict__ bias,
+                                                     float* __restrict__ y, int N, int K, int H, int W, float* __restrict__ ypool,
+                                                     const float* __restrict__ addx, float* __restrict__ y2) {
+    const int TH = H >> 2, TW = W >> 2;
+    const long long total = (long long)N * K * TH * TW, part = (long long)N * K * H * W;
+    for (long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (long long)gridDim.x * blockDim.x) {
+        const int etx = (int)(t % TW);
+        long long r = t / TW;
+        const int ety = (int)(r % TH);
+        r /= TH;
+        const int k = (int)(r % K), eimg = (int)(r / K);
+        const float* p = ws + (((long long)eimg * K + k) * H + 4 * ety) * W + 4 * etx;
+        f4v raw[4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) raw[i] = *reinterpret_cast<const f4v*>(p + (long long)i * W);
+        for (int s = 1; s < splits; ++s) {
+            p += part;
+#pragma unroll
+            for (int i = 0; i < 4; ++i) raw[i] += *reinterpret_cast<const f4v*>(p + (long long)i * W);
+        }
+        finish_tile<ACT, EPI>(raw, k, eimg, ety, etx, bias, y, K, H, W, ypool, addx, y2);
+    }
 }
 
 // ---- Weight gradient in the same transform domain (round 5; tools/gen_wino43_asm.py, "WRW"):
