@@ -376,6 +376,26 @@ long long tai_sepconv_backward_bytes(int B, int C, int H, int W, int ks);
  * held against on the box it runs on. */
 int tai_hbm_read_probe(const void* buffer, long long bytes, int nt, float* sink, void* hip_stream);
 
+/* Opt-in bf16 inference convolution (csrc/conv_bf16.hip.inc): k x k, stride 1, padding k / 2, k in {3, 5, 7}, C >= 16 input and
+ * K >= 16 output channels, any N, H, W >= 1.  y = act(bias + sum bf16(x) bf16(w)): operands rounded to bf16 to nearest even (NaN kept),
+ * products exact, sums in fp32 in an order fixed by (C, k), no split and no atomics; x, y and bias are fp32.  Replaces, where the
+ * caller opts in (conv_ops.set_conv_precision('bf16')), the inference forward of the generator's nn.Conv2d(C, K, k, padding=k // 2)
+ * [+ ReLU / Tanh] (mcnet.py:28-43,79-102,137-144,172-176,203-225; tai.py:256-261) and of DecCnn's stride-1
+ * nn.ConvTranspose2d(C, K, 3, padding=1) (mcnet.py:203-225).
+ * Element count (bf16) of the packed weights of a K x C x k x k layer; negative (TAI_SEPCONV_EINVAL) outside the rule above. */
+long long tai_conv_bf16_weight_elems(int K, int C, int k);
+/* Packs w into Wp (16-byte aligned, tai_conv_bf16_weight_elems bf16 elements): bf16 in the order the kernel's B fragments are read,
+ * zero past C, K and k^2.  transposed != 0: w is a ConvTranspose2d weight [C][K][k][k]; the pack folds in its transpose and flip. */
+int tai_conv_bf16_pack_weights(const float* w, void* Wp, int K, int C, int k, int transposed, void* hip_stream);
+/* The forward.  xs: 1-4 input parts [N][C / nparts][H][W], the operands of a torch.cat along the channels that is never materialised.
+ * act: 0 none, 1 ReLU, 2 tanh.  Epilogues, each selected by a non-NULL pointer (even H and W):
+ *   ypool [N][K][H/2][W/2]: the 2 x 2 max pool of y (the encoders' conv + ReLU + max pool, mcnet.py:28-43,79-102);
+ *   addx  [N][K][H/2][W/2]: y2 = y + fixed_unpool(addx) (addx on the even (2i, 2j) sites; Residual blocks and DecCnn,
+ *         mcnet.py:172-176,234-236); with y2 NULL, y receives the sum instead of the plain output.
+ * TAI_SEPCONV_EINVAL with a message outside the rule above or the index space (N C H W and N K H W below 2^31). */
+int tai_conv_bf16_forward(const float* const* xs, int nparts, const void* Wp, const float* bias, float* y, float* ypool,
+                          const float* addx, float* y2, int N, int C, int K, int H, int W, int k, int act, void* hip_stream);
+
 /* Text of the last error on the calling thread ("" if none). */
 const char* tai_sepconv_last_error(void);
 

@@ -47,6 +47,9 @@ def main(args=None):
     if getattr(opt, 'winograd_arithmetic', 'fp32') != 'fp32':
         from video_frame_inpainting_amd import conv_ops
         conv_ops.set_winograd_arithmetic(opt.winograd_arithmetic)
+    if getattr(opt, 'conv_precision', 'fp32') != 'fp32':
+        from video_frame_inpainting_amd import conv_ops
+        conv_ops.set_conv_precision(opt.conv_precision)
     if getattr(opt, 'winograd_tile', None) in (2, 4):
         from video_frame_inpainting_amd import conv_ops
         conv_ops.set_winograd_tile(opt.winograd_tile)

@@ -271,6 +271,12 @@ def lib():
     L.tai_sepconv_backward_bytes.restype = ctypes.c_longlong
     L.tai_hbm_read_probe.argtypes = [P, ctypes.c_longlong, I, P, V]
     L.tai_hbm_read_probe.restype = I
+    L.tai_conv_bf16_weight_elems.argtypes = [I, I, I]
+    L.tai_conv_bf16_weight_elems.restype = ctypes.c_longlong
+    L.tai_conv_bf16_pack_weights.argtypes = [P, P, I, I, I, I, V]
+    L.tai_conv_bf16_pack_weights.restype = I
+    L.tai_conv_bf16_forward.argtypes = [P, I, P, P, P, P, P, P] + [I] * 7 + [V]
+    L.tai_conv_bf16_forward.restype = I
     L.tai_sepconv_last_error.restype = ctypes.c_char_p
     L.tai_sepconv_source_hash.restype = ctypes.c_char_p
     L.tai_sepconv_version.restype = I

@@ -67,6 +67,85 @@ def get_winograd_arithmetic():
     return [k for k, v in WINOGRAD_ARITHMETICS.items() if v == mode][0]
 
 
+CONV_PRECISIONS = ('fp32', 'bf16')
+_CONV_PREC = ['fp32']
+
+
+def set_conv_precision(name):
+    """Precision of the inference convolutions, process-wide: ``'fp32'`` (default: the routes and bits of before) or ``'bf16'``
+    (opt-in, inference only): every layer _bf16_ok takes -- C >= 16 and K >= 16, k in {3, 5, 7}, stride 1, padding k // 2, the
+    stride-1 ConvTranspose2d included -- computes act(bias + sum bf16(x) bf16(w)) on csrc/conv_bf16.hip.inc (operands rounded to
+    nearest even, products exact, fp32 sums in an order fixed by the layer's shape).  Where autograd needs a gradient every path
+    runs as in fp32 mode.  With set_winograd_arithmetic('bf16x3') as well, that arithmetic applies only to the layers the bf16
+    kernel does not take.  A hipGraph captured before a switch keeps replaying what it captured: the packed bf16 weights are
+    cached beside the fp32 ones.  Returns the previous name."""
+    if name not in CONV_PRECISIONS:
+        raise ValueError(name)
+    prev, _CONV_PREC[0] = _CONV_PREC[0], name
+    return prev
+
+
+def get_conv_precision():
+    return _CONV_PREC[0]
+
+
+def _bf16_ok(Ci, Co, k, padding):
+    """Does the bf16 kernel take this layer (in 'bf16' mode)?  A rule on the weight alone -- never on N, H, W or a grid -- so one
+    CPU emulation states what the GPU computes and an image's arithmetic does not depend on its batch."""
+    return Ci >= 16 and Co >= 16 and k in (3, 5, 7) and padding == k // 2
+
+
+def _bf16_route(Ci, Co, kh, kw, padding, *tensors):
+    """bf16 mode, a no-grad call and a layer _bf16_ok takes"""
+    return _CONV_PREC[0] == 'bf16' and kh == kw and _bf16_ok(Ci, Co, kh, padding) and _no_grad_needed(*tensors)
+
+
+def _bf16_weights(weight, transposed):
+    """The packed bf16 weights of tai_conv_bf16_forward (tai_conv_bf16_pack_weights folds in a ConvTranspose2d's transpose and flip)."""
+    def make():
+        w = weight.detach().contiguous()
+        k = w.shape[2]
+        K, C = (w.shape[1], w.shape[0]) if transposed else (w.shape[0], w.shape[1])
+        L = _native.lib()
+        n = L.tai_conv_bf16_weight_elems(K, C, k)
+        _native.check(n if n < 0 else 0, 'tai_conv_bf16_weight_elems')
+        Wp = torch.empty(n, dtype=torch.bfloat16, device=w.device)
+        with torch.cuda.device(w.device):
+            _native.check(L.tai_conv_bf16_pack_weights(w.data_ptr(), Wp.data_ptr(), K, C, k, int(transposed),
+                                                       torch.cuda.current_stream(w.device).cuda_stream), 'tai_conv_bf16_pack_weights')
+        return Wp
+    return _cached(weight, ('bf16', transposed), make)
+
+
+def _bf16_conv(parts, weight, bias, act, transposed=False, out=None, pool=False, addx=None, keep_plain=True):
+    """One tai_conv_bf16_forward over 1-4 channel parts.  Returns y; with ``pool`` (y, pooled); with ``addx``
+    (y or None, y + fixed_unpool(addx)) as conv_bias_unpool_add."""
+    x0 = parts[0]
+    N, Cp, H, W = x0.shape
+    k = weight.shape[2]
+    Co, Ci = (weight.shape[1], weight.shape[0]) if transposed else (weight.shape[0], weight.shape[1])
+    parts = [p.contiguous() for p in parts]
+    y = out if _usable_out(out, (N, Co, H, W), x0) else torch.empty((N, Co, H, W), dtype=torch.float32, device=x0.device)
+    yp = torch.empty((N, Co, H // 2, W // 2), dtype=torch.float32, device=x0.device) if pool else None
+    y2 = None
+    if addx is not None:
+        addx = addx.contiguous()
+        y2 = torch.empty_like(y) if keep_plain else None
+    ptrs = (ctypes.c_void_p * len(parts))(*[p.data_ptr() for p in parts])
+    Wp = _bf16_weights(weight, transposed)
+    with torch.cuda.device(x0.device):
+        _native.check(_native.lib().tai_conv_bf16_forward(ptrs, len(parts), Wp.data_ptr(), bias.data_ptr(), y.data_ptr(),
+                                                          yp.data_ptr() if yp is not None else None,
+                                                          addx.data_ptr() if addx is not None else None,
+                                                          y2.data_ptr() if y2 is not None else None, N, Ci, Co, H, W, k, _ACT[act],
+                                                          torch.cuda.current_stream(x0.device).cuda_stream), 'tai_conv_bf16_forward')
+    if pool:
+        return y, yp
+    if addx is not None:
+        return (y, y2) if keep_plain else (None, y)
+    return y
+
+
 _WINO_TILE = [4]
 WINO43_MIN_CHANNELS = 64         # F(4x4, 3x3) where both C and K are at least this: every 3x3 layer of MC-Net but the first and the last.  (128 until
                                  # the kernel moved from Lavin's interpolation points to (0, +-3/4, +-3/2, inf), whose per-layer rounding is ~4x lower:
@@ -346,6 +425,8 @@ def motion_enc_chain(diff, conv1, conv2, conv3):
     the shapes do not qualify (the caller then runs the stages one by one)."""
     if not (torch.is_tensor(diff) and diff.is_cuda and diff.dtype == torch.float32 and diff.dim() == 4 and diff.shape[1] == 1):
         return None
+    if _CONV_PREC[0] == 'bf16':         # the stages one by one: the thin first layer in fp32, the 5x5 and 7x7 on the bf16 kernel
+        return None
     ws = [conv1.weight, conv2.weight, conv3.weight]
     bs = [conv1.bias, conv2.bias, conv3.bias]
     if any(b is None for b in bs) or not _no_grad_needed(diff, *ws, *bs):
@@ -408,6 +489,11 @@ def conv_bias_unpool_add(x, weight, bias, padding, addx, keep_plain=True):
     x0 = parts[0]
     Co, Ci, kh, kw = weight.shape
     N, Cp, H, W = x0.shape
+    if (x0.is_cuda and x0.dtype == torch.float32 and bias is not None and addx.is_cuda and addx.dtype == torch.float32
+            and tuple(addx.shape) == (N, Co, H // 2, W // 2) and H % 2 == 0 and W % 2 == 0 and len(parts) <= 4 and Cp * len(parts) == Ci
+            and all(q.shape == x0.shape and q.dtype == x0.dtype for q in parts)
+            and _bf16_route(Ci, Co, kh, kw, padding, weight, bias, addx, *parts)):
+        return _bf16_conv(parts, weight, bias, None, addx=addx, keep_plain=keep_plain)
     fused = (x0.is_cuda and x0.dtype == torch.float32 and bias is not None and addx.is_cuda and addx.dtype == torch.float32
              and tuple(addx.shape) == (N, Co, H // 2, W // 2) and len(parts) <= 4 and Cp * len(parts) == Ci
              and (len(parts) == 1 or Cp % 8 == 0) and all(q.shape == x0.shape and q.dtype == x0.dtype for q in parts)
@@ -972,6 +1058,9 @@ def conv_bias_act_maxpool(x, weight, bias, padding, act):
     """(y, max_pool2d(y, 2)) with y = conv_bias_act(x, ...): the kernels that own a whole 2x2 window per lane (Winograd,
     one-input-channel) write the pooled tensor in their epilogue instead of leaving a second pass over y to ATen."""
     Co, Ci, kh, kw = weight.shape
+    if (torch.is_tensor(x) and x.is_cuda and x.dtype == torch.float32 and bias is not None and x.dim() == 4 and x.shape[1] == Ci
+            and x.shape[2] % 2 == 0 and x.shape[3] % 2 == 0 and _bf16_route(Ci, Co, kh, kw, padding, x, weight, bias)):
+        return _bf16_conv([x], weight, bias, act, pool=True)
     fused = (torch.is_tensor(x) and x.is_cuda and x.dtype == torch.float32 and bias is not None and act in (None, 'relu')
              and x.shape[2] % 2 == 0 and x.shape[3] % 4 == 0
              and not (torch.is_grad_enabled() and (x.requires_grad or weight.requires_grad or bias.requires_grad)))
@@ -1032,6 +1121,10 @@ def _conv_bias_act(x, weight, bias, padding, act, transposed, out):
         kh, kw = weight.shape[2], weight.shape[3]
         Co, Ci = (weight.shape[1], weight.shape[0]) if transposed else (weight.shape[0], weight.shape[1])
         N, Cp, H, W = x0.shape
+        if (len(parts) <= 4 and x0.is_cuda and x0.dtype == torch.float32 and bias is not None and Cp * len(parts) == Ci
+                and all(p.shape == x0.shape and p.dtype == x0.dtype for p in parts)
+                and _bf16_route(Ci, Co, kh, kw, padding, weight, bias, *parts)):
+            return _bf16_conv(parts, weight, bias, act, transposed, out)
         direct = (len(parts) <= 4 and x0.is_cuda and x0.dtype == torch.float32 and bias is not None and Cp % 8 == 0
                   and Cp * len(parts) == Ci and all(p.shape == x0.shape and p.is_contiguous() and p.dtype == x0.dtype for p in parts)
                   and not (torch.is_grad_enabled() and (weight.requires_grad or bias.requires_grad or any(p.requires_grad for p in parts)))
@@ -1087,6 +1180,8 @@ def _conv_bias_act(x, weight, bias, padding, act, transposed, out):
     kh, kw = weight.shape[2], weight.shape[3]
     Co, Ci = (weight.shape[1], weight.shape[0]) if transposed else (weight.shape[0], weight.shape[1])
     N, _, H, W = x.shape
+    if x.shape[1] == Ci and _bf16_route(Ci, Co, kh, kw, padding):     # (the fused test above: no gradient needed)
+        return _bf16_conv([x], weight, bias, act, transposed, out)
     L = _native.lib()
     stream = torch.cuda.current_stream(x.device).cuda_stream
     thin_in = Ci == 1 and kh == kw and kh in (3, 5) and padding == kh // 2 and W % 4 == 0 and act in (None, 'relu') and Co >= 16

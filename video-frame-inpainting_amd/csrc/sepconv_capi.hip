@@ -24,6 +24,7 @@
 #include "wino_split.hip.inc"
 #include "wino43_conv.hip.inc"
 #include "wino_wrw.hip.inc"
+#include "conv_bf16.hip.inc"
 #include "spectral_norm.hip.inc"
 #include "hbm_probe.hip.inc"
 
@@ -1517,6 +1518,79 @@ int tai_sepconv_backward(const float* grad_output, const float* input, const flo
         }
     }
     return TAI_SEPCONV_OK;
+}
+
+// ---- opt-in bf16 inference convolution (csrc/conv_bf16.hip.inc) ----
+
+static int bf16_shape_ok(int K, int C, int k) { return C >= 16 && K >= 16 && (k == 3 || k == 5 || k == 7); }
+
+long long tai_conv_bf16_weight_elems(int K, int C, int k) {
+    g_err[0] = 0;
+    if (!bf16_shape_ok(K, C, k)) return fail(TAI_SEPCONV_EINVAL, "%s", "conv_bf16: needs C >= 16, K >= 16 and k in {3, 5, 7}");
+    return (long long)((K + cbf16::NT - 1) / cbf16::NT) * ((C + cbf16::KC - 1) / cbf16::KC) * cbf16::ksteps(k) * (cbf16::STEP_BYTES / 2);
+}
+
+int tai_conv_bf16_pack_weights(const float* w, void* Wp, int K, int C, int k, int transposed, void* hip_stream) {
+    g_err[0] = 0;
+    if (!w || !Wp) return fail(TAI_SEPCONV_EINVAL, "%s", "null pointer");
+    if (!bf16_shape_ok(K, C, k)) return fail(TAI_SEPCONV_EINVAL, "%s", "conv_bf16_pack_weights: needs C >= 16, K >= 16 and k in {3, 5, 7}");
+    if ((long long)K * C * k * k >= (1LL << 31)) return fail(TAI_SEPCONV_EINVAL, "%s", "conv_bf16_pack_weights: weight too large");
+    if (reinterpret_cast<uintptr_t>(Wp) % 16 != 0) return fail(TAI_SEPCONV_EINVAL, "%s", "conv_bf16_pack_weights: Wp must be 16-byte aligned");
+    const long long pairs = tai_conv_bf16_weight_elems(K, C, k) / 2;
+    hipStream_t s = static_cast<hipStream_t>(hip_stream);
+    hipLaunchKernelGGL(cbf16::pack_weights, dim3((unsigned)((pairs + 255) / 256)), dim3(256), 0, s, w, static_cast<unsigned*>(Wp), K, C, k,
+                       transposed ? 1 : 0, (C + cbf16::KC - 1) / cbf16::KC, pairs);
+    return check_launch("conv_bf16_pack_weights");
+}
+
+int tai_conv_bf16_forward(const float* const* xs, int nparts, const void* Wp, const float* bias, float* y, float* ypool, const float* addx,
+                          float* y2, int N, int C, int K, int H, int W, int k, int act, void* hip_stream) {
+    g_err[0] = 0;
+    if (!xs || !Wp || !bias || !y || nparts < 1 || nparts > 4) return fail(TAI_SEPCONV_EINVAL, "%s", "conv_bf16_forward: bad argument (1 to 4 input parts)");
+    for (int p = 0; p < nparts; ++p)
+        if (!xs[p]) return fail(TAI_SEPCONV_EINVAL, "%s", "conv_bf16_forward: null input part");
+    if (!bf16_shape_ok(K, C, k)) return fail(TAI_SEPCONV_EINVAL, "%s", "conv_bf16_forward: needs C >= 16, K >= 16 and k in {3, 5, 7}");
+    if (N <= 0 || H <= 0 || W <= 0 || C % nparts != 0 || act < 0 || act > 2)
+        return fail(TAI_SEPCONV_EINVAL, "%s", "conv_bf16_forward: needs N, H, W >= 1, C a multiple of the part count, act in {0, 1, 2}");
+    if ((long long)N * C * H * W >= (1LL << 31) || (long long)N * K * H * W >= (1LL << 31))
+        return fail(TAI_SEPCONV_EINVAL, "%s", "conv_bf16_forward: tensor too large (2^31 elements or more)");
+    if ((ypool || addx) && (H % 2 != 0 || W % 2 != 0))
+        return fail(TAI_SEPCONV_EINVAL, "%s", "conv_bf16_forward: the pool and unpool epilogues need even H and W");
+    if (y2 && !addx) return fail(TAI_SEPCONV_EINVAL, "%s", "conv_bf16_forward: y2 needs addx");
+    if (reinterpret_cast<uintptr_t>(Wp) % 16 != 0) return fail(TAI_SEPCONV_EINVAL, "%s", "conv_bf16_forward: Wp must be 16-byte aligned");
+    const cbf16::Plan pl = cbf16::plan(N, K, H, W, k);
+    if (pl.blocks <= 0 || pl.blocks >= (1LL << 31)) return fail(TAI_SEPCONV_EINVAL, "%s", "conv_bf16_forward: no tile fits");
+    cbf16::Args a{};
+    for (int p = 0; p < 4; ++p) a.x[p] = xs[p < nparts ? p : 0];
+    a.cpart = C / nparts;
+    a.w = static_cast<const uint4*>(Wp);
+    a.bias = bias; a.y = y; a.ypool = ypool; a.addx = addx; a.y2 = y2;
+    a.N = N; a.C = C; a.K = K; a.H = H; a.W = W;
+    a.TH = pl.TH; a.TW = pl.TW; a.IMG = pl.IMG; a.PH = pl.PH; a.PW = pl.PW; a.pitch = pl.pitch;
+    a.tiles_x = pl.tiles_x; a.tiles_y = pl.tiles_y;
+    a.kblocks = (K + cbf16::NT - 1) / cbf16::NT;
+    a.nchunks = (C + cbf16::KC - 1) / cbf16::KC;
+    hipStream_t s = static_cast<hipStream_t>(hip_stream);
+    const size_t lds = (size_t)pl.lds_bytes;
+#define TAI_BF16_LAUNCH(KS, MW, ACT)                                                                                 \
+    do {                                                                                                             \
+        auto kern = cbf16::conv_bf16<KS, MW, ACT>;                                                                   \
+        if (int rc = allow_lds(kern, lds)) return rc;                                                                \
+        hipLaunchKernelGGL(kern, dim3((unsigned)pl.blocks), dim3(cbf16::THREADS), lds, s, a);                        \
+    } while (0)
+#define TAI_BF16_ACT(KS, MW)                                                                                         \
+    do {                                                                                                             \
+        if (act == 0) TAI_BF16_LAUNCH(KS, MW, 0); else if (act == 1) TAI_BF16_LAUNCH(KS, MW, 1); else TAI_BF16_LAUNCH(KS, MW, 2); \
+    } while (0)
+#define TAI_BF16_MW(KS)                                                                                              \
+    do {                                                                                                             \
+        if (pl.MW == 4) TAI_BF16_ACT(KS, 4); else TAI_BF16_ACT(KS, 2);                                               \
+    } while (0)
+    if (k == 3) TAI_BF16_MW(3); else if (k == 5) TAI_BF16_MW(5); else TAI_BF16_MW(7);
+#undef TAI_BF16_MW
+#undef TAI_BF16_ACT
+#undef TAI_BF16_LAUNCH
+    return check_launch("conv_bf16_forward");
 }
 
 }  // extern "C"

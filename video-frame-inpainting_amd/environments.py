@@ -101,7 +101,8 @@ class BaseVideoFillInEnvironment(object):
 
     def forward_test(self):
         if self.use_graph:
-            key = (self.T, tuple(self.preceding_frames.shape), tuple(self.following_frames.shape))
+            # the convolution precision is part of the key: a switch captures anew instead of replaying the other arithmetic
+            key = (self.T, tuple(self.preceding_frames.shape), tuple(self.following_frames.shape), conv_ops.get_conv_precision())
             if key not in self._graphs:
                 self._graphs[key] = GraphedForward(self.generator, self.T, self.preceding_frames, self.following_frames)
             self.gen_output = self._graphs[key](self.preceding_frames, self.following_frames)

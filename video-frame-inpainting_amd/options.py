@@ -113,3 +113,7 @@ class TestOptions(BaseOptions):
                        help='Flag to write intermediate predictions in addition to final ones')
         g.add_argument('--random_init', action='store_true',
                        help='(this build) skip the snapshot load and keep the seeded xavier initialisation')
+        g.add_argument('--conv_precision', type=str, default='fp32', choices=['fp32', 'bf16'],
+                       help='(this build) precision of the inference convolutions: fp32 (default) or bf16 = opt-in: the layers with at '
+                            'least 16 input and output channels and k in {3, 5, 7} take bf16 operands (rounded to nearest even), exact '
+                            'products and fp32 sums (conv_ops.set_conv_precision)')
