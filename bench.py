@@ -3,6 +3,7 @@
 
   python bench.py --gpus N --steps K --warmup W        (N > 1: this process starts the N rank processes itself)
   python bench.py ... --dump-outputs DIR               (also writes the last timed step's outputs: DIR/<key>.npy)
+  python bench.py ... --full                           (after the headline, also every leg listed below)
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
 Metric (BASELINE.json): inpainted frames/sec at 128x128, K=F=5, T=5.  Workload = configs[1]: TAI_gray inference, batch
@@ -12,7 +13,8 @@ checkpoints; the reference's zero-bias init makes every prediction a constant gr
 whole model over one batch; N > 1 shards clips over ranks with no data-path collective (weak scaling); the timed region
 is bracketed by barrier + synchronize and the MAX over ranks is reported.  Inputs are resident in HBM before timing.
 
-The JSON line also carries
+A plain run sets up, warms up, times the steps, writes --dump-outputs and prints the headline line.  With --full the JSON line
+also carries
   roofline      the separable-convolution forward kernel as the model launches it -- [T*32,1,128,128], 1.07 GB of once-read taps from
                 HBM: algorithmic HBM bytes (6,876,944 B per sample) / mean launch duration from HIP events on the
                 launch stream, against the 8 TB/s HBM3E peak, with this box's streaming-read rates beside it; `traffic` is the
@@ -27,7 +29,9 @@ The JSON line also carries
                 host's cores as BASELINE.md section 2 plans it (B = 1 and B = 8, 1 warm-up + 3 timed forwards each,
                 median; sepconv-only CPU time and GB/s; rank 0, N = 1 only) -- a reported baseline;
   parity        the GPU output against that oracle run on the same 8 full-width clips: per output key max |diff| over
-                max |ref|, distinct gray levels of the uint8 prediction, PSNR / SSIM vs ground truth on both sides.
+                max |ref|, distinct gray levels of the uint8 prediction, PSNR / SSIM vs ground truth on both sides;
+  secondary     configs[3] and configs[4] end to end, configs[1] in the opt-in arithmetics, the 3-channel sepconv forward;
+  train_step    configs[2]'s per-GPU training update (N = 1), or train_step_dp, the data-parallel update over the ranks (N > 1).
 """
 import argparse
 import json
@@ -792,25 +796,33 @@ def rehearse_launch(args):
         dist.destroy_process_group()
 
 
-def main():
+def parser():
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
     ap.add_argument('--steps', type=int, default=20)
     ap.add_argument('--warmup', type=int, default=3)
     ap.add_argument('--batch', type=int, default=32, help='clips per GPU (configs[1]: 32)')
     ap.add_argument('--no-graph', action='store_true', help='eager launches instead of the hipGraph replay')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='with --full: skip the cpu_baseline and parity legs')
     ap.add_argument('--miopen-find', action='store_true', help='let MIOpen benchmark its algorithms during warm-up')
     ap.add_argument('--rehearse-launch', action='store_true', help='CPU/gloo rehearsal of the rank launch only (tests)')
     ap.add_argument('--rehearse-train', action='store_true', help='with --rehearse-launch: also the multi-rank training leg on CPU/gloo')
     ap.add_argument('--rehearse-one-gpu', action='store_true',
                     help='N ranks all on cuda:0 with gloo for the control plane: a rehearsal of the N-rank code path on a '
                          'one-GPU box; the line is marked "rehearsal" and is never a measurement')
+    ap.add_argument('--full', action='store_true',
+                    help='after the headline, also measure the rooflines, the CPU baseline and parity, the secondary configs and the '
+                         'training update (extra keys of the line); a plain run prints the headline alone')
     ap.add_argument('--train-leg-timeout', type=int, default=420, help='seconds the multi-rank training leg may take before rank 0 prints the line without it')
-    ap.add_argument('--no-extras', action='store_true', help='skip the secondary-config and training-update legs (extra keys of the line)')
+    ap.add_argument('--no-extras', action='store_true', help='with --full: skip the secondary-config and training-update legs')
     ap.add_argument('--cpu-threads', type=int, default=None, help='threads of the cpu_baseline leg (default: see host_cpu_share)')
     ap.add_argument('--dump-outputs', metavar='DIR', default=None,
                     help="write the last timed step's outputs (rank 0's clips) as DIR/<key>.npy, float32, at most 64 MB in all")
+    return ap
+
+
+def main():
+    ap = parser()
     args = ap.parse_args()
     if args.steps < 1:
         ap.error('--steps must be at least 1')
@@ -904,7 +916,7 @@ def main():
         line['dumped_outputs'] = {'dir': args.dump_outputs, 'arrays': dumped}
     if args.rehearse_one_gpu:
         line['rehearsal'] = 'all %d ranks on one GPU, gloo control plane: NOT a measurement' % world
-    if rank == 0:
+    if rank == 0 and args.full:
         line['roofline'] = sepconv_roofline(device, B)
         log('roofline measured')
         if B == 32:
@@ -929,8 +941,8 @@ def main():
                 except Exception as e:          # an extra leg must never cost the headline line
                     line[key] = {'error': '%s: %s' % (type(e).__name__, e)}
                     log('%s leg failed: %r' % (key, e))
-    if world > 1 and B == 32 and not args.no_extras:       # (also in the one-GPU rehearsal: the line is then marked as such)
-        # configs[2] is the one config with a collective: measured whenever there are peers (every rank takes part; rank 0 reports).
+    if args.full and world > 1 and B == 32 and not args.no_extras:       # (also in the one-GPU rehearsal: the line is then marked as such)
+        # configs[2] is the one config with a collective: with --full, measured whenever there are peers (every rank takes part; rank 0 reports).
         # The headline above is already measured and must reach stdout whatever happens here: the leg runs in a worker thread under
         # a deadline; if a rank fails or a collective never completes, rank 0 prints the line with the error and every rank leaves.
         import threading

@@ -58,6 +58,16 @@ def test_the_multi_rank_training_leg_runs_over_gloo_and_keeps_replicas_identical
     assert 'REHEARSAL' in rec['workload']
 
 
+def test_the_extra_legs_are_opt_in():
+    """A plain run measures the headline alone; --full adds the other legs, which --no-cpu-baseline / --no-extras still trim."""
+    sys.path.insert(0, ROOT)
+    import bench
+    ap = bench.parser()
+    assert ap.parse_args(['--gpus', '1', '--steps', '5', '--warmup', '2']).full is False
+    a = ap.parse_args(['--full', '--no-cpu-baseline'])
+    assert a.full is True and a.no_cpu_baseline is True and a.no_extras is False
+
+
 def test_dump_outputs_writes_float32_arrays_within_the_budget_and_samples_reproducibly(tmp_path, monkeypatch):
     """--dump-outputs: one float32 <key>.npy per output; an array over its share of the budget becomes a fixed seeded sample,
     the same elements on every run."""

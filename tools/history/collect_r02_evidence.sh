@@ -4,7 +4,7 @@
 set -o pipefail
 out=gpurun_out/evidence_r02; mkdir -p $out
 export TMPDIR=/tmp
-BENCH="python3 bench.py --steps 5 --warmup 2 --no-cpu-baseline"
+BENCH="python3 bench.py --steps 5 --warmup 2 --full --no-cpu-baseline"
 echo "[1] bench kernel trace"; timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $out/bench_trace -- $BENCH > $out/bench_trace.log 2>&1
 echo "[2] bench FETCH_SIZE"; timeout -k 10 300 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $out/bench_fetch -- $BENCH > $out/bench_fetch.log 2>&1
 echo "[3] bench WRITE_SIZE"; timeout -k 10 300 rocprofv3 --pmc WRITE_SIZE GRBM_GUI_ACTIVE --output-format csv -d $out/bench_write -- $BENCH > $out/bench_write.log 2>&1

@@ -45,7 +45,7 @@ by_grid = collections.defaultdict(list)
 for r in trace_rows('bench_trace'):
     if 'sepconv_forward' in r['Kernel_Name']:
         by_grid[(short(r['Kernel_Name']), int(r.get('Grid_Size') or r.get('Grid_Size_X') or 0))].append((int(r['End_Timestamp']) - int(r['Start_Timestamp'])) / 1e3)
-lines = ['rocprofv3 --kernel-trace of `python3 bench.py --steps 5 --warmup 2 --no-cpu-baseline` (r02), sepconv forward launches by grid size',
+lines = ['rocprofv3 --kernel-trace of `python3 bench.py --steps 5 --warmup 2 --full --no-cpu-baseline` (r02), sepconv forward launches by grid size',
          '(grid 131072 threads = 256 workgroups x 512 = the [32,1,128,128] roofline shape; grid 655360 = the in-model call over all 5 time steps, [160,1,128,128])']
 fwd_avg = None
 for (k, g), v in sorted(by_grid.items()):
@@ -75,7 +75,7 @@ pmc['kernel_trace_in_bench'] = fwd_avg
 pmc['note'] = ('hbm_bytes = 2 x FETCH_SIZE(KB) x 1024 + WRITE_SIZE(KB) x 1024: MI355X_MICROARCH.md (HBM) -- on gfx950 FETCH_SIZE reports exactly '
                'half the bytes of a wide coalesced streaming read (16 B/lane global_load and LDS-DMA alike); WRITE_SIZE is exact for 16 B/lane '
                'streaming stores. Counters from `rocprofv3 --pmc FETCH_SIZE` / `--pmc WRITE_SIZE GRBM_GUI_ACTIVE` (separate runs) of '
-               '`python3 bench.py --steps 5 --warmup 2 --no-cpu-baseline`, dispatches of grid 131072 only.')
+               '`python3 bench.py --steps 5 --warmup 2 --full --no-cpu-baseline`, dispatches of grid 131072 only.')
 try:       # what bench.py checks before it prints the value as `roofline.traffic`
     sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
     from video_frame_inpainting_amd import _native
@@ -84,7 +84,7 @@ try:       # what bench.py checks before it prints the value as `roofline.traffi
 except Exception as e:
     pmc['library_version_error'] = repr(e)
 pmc['source'] = ('tools/collect_r02_evidence.sh: rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE GRBM_GUI_ACTIVE / --kernel-trace --stats, separate '
-                 'runs of `python3 bench.py --steps 5 --warmup 2 --no-cpu-baseline`; dispatches of the [32,1,128,128] roofline shape (grid 131072)')
+                 'runs of `python3 bench.py --steps 5 --warmup 2 --full --no-cpu-baseline`; dispatches of the [32,1,128,128] roofline shape (grid 131072)')
 json.dump(pmc, open(os.path.join(res_dir, 'sepconv_fwd_pmc_measured.json'), 'w'), indent=1)
 print(json.dumps(pmc, indent=1)[:600])
 
@@ -96,7 +96,7 @@ for sub in ('bench_sq', 'bench_lds', 'bench_fetch', 'bench_write'):
             wino.setdefault(c, [0.0, 0])
             wino[c][0] += sum(v)
             wino[c][1] += len(v)
-lines = ['rocprofv3 PMC counters of the Winograd convolution kernels (wino::conv3x3<...>) inside `python3 bench.py --steps 5 --warmup 2 --no-cpu-baseline`,',
+lines = ['rocprofv3 PMC counters of the Winograd convolution kernels (wino::conv3x3<...>) inside `python3 bench.py --steps 5 --warmup 2 --full --no-cpu-baseline`,',
          'summed over every dispatch of the run (eager warm-up forwards + graph replays); separate --pmc passes']
 for c, (tot, n) in sorted(wino.items()):
     lines.append('%-28s sum %.6g over %d dispatches (mean %.6g)' % (c, tot, n, tot / max(n, 1)))

@@ -4,7 +4,7 @@ import collections, csv, glob, json, os, sys
 root = sys.argv[1]
 res_dir = os.path.join(root, 'summaries')
 os.makedirs(res_dir, exist_ok=True)
-CMD = 'python3 bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-extras'
+CMD = 'python3 bench.py --steps 5 --warmup 2 --full --no-cpu-baseline --no-extras'
 
 
 def short(name):
