@@ -396,6 +396,21 @@ int tai_conv_bf16_pack_weights(const float* w, void* Wp, int K, int C, int k, in
 int tai_conv_bf16_forward(const float* const* xs, int nparts, const void* Wp, const float* bias, float* y, float* ypool,
                           const float* addx, float* y2, int N, int C, int K, int H, int W, int k, int act, void* hip_stream);
 
+/* Per-frame image-quality metrics (csrc/frame_metrics.hip.inc): the reference's compute_errors (train.py:237-287) as
+ * video_frame_inpainting_amd/metrics.py restates it.  pred and gt are contiguous fp32 [N, C, H, W] in [-1, 1] (N = B T frames),
+ * H >= 7 and W >= 7 (the 7x7 SSIM window; smaller planes are refused with TAI_SEPCONV_EINVAL).  Per frame n:
+ *   sse[n]   exact sum over all channels of (u(pred) - u(gt))^2, u(x) = uint8(trunc((clip(x, -1, 1) + 1) / 2 * 255)) in fp32;
+ *   ssim[n]  SSIM(u(gt), u(pred)): 7x7 uniform window, K1 = 0.01, K2 = 0.03, L = 255, covariance x 49/48, mean over the
+ *            (H-6) x (W-6) interior, then over channels; per pixel bit-identical to the host's float64 expression;
+ *   l2[n]    mean of ((clip(p) + 1) / 2 - (clip(g) + 1) / 2)^2, squares in fp32, sum in fp64.
+ * The workspace (8-byte aligned, tai_frame_metrics_workspace_bytes bytes) holds per-tile partials that are summed per frame in a
+ * fixed order: results are reproducible bit for bit and do not depend on the other frames of the batch.  No allocation, copy or
+ * synchronisation: asynchronous on hip_stream and capturable into a hipGraph.
+ * Workspace bytes for N x C x H x W; negative (TAI_SEPCONV_EINVAL) outside the rule above. */
+long long tai_frame_metrics_workspace_bytes(int N, int C, int H, int W);
+int tai_frame_metrics(const float* pred, const float* gt, long long* sse, double* ssim, double* l2, void* workspace, int N, int C,
+                      int H, int W, void* hip_stream);
+
 /* Text of the last error on the calling thread ("" if none). */
 const char* tai_sepconv_last_error(void);
 

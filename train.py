@@ -4,8 +4,10 @@ slice the clip -> set_train_inputs -> train() -> forward_train() -> optimize_par
 parallel over RCCL when launched with torch.distributed.run), with the reference's snapshot files ``model_latest.ckpt``
 / ``model_%08d.ckpt`` (train.py:137-140).  Clips come from ``--train_video_list_path`` (the reference's list format and
 augmentation flags, train.py:37-43; video_frame_inpainting_amd/data.py; each rank shuffles with its own seed) or, with
-``--synthetic N``, from N seeded synthetic clips.  TensorBoard logging and the periodic validation of the reference are
-outside the hot path.
+``--synthetic N``, from N seeded synthetic clips.  Every ``--validate_freq`` updates the reference's validation legs run
+(train.py:142-196; video_frame_inpainting_amd/validation.py) on ``--val_video_list*_path`` or, with ``--val_synthetic N``, on N
+seeded synthetic clips, scored on the GPU (metrics.compute_errors_device); the snapshot with the best summed per-frame SSIM of
+the first leg is kept as ``model_best.ckpt``.  TensorBoard logging is outside the hot path.
 
   python train.py --name demo --K 5 --T 5 --F 5 --c_dim 1 --image_size 128 --batch_size 4 --model_key TAI_gray \
       --max_iter 10 --synthetic 64
@@ -21,6 +23,7 @@ from video_frame_inpainting_amd import parallel, synthetic
 from video_frame_inpainting_amd.data import ContiguousVideoClipDataset
 from video_frame_inpainting_amd.environments import create_training_environment
 from video_frame_inpainting_amd.options import TrainOptions
+from video_frame_inpainting_amd.validation import Validator
 
 
 def main(args=None):
@@ -63,6 +66,13 @@ def main(args=None):
                                       graph_step=opt.graph_step)
     env.sync_replicas()
     total_updates = env.start_update
+    # a resumed run starts from the best values its snapshot carries (train.py:96-97)
+    validator = Validator(opt, (env.start_sum_avg_psnr_err, env.start_sum_avg_ssim_err))
+    for leg in validator.legs:
+        if rank == 0:
+            print('# validation leg %s: (K,T,F)=(%d,%d,%d) on %s' % (leg.name, leg.K, leg.T, leg.F,
+                                                                      '%d synthetic clips' % leg.source[1]
+                                                                      if isinstance(leg.source, tuple) else leg.source))
     order = np.random.RandomState(opt.seed + 7 * rank)
     while total_updates < opt.max_iter:
         t0 = time.time()
@@ -81,9 +91,11 @@ def main(args=None):
                 print('iter %d (K,T,F)=(%d,%d,%d) %.3fs  %s' % (total_updates, K, T, F, time.time() - t0,
                                                                 ' '.join('%s=%.5f' % kv for kv in sorted(errs.items()))))
         if total_updates % opt.save_latest_freq == 0:
-            env.save('model_latest.ckpt', total_updates, 0, 0)
-            env.save('model_%08d.ckpt' % total_updates, total_updates, 0, 0)
-    env.save('model_latest.ckpt', total_updates, 0, 0)
+            env.save('model_latest.ckpt', total_updates, *validator.best)
+            env.save('model_%08d.ckpt' % total_updates, total_updates, *validator.best)
+        if validator and total_updates % opt.validate_freq == 0:
+            validator.validate(env, total_updates)
+    env.save('model_latest.ckpt', total_updates, *validator.best)
     print('Done.')
 
 

@@ -7,6 +7,7 @@ Layout (mirrors the reference's modules for this path):
   environments, options       eval / training environments and flags (reference src/environments, src/options)
   losses, sn_discriminator    training-path losses (reference src/losses, src/discriminators)
   metrics, synthetic          PSNR/SSIM definition of the reference; seeded synthetic clips
+  validation                  the training loop's periodic validation and best-snapshot rule (metrics on the GPU)
   graph, parallel             hipGraph capture; clip-sharded data parallelism over RCCL
 """
 import os as _os

@@ -277,6 +277,10 @@ def lib():
     L.tai_conv_bf16_pack_weights.restype = I
     L.tai_conv_bf16_forward.argtypes = [P, I, P, P, P, P, P, P] + [I] * 7 + [V]
     L.tai_conv_bf16_forward.restype = I
+    L.tai_frame_metrics_workspace_bytes.argtypes = [I] * 4
+    L.tai_frame_metrics_workspace_bytes.restype = ctypes.c_longlong
+    L.tai_frame_metrics.argtypes = [P, P, P, P, P, P, I, I, I, I, V]
+    L.tai_frame_metrics.restype = I
     L.tai_sepconv_last_error.restype = ctypes.c_char_p
     L.tai_sepconv_source_hash.restype = ctypes.c_char_p
     L.tai_sepconv_version.restype = I

@@ -1,0 +1,164 @@
+// Per-frame PSNR / SSIM / L2 of predicted against ground-truth frames (included by sepconv_capi.hip), with the definitions of
+// video_frame_inpainting_amd/metrics.py (the reference's compute_errors, train.py:237-287, and scikit-image 0.13.1's defaults):
+//   uint8 frames  u = uint8(trunc(((clip(x, -1, 1) + 1) / 2) * 255)), fp32, in that operation order;
+//   SSE           exact sum over all channels of (u_pred - u_gt)^2 (PSNR is derived from it on the host);
+//   SSIM(gt, pred) on the uint8 planes: 7x7 uniform window, K1 = 0.01, K2 = 0.03, L = 255, covariance scaled by 49/48, mean
+//                 over the (H-6) x (W-6) valid interior, then the mean over channels;
+//   L2            mean of (p' - g')^2, p' = (clip(p) + 1) / 2 in fp32, squared in fp32, summed in fp64.
+//
+// Exactness: the five 7x7 window sums (X, Y, X^2, Y^2, XY) of uint8 values are integers below 49 * 255^2 < 2^22, exact in int32 in
+// any order; the host's integral-image sums of the same integers are exact in float64 too.  So mu = sum / 49.0 is the same double on
+// both sides (correctly rounded division), and the per-pixel SSIM expression below is evaluated in float64 in the host's operation
+// order with contraction off: bit-identical per pixel.  Only the order of the interior mean's summation differs (numpy sums pairwise).
+//
+// Work split: one workgroup per (frame, channel, 16 x 64 tile of SSIM outputs).  It stages the 22 x 70 input window of both planes as
+// integers in LDS, forms the vertical 7-row sums, then the horizontal ones and the SSIM per output pixel.  SSE and L2 are taken over
+// the input pixels the tile owns (its 16 x 64 block; the last tile of a row / column also owns the 6 pixels past the interior), so
+// every pixel is counted once.  The tile's three partials go to the workspace; `finish` sums them per frame in a fixed order.  No
+// atomics, no dependence on the batch: a frame's bits depend only on its own pixels and on (C, H, W).
+
+namespace fmetrics {
+
+constexpr int BH = 16, TW = 64;            // SSIM outputs per tile: rows x columns
+constexpr int IH = BH + 6, IW = TW + 6;    // input window of a tile
+constexpr int THREADS = 256;
+
+// skimage's constants as Python computes them: (0.01 * 255) ** 2, (0.03 * 255) ** 2, 49 / 48.0
+constexpr double C1 = 0x1.a028f5c28f5c4p+2, C2 = 0x1.d42e147ae147ap+5, COV_NORM = 0x1.0555555555555p+0;
+
+__device__ __forceinline__ int to_u8(float x, float& unit) {
+#pragma clang fp contract(off)
+    const float c = fminf(fmaxf(x, -1.f), 1.f);
+    unit = (c + 1.f) / 2.f;
+    return (int)(unit * 255.f);
+}
+
+template <typename V>
+__device__ __forceinline__ V wave_sum(V x) {
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) x += __shfl_xor(x, m, 64);
+    return x;
+}
+
+__global__ __launch_bounds__(THREADS)
+void tile_partials(const float* __restrict__ pred, const float* __restrict__ gt, double* __restrict__ part_ssim,
+                   double* __restrict__ part_l2, long long* __restrict__ part_sse, int H, int W, int nby, int nbx) {
+#pragma clang fp contract(off)
+    __shared__ int sx[IH * IW], sy[IH * IW];          // X = gt, Y = pred (the argument order of compute_errors' SSIM)
+    __shared__ int sv[5][BH * IW];                    // vertical 7-row sums of X, Y, X^2, Y^2, XY
+    __shared__ double red_s[THREADS / 64], red_l[THREADS / 64];
+    __shared__ long long red_e[THREADS / 64];
+    const int tile = blockIdx.x;
+    const int bx = tile % nbx, by = (tile / nbx) % nby;
+    const long long plane = tile / (nbx * nby);       // frame * C + channel
+    const int r0 = by * BH, c0 = bx * TW, Ho = H - 6, Wo = W - 6;
+    const int own_r1 = by == nby - 1 ? H : r0 + BH, own_c1 = bx == nbx - 1 ? W : c0 + TW;
+    const float* p = pred + plane * H * W;
+    const float* g = gt + plane * H * W;
+
+    long long sse = 0;
+    double l2 = 0.0;
+    for (int i = threadIdx.x; i < IH * IW; i += THREADS) {
+        const int lr = i / IW, lc = i - lr * IW, r = r0 + lr, c = c0 + lc;
+        int xu = 0, yu = 0;
+        if (r < H && c < W) {
+            float pf, gf;
+            yu = to_u8(p[(long long)r * W + c], pf);
+            xu = to_u8(g[(long long)r * W + c], gf);
+            if (r < own_r1 && c < own_c1) {
+                const int d = yu - xu;
+                sse += d * d;
+                const float e = pf - gf;
+                l2 += (double)(e * e);
+            }
+        }
+        sx[i] = xu;
+        sy[i] = yu;
+    }
+    __syncthreads();
+    for (int i = threadIdx.x; i < BH * IW; i += THREADS) {
+        const int lr = i / IW, lc = i - lr * IW;
+        int a = 0, b = 0, aa = 0, bb = 0, ab = 0;
+#pragma unroll
+        for (int k = 0; k < 7; ++k) {
+            const int x = sx[(lr + k) * IW + lc], y = sy[(lr + k) * IW + lc];
+            a += x; b += y; aa += x * x; bb += y * y; ab += x * y;
+        }
+        sv[0][i] = a; sv[1][i] = b; sv[2][i] = aa; sv[3][i] = bb; sv[4][i] = ab;
+    }
+    __syncthreads();
+    double ssim = 0.0;
+    for (int i = threadIdx.x; i < BH * TW; i += THREADS) {
+        const int lr = i / TW, lc = i - lr * TW;
+        if (r0 + lr >= Ho || c0 + lc >= Wo) continue;
+        int s[5] = {0, 0, 0, 0, 0};
+#pragma unroll
+        for (int q = 0; q < 5; ++q)
+#pragma unroll
+            for (int k = 0; k < 7; ++k) s[q] += sv[q][lr * IW + lc + k];
+        // metrics.ssim_uint8, term for term
+        const double ux = s[0] / 49.0, uy = s[1] / 49.0;
+        const double uxx = s[2] / 49.0, uyy = s[3] / 49.0, uxy = s[4] / 49.0;
+        const double vx = COV_NORM * (uxx - ux * ux), vy = COV_NORM * (uyy - uy * uy), vxy = COV_NORM * (uxy - ux * uy);
+        const double num = (2.0 * ux * uy + C1) * (2.0 * vxy + C2);
+        const double den = (ux * ux + uy * uy + C1) * (vx + vy + C2);
+        ssim += num / den;
+    }
+    ssim = wave_sum(ssim);
+    l2 = wave_sum(l2);
+    sse = wave_sum(sse);
+    if ((threadIdx.x & 63) == 0) {
+        red_s[threadIdx.x >> 6] = ssim;
+        red_l[threadIdx.x >> 6] = l2;
+        red_e[threadIdx.x >> 6] = sse;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double ts = 0.0, tl = 0.0;
+        long long te = 0;
+        for (int w = 0; w < THREADS / 64; ++w) { ts += red_s[w]; tl += red_l[w]; te += red_e[w]; }
+        part_ssim[tile] = ts;
+        part_l2[tile] = tl;
+        part_sse[tile] = te;
+    }
+}
+
+// One thread per frame: channels in order, tiles in order within a channel.
+__global__ __launch_bounds__(64)
+void finish(const double* __restrict__ part_ssim, const double* __restrict__ part_l2, const long long* __restrict__ part_sse,
+            long long* __restrict__ sse, double* __restrict__ ssim, double* __restrict__ l2, int N, int C, int H, int W, int tiles) {
+#pragma clang fp contract(off)
+    const int n = blockIdx.x * blockDim.x + threadIdx.x;
+    if (n >= N) return;
+    const double interior = (double)(H - 6) * (double)(W - 6);
+    long long e = 0;
+    double l = 0.0, s = 0.0;
+    for (int c = 0; c < C; ++c) {
+        const long long base = ((long long)n * C + c) * tiles;
+        double sc = 0.0;
+        for (int t = 0; t < tiles; ++t) {
+            sc += part_ssim[base + t];
+            l += part_l2[base + t];
+            e += part_sse[base + t];
+        }
+        s += sc / interior;
+    }
+    sse[n] = e;
+    ssim[n] = s / (double)C;
+    l2[n] = l / ((double)C * (double)H * (double)W);
+}
+
+struct Plan {
+    int nby, nbx;
+    long long tiles_total;    // N * C * nby * nbx
+};
+
+inline Plan plan(int N, int C, int H, int W) {
+    Plan p;
+    p.nby = (H - 6 + BH - 1) / BH;
+    p.nbx = (W - 6 + TW - 1) / TW;
+    p.tiles_total = (long long)N * C * p.nby * p.nbx;
+    return p;
+}
+
+}  // namespace fmetrics

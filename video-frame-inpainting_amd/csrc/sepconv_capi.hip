@@ -27,6 +27,7 @@
 #include "conv_bf16.hip.inc"
 #include "spectral_norm.hip.inc"
 #include "hbm_probe.hip.inc"
+#include "frame_metrics.hip.inc"
 
 namespace {
 
@@ -1591,6 +1592,36 @@ int tai_conv_bf16_forward(const float* const* xs, int nparts, const void* Wp, co
 #undef TAI_BF16_ACT
 #undef TAI_BF16_LAUNCH
     return check_launch("conv_bf16_forward");
+}
+
+long long tai_frame_metrics_workspace_bytes(int N, int C, int H, int W) {
+    if (N <= 0 || C <= 0 || H < 7 || W < 7) return TAI_SEPCONV_EINVAL;
+    const fmetrics::Plan pl = fmetrics::plan(N, C, H, W);
+    if (pl.tiles_total >= (1LL << 31)) return TAI_SEPCONV_EINVAL;
+    return pl.tiles_total * (2 * (long long)sizeof(double) + (long long)sizeof(long long));
+}
+
+int tai_frame_metrics(const float* pred, const float* gt, long long* sse, double* ssim, double* l2, void* workspace, int N, int C,
+                      int H, int W, void* hip_stream) {
+    g_err[0] = 0;
+    if (!pred || !gt || !sse || !ssim || !l2 || !workspace) return fail(TAI_SEPCONV_EINVAL, "%s", "frame_metrics: null pointer");
+    if (N <= 0 || C <= 0 || H < 7 || W < 7)
+        return fail(TAI_SEPCONV_EINVAL, "%s", "frame_metrics: needs N, C >= 1 and H, W >= 7 (the 7x7 SSIM window)");
+    if ((long long)N * C * H * W >= (1LL << 40) || (long long)H * W >= (1LL << 31))
+        return fail(TAI_SEPCONV_EINVAL, "%s", "frame_metrics: tensor too large");
+    if (reinterpret_cast<uintptr_t>(workspace) % 8 != 0) return fail(TAI_SEPCONV_EINVAL, "%s", "frame_metrics: workspace must be 8-byte aligned");
+    const fmetrics::Plan pl = fmetrics::plan(N, C, H, W);
+    if (pl.tiles_total >= (1LL << 31)) return fail(TAI_SEPCONV_EINVAL, "%s", "frame_metrics: too many tiles (2^31 or more)");
+    double* part_ssim = static_cast<double*>(workspace);
+    double* part_l2 = part_ssim + pl.tiles_total;
+    long long* part_sse = reinterpret_cast<long long*>(part_l2 + pl.tiles_total);
+    hipStream_t s = static_cast<hipStream_t>(hip_stream);
+    hipLaunchKernelGGL(fmetrics::tile_partials, dim3((unsigned)pl.tiles_total), dim3(fmetrics::THREADS), 0, s, pred, gt, part_ssim, part_l2,
+                       part_sse, H, W, pl.nby, pl.nbx);
+    if (int rc = check_launch("frame_metrics tile_partials")) return rc;
+    hipLaunchKernelGGL(fmetrics::finish, dim3((unsigned)((N + 63) / 64)), dim3(64), 0, s, part_ssim, part_l2, part_sse, sse, ssim, l2, N, C, H,
+                       W, pl.nby * pl.nbx);
+    return check_launch("frame_metrics finish");
 }
 
 }  // extern "C"

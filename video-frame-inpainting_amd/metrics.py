@@ -69,3 +69,67 @@ def summarize(table):
     """Mean over frames, then mean +- std/sqrt(N) over videos (summarize_quant_results.py:223-228)."""
     per_video = np.mean(table, axis=1)
     return float(np.mean(per_video)), float(np.std(per_video) / np.sqrt(len(per_video)))
+
+
+def psnr_from_sse(sse, n_values):
+    """PSNR of one frame from its exact integer SSE over ``n_values`` uint8 values: ``psnr_uint8``'s expression on the same
+    float64 MSE (numpy's mean is the float64 sum divided by the count, and the sum of squared uint8 differences is exact)."""
+    if sse == 0:
+        return float('inf')
+    mse = np.float64(sse) / n_values
+    return 10 * np.log10(255.0 ** 2 / mse)
+
+
+def frame_metrics_device(pred, gt, out=None, workspace=None):
+    """Launch the HIP frame-metrics kernels (``tai_frame_metrics``) on the current stream of ``pred``'s device.  pred, gt: CUDA
+    [..., C, H, W] tensors of the same shape (fp32, contiguous after conversion); N = the product of the leading dimensions.
+    Returns ``out``: a float64 device tensor [3, N] whose row 0 holds the exact SSE as int64 bits (``out[0].view(torch.int64)``),
+    row 1 the SSIM and row 2 the L2 term.  ``out`` and ``workspace`` (uint8, ``tai_frame_metrics_workspace_bytes``) may be given:
+    then nothing is allocated and the call can be captured into a hipGraph."""
+    import torch
+    from . import _native
+    if pred.shape != gt.shape or pred.dim() < 3:
+        raise ValueError('frame_metrics_device: pred %s and gt %s must have one shape [..., C, H, W]'
+                         % (tuple(pred.shape), tuple(gt.shape)))
+    C, H, W = pred.shape[-3:]
+    N = pred.numel() // max(C * H * W, 1)
+    dev = pred.device
+    p = pred.detach().to(torch.float32).contiguous()
+    g = gt.detach().to(device=dev, dtype=torch.float32).contiguous()
+    L = _native.lib()
+    nbytes = L.tai_frame_metrics_workspace_bytes(N, C, H, W)
+    if nbytes < 0:
+        raise ValueError('frame_metrics_device: needs N, C >= 1 and H, W >= 7 (the 7x7 SSIM window), got [%d, %d, %d, %d]'
+                         % (N, C, H, W))
+    if workspace is None:
+        workspace = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    if workspace.numel() * workspace.element_size() < nbytes:
+        raise ValueError('frame_metrics_device: workspace holds %d bytes, %d needed'
+                         % (workspace.numel() * workspace.element_size(), nbytes))
+    if out is None:
+        out = torch.empty(3, N, dtype=torch.float64, device=dev)
+    if out.dtype != torch.float64 or tuple(out.shape) != (3, N) or not out.is_contiguous():
+        raise ValueError('frame_metrics_device: out must be a contiguous float64 [3, %d] tensor' % N)
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        _native.check(L.tai_frame_metrics(p.data_ptr(), g.data_ptr(), out[0].data_ptr(), out[1].data_ptr(), out[2].data_ptr(),
+                                          workspace.data_ptr(), N, C, H, W, stream), 'tai_frame_metrics')
+    return out
+
+
+def compute_errors_device(pred, gt):
+    """``compute_errors`` for [B, T, C, H, W] tensors.  CUDA tensors are scored by the HIP kernel (one launch pair, one copy of
+    the [3, B T] results to the host); PSNR is then formed on the host from the exact SSE with ``psnr_uint8``'s expression, so
+    it is bit-identical to ``compute_errors``; SSIM agrees to float64 rounding of the interior mean's summation order, L2 to the
+    float32 rounding of the host's sum.  CPU tensors (and arrays) go to ``compute_errors``.  -> (psnr, ssim, l2), float64 [B, T]."""
+    import torch
+    if not (torch.is_tensor(pred) and pred.is_cuda):
+        to_np = lambda x: x.detach().cpu().numpy() if torch.is_tensor(x) else x
+        return compute_errors(to_np(pred), to_np(gt))
+    if pred.dim() != 5:
+        raise ValueError('compute_errors_device: expected [B, T, C, H, W], got %s' % (tuple(pred.shape),))
+    B, T, C, H, W = pred.shape
+    host = frame_metrics_device(pred, gt).cpu().numpy()
+    sse = host[0].view(np.int64)
+    psnr = np.array([psnr_from_sse(int(e), C * H * W) for e in sse], dtype=np.float64)
+    return psnr.reshape(B, T), host[1].reshape(B, T).copy(), host[2].reshape(B, T).copy()

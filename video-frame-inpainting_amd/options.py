@@ -82,6 +82,10 @@ class TrainOptions(BaseOptions):
                      'val_video_list_alt_K_F_path', 'vis_video_list_path', 'vis_video_list_alt_T_path',
                      'vis_video_list_alt_K_F_path'):
             g.add_argument('--' + name, type=str, default=None)
+        g.add_argument('--val_synthetic', type=int, default=0, metavar='N_CLIPS',
+                       help='(this build) validate on N seeded synthetic clips (a seed other than the training clips\') instead of '
+                            'the --val_video_list* lists: every --validate_freq updates, the (K, T, F) leg, the (K, alt_T, F) leg when '
+                            '--alt_T is given and the (alt_K, T, alt_F) leg when --alt_K and --alt_F are')
         g.add_argument('--serial_batches', action='store_true')
         g.add_argument('--no_backwards', action='store_true')
         g.add_argument('--no_flip', action='store_true')

@@ -215,3 +215,30 @@ def allreduce_scalar_mean(value, device):
     t = torch.tensor([float(value)], dtype=torch.float64, device=device)
     dist.all_reduce(t)
     return float(t.item() / world_size())
+
+
+def gather_rows(table, n_items):
+    """All-gather per-item rows: rank r holds the rows of ``shard_slice(n_items, r, world)`` (any trailing shape, shards of
+    uneven length); every rank gets the [n_items, ...] float64 table in item order.  One padded ``all_gather`` (on the current GPU
+    under nccl, on the CPU under gloo)."""
+    import numpy as np
+    table = np.asarray(table, dtype=np.float64)
+    world, me = world_size(), rank()
+    mine = shard_slice(n_items, me, world)
+    if table.shape[0] != mine.stop - mine.start:
+        raise ValueError('gather_rows: rank %d holds %d rows, its shard of %d items has %d'
+                         % (me, table.shape[0], n_items, mine.stop - mine.start))
+    if world == 1:
+        return table
+    per = -(-n_items // world)
+    dev = torch.device('cuda', torch.cuda.current_device()) if dist.get_backend() == 'nccl' else torch.device('cpu')
+    buf = torch.zeros((per,) + table.shape[1:], dtype=torch.float64)
+    buf[:table.shape[0]] = torch.from_numpy(table)
+    buf = buf.to(dev)
+    parts = [torch.empty_like(buf) for _ in range(world)]
+    dist.all_gather(parts, buf)
+    rows = []
+    for r, part in enumerate(parts):
+        s = shard_slice(n_items, r, world)
+        rows.append(part[:s.stop - s.start].cpu().numpy())
+    return np.concatenate(rows, axis=0)
