@@ -411,6 +411,36 @@ long long tai_frame_metrics_workspace_bytes(int N, int C, int H, int W);
 int tai_frame_metrics(const float* pred, const float* gt, long long* sse, double* ssim, double* l2, void* workspace, int N, int C,
                       int H, int W, void* hip_stream);
 
+/* The clip pipeline's two ends (csrc/clip_pipeline.hip.inc): what stands between a decoded frame and the models, and between the models
+ * and a PNG, bit-equal to the host code (video_frame_inpainting_amd/data.py and util.py) it replaces when asked to.
+ *
+ * tai_clip_from_frames replaces the per-frame host pipeline of src/data/base_dataset.py:50-103 (cv2.resize, RGB -> BGR, flip,
+ * copyMakeBorder, to_tensor, fore_transform, bgr2gray) for a whole batch in one launch.
+ *   frames      device buffer of frames_bytes bytes holding uint8 RGB frames [h_i][w_i][3], packed in any order;
+ *   table       device copy, and table_host a host copy, of N descriptors of four 64-bit integers {byte offset of the frame in `frames`,
+ *               h_i, w_i, flags (bit 0: mirror the output columns)}; frames of one call may differ in source size.  table_host is
+ *               read before the call returns and checked against frames_bytes; the kernel re-checks the device copy per frame and
+ *               writes the padding level for a frame whose descriptor is out of range, so a table that is changed under a replayed
+ *               graph cannot become an out-of-bounds read;
+ *   levels      device [4][256] fp32: row 0 the value of level q, (float(q) / 255) * 2 - 1; rows 1-3 the products 0.1140, 0.5870,
+ *               0.2989 x row 0 -- computed by the caller with the host path's own expressions (clip_pipeline.level_tables);
+ *   out         contiguous fp32 [N][c_dim][H + pad_h][W + pad_w], every element written: bilinear resize to H x W (half-pixel
+ *               centres, edge clamp, fp64, round half up), BGR channel order (c_dim 3) or (B' + G') + R' (c_dim 1), padding = level 0.
+ * Time reversal is an ordering of the descriptors.  A frame's output depends on its own descriptor and pixels only.
+ *
+ * tai_frames_to_uint8 replaces predict.py:103-120's way out (clip, inverse_transform, x 255, truncating uint8 cast, channel-last,
+ * BGR -> RGB): x contiguous fp32 [N][C][Hs][Ws], out uint8 [N][h][w][C] = the top-left h x w of every plane,
+ * u(x) = uint8(trunc(255 * ((clip(x, -1, 1) + 1) / 2))) in fp32 (the u of tai_frame_metrics); reverse_channels != 0 writes channel
+ * C - 1 - c at position c.  NaN maps to 0.
+ *
+ * Both: caller-allocated buffers, no allocation, copy or synchronisation, asynchronous on hip_stream, capturable into a hipGraph.
+ * TAI_SEPCONV_EINVAL with a message for a null pointer, c_dim / C outside {1, 3}, non-positive sizes, a descriptor that points past
+ * frames_bytes, or an index space of 2^31 elements or more; nothing is launched then. */
+int tai_clip_from_frames(const unsigned char* frames, long long frames_bytes, const long long* table, const long long* table_host,
+                         const float* levels, float* out, int N, int c_dim, int H, int W, int pad_h, int pad_w, void* hip_stream);
+int tai_frames_to_uint8(const float* x, unsigned char* out, int N, int C, int Hs, int Ws, int h, int w, int reverse_channels,
+                        void* hip_stream);
+
 /* Text of the last error on the calling thread ("" if none). */
 const char* tai_sepconv_last_error(void);
 

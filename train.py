@@ -19,7 +19,7 @@ import numpy as np
 import torch
 
 import video_frame_inpainting_amd as vfi
-from video_frame_inpainting_amd import parallel, synthetic
+from video_frame_inpainting_amd import clip_pipeline, parallel, synthetic
 from video_frame_inpainting_amd.data import ContiguousVideoClipDataset
 from video_frame_inpainting_amd.environments import create_training_environment
 from video_frame_inpainting_amd.options import TrainOptions
@@ -40,18 +40,23 @@ def main(args=None):
     H, W = opt.image_size[0] + opt.padding_size[0], opt.image_size[1] + opt.padding_size[1]
     loader = None
     if getattr(opt, 'train_video_list_path', None) and not opt.synthetic:
+        # --device_preprocess: the workers hand over raw uint8 frames and the GPU builds the (bit-identical) clip tensor
+        on_device = bool(getattr(opt, 'device_preprocess', False))
         dataset = ContiguousVideoClipDataset(opt.c_dim, opt.train_video_list_path, opt.K + opt.T + opt.F, not opt.no_backwards,
-                                             not opt.no_flip, opt.image_size, True, opt.padding_size, seed=opt.seed + 7 * rank)
+                                             not opt.no_flip, opt.image_size, True, opt.padding_size, seed=opt.seed + 7 * rank,
+                                             raw=on_device)
         gen = torch.Generator().manual_seed(opt.seed + 7 * rank)
         loader = torch.utils.data.DataLoader(dataset, batch_size=opt.batch_size, shuffle=not opt.serial_batches,
                                              num_workers=opt.num_threads, drop_last=True, generator=gen,
-                                             worker_init_fn=dataset.worker_init)
+                                             worker_init_fn=dataset.worker_init,
+                                             collate_fn=clip_pipeline.collate_for(opt.num_threads) if on_device else None)
+        builder = clip_pipeline.DeviceClipBuilder(opt.c_dim, opt.image_size, opt.padding_size, device) if on_device else None
         print('# training videos = %d' % len(dataset))
 
         def batches():                                               # inf_data_loader (train.py:41)
             while True:
                 for item in loader:
-                    yield item['targets']
+                    yield builder.build(item) if on_device else item['targets']
         stream = batches()
     else:
         n_clips = opt.synthetic or 64

@@ -281,6 +281,10 @@ def lib():
     L.tai_frame_metrics_workspace_bytes.restype = ctypes.c_longlong
     L.tai_frame_metrics.argtypes = [P, P, P, P, P, P, I, I, I, I, V]
     L.tai_frame_metrics.restype = I
+    L.tai_clip_from_frames.argtypes = [P, ctypes.c_longlong, P, P, P, P, I, I, I, I, I, I, V]
+    L.tai_clip_from_frames.restype = I
+    L.tai_frames_to_uint8.argtypes = [P, P, I, I, I, I, I, I, I, V]
+    L.tai_frames_to_uint8.restype = I
     L.tai_sepconv_last_error.restype = ctypes.c_char_p
     L.tai_sepconv_source_hash.restype = ctypes.c_char_p
     L.tai_sepconv_version.restype = I

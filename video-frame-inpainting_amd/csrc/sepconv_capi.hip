@@ -28,6 +28,7 @@
 #include "spectral_norm.hip.inc"
 #include "hbm_probe.hip.inc"
 #include "frame_metrics.hip.inc"
+#include "clip_pipeline.hip.inc"
 
 namespace {
 
@@ -281,7 +282,7 @@ int launch_grad_vh_tiled(const float* gO, const float* in, const float* v, const
 
 extern "C" {
 
-int tai_sepconv_version(void) { return 500; }     // 0.5.0: F(4x4, 3x3) chunk loop as generated assembly, displaced-read blocks, any C; (0.4.1: persistent forward kernel beyond the Infinity Cache: type-A waves at their partners' priority (0.4.0: nt tap loads + reversed walk; source hash))
+int tai_sepconv_version(void) { return 600; }     // 0.6.0: clip pipeline entry points (tai_clip_from_frames, tai_frames_to_uint8), no other kernel changed; (0.5.0: F(4x4, 3x3) chunk loop as generated assembly, displaced-read blocks, any C; (0.4.1: persistent forward kernel beyond the Infinity Cache: type-A waves at their partners' priority (0.4.0: nt tap loads + reversed walk; source hash)))
 
 const char* tai_sepconv_last_error(void) { return g_err; }
 
@@ -1622,6 +1623,52 @@ int tai_frame_metrics(const float* pred, const float* gt, long long* sse, double
     hipLaunchKernelGGL(fmetrics::finish, dim3((unsigned)((N + 63) / 64)), dim3(64), 0, s, part_ssim, part_l2, part_sse, sse, ssim, l2, N, C, H,
                        W, pl.nby * pl.nbx);
     return check_launch("frame_metrics finish");
+}
+
+int tai_clip_from_frames(const unsigned char* frames, long long frames_bytes, const long long* table, const long long* table_host,
+                         const float* levels, float* out, int N, int c_dim, int H, int W, int pad_h, int pad_w, void* hip_stream) {
+    g_err[0] = 0;
+    if (!frames || !table || !table_host || !levels || !out) return fail(TAI_SEPCONV_EINVAL, "%s", "clip_from_frames: null pointer");
+    if (c_dim != 1 && c_dim != 3) return fail(TAI_SEPCONV_EINVAL, "%s", "clip_from_frames: c_dim must be 1 or 3");
+    if (N <= 0 || H <= 0 || W <= 0 || pad_h < 0 || pad_w < 0 || frames_bytes <= 0)
+        return fail(TAI_SEPCONV_EINVAL, "%s", "clip_from_frames: needs N, H, W, frames_bytes > 0 and pad_h, pad_w >= 0");
+    const long long Hp = (long long)H + pad_h, Wp = (long long)W + pad_w;
+    if (Hp >= (1LL << 24) || Wp >= (1LL << 24) || (long long)N * c_dim * Hp * Wp >= (1LL << 31) || frames_bytes >= (1LL << 40))
+        return fail(TAI_SEPCONV_EINVAL, "%s", "clip_from_frames: index space too large (2^31 output elements or more)");
+    for (int n = 0; n < N; ++n) {
+        const long long off = table_host[4 * n], h = table_host[4 * n + 1], w = table_host[4 * n + 2];
+        if (h <= 0 || w <= 0 || h >= (1LL << 24) || w >= (1LL << 24))
+            return fail(TAI_SEPCONV_EINVAL, "%s", "clip_from_frames: a frame descriptor has a non-positive or oversized source size");
+        if (off < 0 || off > frames_bytes || h * w * 3 > frames_bytes - off)
+            return fail(TAI_SEPCONV_EINVAL, "%s", "clip_from_frames: a frame descriptor points past the stated length of the frame buffer");
+    }
+    const bool vec4 = Wp % 4 == 0 && reinterpret_cast<uintptr_t>(out) % 16 == 0;
+    const int runs_per_row = (int)((Wp + 3) / 4);
+    const long long total_runs = (long long)N * Hp * runs_per_row;
+    hipStream_t s = static_cast<hipStream_t>(hip_stream);
+    const dim3 grid(clip::blocks_for(total_runs)), block(clip::THREADS);
+#define TAI_CLIP_LAUNCH(C_, V_) hipLaunchKernelGGL((clip::from_frames<C_, V_>), grid, block, 0, s, frames, frames_bytes, table, levels, out, N, H, W, \
+                                                   (int)Hp, (int)Wp, runs_per_row, total_runs)
+    if (c_dim == 1) { if (vec4) TAI_CLIP_LAUNCH(1, true); else TAI_CLIP_LAUNCH(1, false); }
+    else            { if (vec4) TAI_CLIP_LAUNCH(3, true); else TAI_CLIP_LAUNCH(3, false); }
+#undef TAI_CLIP_LAUNCH
+    return check_launch("clip_from_frames");
+}
+
+int tai_frames_to_uint8(const float* x, unsigned char* out, int N, int C, int Hs, int Ws, int h, int w, int reverse_channels,
+                        void* hip_stream) {
+    g_err[0] = 0;
+    if (!x || !out) return fail(TAI_SEPCONV_EINVAL, "%s", "frames_to_uint8: null pointer");
+    if (C != 1 && C != 3) return fail(TAI_SEPCONV_EINVAL, "%s", "frames_to_uint8: C must be 1 or 3");
+    if (N <= 0 || Hs <= 0 || Ws <= 0 || h <= 0 || w <= 0 || h > Hs || w > Ws)
+        return fail(TAI_SEPCONV_EINVAL, "%s", "frames_to_uint8: needs N > 0 and 0 < h <= Hs, 0 < w <= Ws");
+    if ((long long)N * C * Hs * Ws >= (1LL << 31)) return fail(TAI_SEPCONV_EINVAL, "%s", "frames_to_uint8: index space too large (2^31 elements or more)");
+    const long long total = (long long)N * h * w;
+    hipStream_t s = static_cast<hipStream_t>(hip_stream);
+    const dim3 grid(clip::blocks_for(total)), block(clip::THREADS);
+    if (C == 1) hipLaunchKernelGGL((clip::to_uint8<1>), grid, block, 0, s, x, out, Hs, Ws, h, w, reverse_channels != 0, total);
+    else        hipLaunchKernelGGL((clip::to_uint8<3>), grid, block, 0, s, x, out, Hs, Ws, h, w, reverse_channels != 0, total);
+    return check_launch("frames_to_uint8");
 }
 
 }  // extern "C"

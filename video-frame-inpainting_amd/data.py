@@ -164,6 +164,24 @@ class _ClipReader(object):
         clip = fore_transform(torch.stack(frames))                  # T x C x H x W in [-1, 1]
         return bgr2gray(clip) if self.c_dim == 1 else clip
 
+    def raw_clip(self, source, indexes, reverse):
+        """The decoded frames of one clip as they are, uint8 RGB [T, h, w, 3] in playback order (``reverse`` applied): what the
+        device clip pipeline (clip_pipeline.DeviceClipBuilder) takes in place of ``clip``'s tensor.  None on a read error, like
+        ``clip``; frames of one clip must share one size."""
+        frames = []
+        for t in indexes:
+            raw = self.frame(source, t)
+            if raw is None:
+                return None
+            if raw.ndim != 3 or raw.shape[2] != 3 or raw.dtype != np.uint8 or (frames and raw.shape != frames[0].shape):
+                warn('Frame %d in %s is not [h, w, 3] uint8 of the clip\'s size: %s %s'
+                     % (t, getattr(source, '_filename', '?'), raw.shape, raw.dtype))
+                return None
+            frames.append(raw)
+        if reverse:
+            frames.reverse()
+        return torch.from_numpy(np.stack(frames))
+
 
 class ContiguousVideoClipDataset(data.Dataset):
     """base_dataset.py:17-202: one line per video, ``<path>`` or ``<path> <a>-<b>``; an item is a random window of
@@ -173,10 +191,14 @@ class ContiguousVideoClipDataset(data.Dataset):
     Every random draw (window start, augmentation coin flips, replacement line) comes from a PRIVATE generator seeded per
     dataset (``seed``; reseeded per DataLoader worker by ``worker_init``): the reference draws from the global ``random``
     and ``numpy.random`` modules, which in a data-parallel run is also where (K, T, F) used to come from -- one rank's
-    decode retry would desynchronise every rank's model shapes."""
+    decode retry would desynchronise every rank's model shapes.
+
+    ``raw=True`` (the device clip pipeline, clip_pipeline.py): an item is ``{'frames': uint8 [T, h, w, 3] RGB as decoded, in
+    playback order, 'mirror': bool, 'clip_label': str}`` -- the same draws in the same order pick the same window, mirror and
+    reversal; the resize, flip, padding, range map and gray conversion are left to the GPU."""
 
     def __init__(self, c_dim, video_list_path, seq_length, backwards, flip, image_size, resample_on_fail, padding_size,
-                 seed=0):
+                 seed=0, raw=False):
         super().__init__()
         with open(video_list_path, 'r') as f:
             self.files = [line.strip() for line in f.readlines()]
@@ -184,6 +206,7 @@ class ContiguousVideoClipDataset(data.Dataset):
         self.backwards, self.flip, self.resample_on_fail = backwards, flip, resample_on_fail
         self.reader = _ClipReader(c_dim, image_size, padding_size)
         self._seed = int(seed)
+        self.raw = bool(raw)
         self.rng = random.Random(self._seed)
 
     def worker_init(self, worker_id):
@@ -210,6 +233,11 @@ class ContiguousVideoClipDataset(data.Dataset):
         start = self.rng.randint(first, last - self.seq_len + 1)
         mirror = self.flip and self.rng.random() > 0.5
         reverse = self.backwards and self.rng.random() > 0.5
+        if self.raw:
+            frames = self.reader.raw_clip(source, range(start, start + self.seq_len), reverse)
+            if frames is None:
+                return None, 'Failed to sample frames starting at %d in %s' % (start, record.path)
+            return {'frames': frames, 'mirror': bool(mirror), 'clip_label': record.label([(first, last)])}, None
         clip = self.reader.clip(source, range(start, start + self.seq_len), mirror, reverse)
         if clip is None:
             return None, 'Failed to sample frames starting at %d in %s' % (start, record.path)
@@ -228,8 +256,8 @@ class DisjointVideoClipDataset(ContiguousVideoClipDataset):
     """base_dataset.py:205-248: ``<path> <a>-<b> <c>-<d>``: the preceding frames a..b and the following frames c..d,
     nothing in between; no augmentation, no resampling."""
 
-    def __init__(self, c_dim, video_list_path, K, F, image_size, padding_size):
-        super().__init__(c_dim, video_list_path, None, False, False, image_size, False, padding_size)
+    def __init__(self, c_dim, video_list_path, K, F, image_size, padding_size, raw=False):
+        super().__init__(c_dim, video_list_path, None, False, False, image_size, False, padding_size, raw=raw)
         self.K, self.F = K, F
 
     def __getitem__(self, index):
@@ -244,6 +272,11 @@ class DisjointVideoClipDataset(ContiguousVideoClipDataset):
         if source is None:
             raise RuntimeError('Video at %s could not be opened' % record.path)
         indexes = [t for a, b in record.spans for t in range(a, b + 1)]
+        if self.raw:
+            frames = self.reader.raw_clip(source, indexes, False)
+            if frames is None:
+                raise RuntimeError('Failed to sample frames %s in %s' % (record.label(record.spans), record.path))
+            return {'frames': frames, 'mirror': False, 'clip_label': record.label(record.spans)}
         clip = self.reader.clip(source, indexes, False, False)
         if clip is None:
             raise RuntimeError('Failed to sample frames %s in %s' % (record.label(record.spans), record.path))

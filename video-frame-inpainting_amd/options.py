@@ -31,6 +31,12 @@ class BaseOptions(object):
         g.add_argument('--synthetic', type=int, default=0, metavar='N_CLIPS',
                        help='(this build) run on N seeded synthetic clips instead of a video list')
         g.add_argument('--seed', type=int, default=1002, help='(this build) seed of the synthetic clips')
+        g.add_argument('--device_preprocess', action='store_true',
+                       help='(this build) build clips on the GPU from raw decoded frames (clip_pipeline.py: resize, BGR, flip, padding, '
+                            'range map and gray in one HIP launch per batch; PNG pixels and PSNR / SSIM on the GPU in predict.py), '
+                            'bit-equal to the host path; off = the host path, unchanged.  Ignored with --synthetic.  A clip window '
+                            'inside a span longer than K + T + F is a seeded draw: with --num_threads 0 the flag reproduces the '
+                            "default path's windows, with workers each worker draws from its own copy of the generator")
         g.add_argument('--winograd_arithmetic', type=str, default='fp32', choices=['fp32', 'bf16x3'],
                        help='(this build) arithmetic of the 3x3 Winograd GEMMs: fp32 = the fp32 MFMA (default, the arithmetic every '
                             'parity statement is made on); bf16x3 = opt-in split bf16 (three bf16 terms per operand, six products, '

@@ -18,7 +18,7 @@ import time
 import numpy as np
 import torch
 
-from . import metrics, parallel, synthetic
+from . import clip_pipeline, metrics, parallel, synthetic
 
 VAL_SEED_OFFSET = 104729          # validation clips: --seed + this (training clips use --seed + rank)
 
@@ -70,15 +70,21 @@ def leg_batches(leg, opt, rank, world, cache=None):
                 cache[leg] = clips
         return n, (clips[i:i + opt.batch_size] for i in range(0, clips.shape[0], opt.batch_size))
     from .data import ContiguousVideoClipDataset
+    on_device = bool(getattr(opt, 'device_preprocess', False))       # raw frames in, the clip tensor built on the GPU (same bits)
     # built afresh for every pass with a fixed seed: each validation scores the same windows
     dataset = ContiguousVideoClipDataset(opt.c_dim, leg.source, length, False, False, opt.image_size, False, opt.padding_size,
-                                         seed=opt.seed + VAL_SEED_OFFSET)
+                                         seed=opt.seed + VAL_SEED_OFFSET, raw=on_device)
     n = len(dataset)
     mine = range(n)[parallel.shard_slice(n, rank, world)]
     loader = torch.utils.data.DataLoader(torch.utils.data.Subset(dataset, list(mine)), batch_size=opt.batch_size, shuffle=False,
                                          num_workers=opt.num_threads, drop_last=False,
                                          generator=torch.Generator().manual_seed(opt.seed + VAL_SEED_OFFSET),
-                                         worker_init_fn=dataset.worker_init)
+                                         worker_init_fn=dataset.worker_init,
+                                         collate_fn=clip_pipeline.collate_for(opt.num_threads) if on_device else None)
+    if on_device:
+        builder = clip_pipeline.DeviceClipBuilder(opt.c_dim, opt.image_size, opt.padding_size,
+                                                  torch.device('cuda', torch.cuda.current_device()))
+        return n, (builder.build(item) for item in loader)
     return n, (item['targets'] for item in loader)
 
 
