@@ -441,6 +441,24 @@ int tai_clip_from_frames(const unsigned char* frames, long long frames_bytes, co
 int tai_frames_to_uint8(const float* x, unsigned char* out, int N, int C, int Hs, int Ws, int h, int w, int reverse_channels,
                         void* hip_stream);
 
+/* A 64-bit digest of a training state where it lives (csrc/state_digest.hip.inc; video_frame_inpainting_amd/run_state.py builds the
+ * table; no counterpart in the reference, whose snapshots carry no check).  On the raw 32-bit words, integer arithmetic modulo 2^64 only:
+ *   mix(z): z += 0x9E3779B97F4A7C15; z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9; z = (z ^ (z >> 27)) * 0x94D049BB133111EB; z ^ (z >> 31)
+ *   entry t with words w[0..n_t) (an 8-byte element is two words, low word first):  E_t = sum_i mix((i << 32) + w[i])
+ *   D = 0x243F6A8885A308D3; for t in table order: D = mix(D ^ E_t); D = mix(D + n_t)
+ * table / table_host: a device and a host copy of n_entries rows of four 64-bit integers {address (a multiple of 4; 0 = the entry lives on
+ * the host or is empty), n_t, E_t as the caller computed it for an entry with address 0 (ignored otherwise), first segment}: an entry
+ * with an address is cut into ceil(n_t / seg_words) segments numbered consecutively in table order, n_segments in all; seg_words is a
+ * positive multiple of 4.  table_host is read before the call returns and refused (TAI_SEPCONV_EINVAL, nothing launched) unless the
+ * segment numbers are exactly those; the kernels read [address, address + 4 n_t) of every entry and nothing else.
+ * workspace: tai_state_digest_workspace_bytes(n_entries, n_segments) bytes, 8-byte aligned; result: one device uint64.
+ * The result depends on the words, their order inside an entry and the order of the entries -- not on seg_words, the grid, the addresses
+ * or on which side an entry lives.  One launch over the segments (16-byte loads where the address allows, per-segment sums to the
+ * workspace, no atomics) and a one-workgroup finish in index order.  No allocation, copy or synchronisation; asynchronous on hip_stream. */
+long long tai_state_digest_workspace_bytes(int n_entries, long long n_segments);
+int tai_state_digest(const long long* table, const long long* table_host, int n_entries, long long n_segments, long long seg_words,
+                     void* workspace, unsigned long long* result, void* hip_stream);
+
 /* Text of the last error on the calling thread ("" if none). */
 const char* tai_sepconv_last_error(void);
 

@@ -9,6 +9,11 @@ augmentation flags, train.py:37-43; video_frame_inpainting_amd/data.py; each ran
 seeded synthetic clips, scored on the GPU (metrics.compute_errors_device); the snapshot with the best summed per-frame SSIM of
 the first leg is kept as ``model_best.ckpt``.  TensorBoard logging is outside the hot path.
 
+``--resumable``: a run cut into several processes is the same run, bit for bit.  Snapshots carry ``run_state`` (run_state.py: the
+spectral-norm vectors, every generator state, the clip order's position, a state digest computed on the GPU), the clip order is one
+that can be entered at any position (data.ResumableBatchSampler), SIGTERM / SIGINT / ``--max_wall_minutes`` end the run after the
+update in flight with ``model_latest.ckpt`` written, and every printed line ends with the state digest (``state=%016x``).
+
   python train.py --name demo --K 5 --T 5 --F 5 --c_dim 1 --image_size 128 --batch_size 4 --model_key TAI_gray \
       --max_iter 10 --synthetic 64
 """
@@ -19,8 +24,8 @@ import numpy as np
 import torch
 
 import video_frame_inpainting_amd as vfi
-from video_frame_inpainting_amd import clip_pipeline, parallel, synthetic
-from video_frame_inpainting_amd.data import ContiguousVideoClipDataset
+from video_frame_inpainting_amd import clip_pipeline, parallel, run_state, synthetic, tai
+from video_frame_inpainting_amd.data import ContiguousVideoClipDataset, ResumableBatchSampler
 from video_frame_inpainting_amd.environments import create_training_environment
 from video_frame_inpainting_amd.options import TrainOptions
 from video_frame_inpainting_amd.validation import Validator
@@ -28,6 +33,30 @@ from video_frame_inpainting_amd.validation import Validator
 
 def main(args=None):
     opt = TrainOptions().parse(args, allow_unknown=True)
+    if not opt.resumable:
+        return _run(opt, None)
+    if opt.graph_step and GRAPH_STEP_REFUSAL:
+        raise SystemExit('--resumable refuses --graph_step: ' + GRAPH_STEP_REFUSAL)
+    # the handlers only set a flag; the loop looks at it between updates.  Whatever was installed before is back when main returns.
+    stop = run_state.StopRequest(opt.max_wall_minutes)
+    stop.install()
+    # a resumed run can only repeat the uninterrupted one if an update is a function of the state: no float atomics in any backward
+    # (the replication padding's in ATen, MIOpen's weight gradients on the shapes the in-tree kernels leave to it)
+    previous = (tai.set_reproducible_backward(True), torch.backends.cudnn.deterministic)
+    torch.backends.cudnn.deterministic = True
+    try:
+        return _run(opt, stop)
+    finally:
+        tai.set_reproducible_backward(previous[0])
+        torch.backends.cudnn.deterministic = previous[1]
+        stop.uninstall()
+
+
+GRAPH_STEP_REFUSAL = None       # a reason, if a replayed update were found to differ from an eager one
+
+
+def _run(opt, stop):
+    resumable = stop is not None
     if getattr(opt, 'miopen_find_mode', None):          # before the first convolution reaches MIOpen
         os.environ['MIOPEN_FIND_MODE'] = opt.miopen_find_mode
     vfi.configure_miopen()                              # FAST find mode unless set; one find-db / kernel cache per rank
@@ -44,18 +73,30 @@ def main(args=None):
         on_device = bool(getattr(opt, 'device_preprocess', False))
         dataset = ContiguousVideoClipDataset(opt.c_dim, opt.train_video_list_path, opt.K + opt.T + opt.F, not opt.no_backwards,
                                              not opt.no_flip, opt.image_size, True, opt.padding_size, seed=opt.seed + 7 * rank,
-                                             raw=on_device)
-        gen = torch.Generator().manual_seed(opt.seed + 7 * rank)
-        loader = torch.utils.data.DataLoader(dataset, batch_size=opt.batch_size, shuffle=not opt.serial_batches,
-                                             num_workers=opt.num_threads, drop_last=True, generator=gen,
-                                             worker_init_fn=dataset.worker_init,
-                                             collate_fn=clip_pipeline.collate_for(opt.num_threads) if on_device else None)
+                                             raw=on_device, rank=rank)
+        collate = clip_pipeline.collate_for(opt.num_threads) if on_device else None
+        sampler = None
+        if resumable:
+            # a counter-based order: the draws of position j of epoch e come from (seed, rank, e, j), whichever worker serves it
+            sampler = ResumableBatchSampler(len(dataset), opt.batch_size, opt.seed, rank, serial=opt.serial_batches)
+            # (a generator of its own: every new iterator draws a base seed for its workers, which must not come out of the global
+            # generator -- a run entered in the middle of an epoch makes one iterator more than the uninterrupted one)
+            loader = torch.utils.data.DataLoader(dataset, batch_sampler=sampler, num_workers=opt.num_threads,
+                                                 worker_init_fn=dataset.worker_init, collate_fn=collate,
+                                                 generator=torch.Generator().manual_seed(opt.seed + 7 * rank))
+        else:
+            gen = torch.Generator().manual_seed(opt.seed + 7 * rank)
+            loader = torch.utils.data.DataLoader(dataset, batch_size=opt.batch_size, shuffle=not opt.serial_batches,
+                                                 num_workers=opt.num_threads, drop_last=True, generator=gen,
+                                                 worker_init_fn=dataset.worker_init, collate_fn=collate)
         builder = clip_pipeline.DeviceClipBuilder(opt.c_dim, opt.image_size, opt.padding_size, device) if on_device else None
         print('# training videos = %d' % len(dataset))
 
         def batches():                                               # inf_data_loader (train.py:41)
             while True:
                 for item in loader:
+                    if sampler is not None:
+                        sampler.took_batch()           # counts batches TAKEN (this generator runs on demand), not prefetched ones
                     yield builder.build(item) if on_device else item['targets']
         stream = batches()
     else:
@@ -68,7 +109,7 @@ def main(args=None):
     env = create_training_environment(model, opt.c_dim, opt.checkpoints_dir, opt.name, opt.K, opt.T, opt.F,
                                       opt.image_size, opt.alpha, opt.beta, opt.lr, opt.beta1, opt.df_dim, opt.Ip,
                                       opt.disc_window_size, opt.padding_size, device=device,
-                                      graph_step=opt.graph_step)
+                                      graph_step=opt.graph_step, resumable=resumable)
     env.sync_replicas()
     total_updates = env.start_update
     # a resumed run starts from the best values its snapshot carries (train.py:96-97)
@@ -79,6 +120,23 @@ def main(args=None):
                                                                       '%d synthetic clips' % leg.source[1]
                                                                       if isinstance(leg.source, tuple) else leg.source))
     order = np.random.RandomState(opt.seed + 7 * rank)
+    if resumable:
+        if loader is not None:
+            env.data_state_source = sampler.state
+        else:
+            env.data_state_source = lambda: {'kind': 'synthetic', 'n_clips': n_clips, 'batch_size': opt.batch_size, 'order': order.get_state()}
+        if env.exact_resume:           # position the clip order where the snapshot left it (no draw from any other generator)
+            saved, mine = env.restored_data_state, env.data_state_source()
+            if saved is None or saved.get('kind') != mine['kind']:
+                raise RuntimeError('the snapshot was written with another clip source (%r): it cannot be continued exactly'
+                                   % (saved and saved.get('kind'),))
+            if loader is not None:
+                sampler.load_state(saved)
+            else:
+                if (saved['n_clips'], saved['batch_size']) != (n_clips, opt.batch_size):
+                    raise RuntimeError('the snapshot was written with --synthetic %d --batch_size %d: it cannot be continued exactly'
+                                       % (saved['n_clips'], saved['batch_size']))
+                order.set_state(run_state.numpy_state(saved['order']))
     while total_updates < opt.max_iter:
         t0 = time.time()
         total_updates += 1
@@ -92,9 +150,16 @@ def main(args=None):
         if total_updates % opt.print_freq == 0 or total_updates == 1:
             torch.cuda.synchronize()
             errs = env.get_current_errors()
+            state = ' state=%016x' % run_state.digest(env) if resumable else ''
             if rank == 0:
-                print('iter %d (K,T,F)=(%d,%d,%d) %.3fs  %s' % (total_updates, K, T, F, time.time() - t0,
-                                                                ' '.join('%s=%.5f' % kv for kv in sorted(errs.items()))))
+                print('iter %d (K,T,F)=(%d,%d,%d) %.3fs  %s%s' % (total_updates, K, T, F, time.time() - t0,
+                                                                  ' '.join('%s=%.5f' % kv for kv in sorted(errs.items())), state))
+        if resumable and stop.agreed():
+            # a save has to fit between SIGTERM and SIGKILL: no validation pass is started once the flag is up
+            env.save('model_latest.ckpt', total_updates, *validator.best)
+            if rank == 0:
+                print('Stop requested: model_latest.ckpt holds update %d' % total_updates)
+            return
         if total_updates % opt.save_latest_freq == 0:
             env.save('model_latest.ckpt', total_updates, *validator.best)
             env.save('model_%08d.ckpt' % total_updates, total_updates, *validator.best)

@@ -285,6 +285,10 @@ def lib():
     L.tai_clip_from_frames.restype = I
     L.tai_frames_to_uint8.argtypes = [P, P, I, I, I, I, I, I, I, V]
     L.tai_frames_to_uint8.restype = I
+    L.tai_state_digest_workspace_bytes.argtypes = [I, ctypes.c_longlong]
+    L.tai_state_digest_workspace_bytes.restype = ctypes.c_longlong
+    L.tai_state_digest.argtypes = [P, P, I, ctypes.c_longlong, ctypes.c_longlong, P, P, V]
+    L.tai_state_digest.restype = I
     L.tai_sepconv_last_error.restype = ctypes.c_char_p
     L.tai_sepconv_source_hash.restype = ctypes.c_char_p
     L.tai_sepconv_version.restype = I

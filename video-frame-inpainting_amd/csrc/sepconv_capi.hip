@@ -29,6 +29,7 @@
 #include "hbm_probe.hip.inc"
 #include "frame_metrics.hip.inc"
 #include "clip_pipeline.hip.inc"
+#include "state_digest.hip.inc"
 
 namespace {
 
@@ -282,7 +283,7 @@ int launch_grad_vh_tiled(const float* gO, const float* in, const float* v, const
 
 extern "C" {
 
-int tai_sepconv_version(void) { return 600; }     // 0.6.0: clip pipeline entry points (tai_clip_from_frames, tai_frames_to_uint8), no other kernel changed; (0.5.0: F(4x4, 3x3) chunk loop as generated assembly, displaced-read blocks, any C; (0.4.1: persistent forward kernel beyond the Infinity Cache: type-A waves at their partners' priority (0.4.0: nt tap loads + reversed walk; source hash)))
+int tai_sepconv_version(void) { return 600; }     // 0.6.0: (tai_state_digest added at the same number: an entry point of its own, and the committed counter summaries are tied to it); clip pipeline entry points (tai_clip_from_frames, tai_frames_to_uint8), no other kernel changed; (0.5.0: F(4x4, 3x3) chunk loop as generated assembly, displaced-read blocks, any C; (0.4.1: persistent forward kernel beyond the Infinity Cache: type-A waves at their partners' priority (0.4.0: nt tap loads + reversed walk; source hash)))
 
 const char* tai_sepconv_last_error(void) { return g_err; }
 
@@ -1669,6 +1670,45 @@ int tai_frames_to_uint8(const float* x, unsigned char* out, int N, int C, int Hs
     if (C == 1) hipLaunchKernelGGL((clip::to_uint8<1>), grid, block, 0, s, x, out, Hs, Ws, h, w, reverse_channels != 0, total);
     else        hipLaunchKernelGGL((clip::to_uint8<3>), grid, block, 0, s, x, out, Hs, Ws, h, w, reverse_channels != 0, total);
     return check_launch("frames_to_uint8");
+}
+
+long long tai_state_digest_workspace_bytes(int n_entries, long long n_segments) {
+    if (n_entries <= 0 || n_segments < 0) return TAI_SEPCONV_EINVAL;
+    return 8LL * (n_segments + n_entries + 1);
+}
+
+int tai_state_digest(const long long* table, const long long* table_host, int n_entries, long long n_segments, long long seg_words,
+                     void* workspace, unsigned long long* result, void* hip_stream) {
+    g_err[0] = 0;
+    if (!table || !table_host || !workspace || !result) return fail(TAI_SEPCONV_EINVAL, "%s", "state_digest: null pointer");
+    if (n_entries <= 0 || seg_words <= 0 || seg_words % 4 != 0 || seg_words > (1LL << 30))
+        return fail(TAI_SEPCONV_EINVAL, "%s", "state_digest: needs n_entries > 0 and 0 < seg_words <= 2^30, a multiple of 4");
+    long long next = 0;
+    for (int t = 0; t < n_entries; ++t) {
+        const long long addr = table_host[4 * t], n = table_host[4 * t + 1], first = table_host[4 * t + 3];
+        if (n < 0 || n >= (1LL << 40) || (addr & 3) != 0 || first != next)
+        {
+            std::snprintf(g_err, sizeof(g_err), "state_digest: row %d is not {4-byte aligned address, 0 <= words < 2^40, sum, first segment %lld}", t, next);
+            return TAI_SEPCONV_EINVAL;
+        }
+        if (addr != 0) next += (n + seg_words - 1) / seg_words;
+    }
+    if (next != n_segments) {
+        std::snprintf(g_err, sizeof(g_err), "state_digest: the table has %lld segments, not %lld", next, n_segments);
+        return TAI_SEPCONV_EINVAL;
+    }
+    hipStream_t s = static_cast<hipStream_t>(hip_stream);
+    unsigned long long* slot = static_cast<unsigned long long*>(workspace);
+    if (n_segments > 0) {
+        // a multiple of the 256 CUs, eight workgroups of four waves each at the most; fewer when there is less to do
+        const long long want = (n_segments + 255) / 256 * 256;
+        const int blocks = (int)(want < 2048 ? want : 2048);
+        hipLaunchKernelGGL(sdig::segment_sums, dim3(blocks), dim3(sdig::THREADS), 0, s, table, n_entries, n_segments, seg_words, slot);
+        const int rc = check_launch("state_digest segment_sums");
+        if (rc != 0) return rc;
+    }
+    hipLaunchKernelGGL(sdig::finish, dim3(1), dim3(sdig::THREADS), 0, s, table, n_entries, n_segments, slot, slot + n_segments, result);
+    return check_launch("state_digest finish");
 }
 
 }  // extern "C"

@@ -183,6 +183,66 @@ class _ClipReader(object):
         return torch.from_numpy(np.stack(frames))
 
 
+def position_key(tag, seed, rank, epoch, j):
+    """One integer per (seed, rank, epoch, position): the seed of that position's private generator (tag 1) and of an epoch's
+    permutation (tag 2).  The fields do not overlap, so two positions never share a stream."""
+    return (int(tag) << 128) | ((int(seed) & 0xffffffff) << 96) | ((int(rank) & 0xffffffff) << 64) | ((int(epoch) & 0xffffffff) << 32) \
+        | (int(j) & 0xffffffff)
+
+
+class ResumableBatchSampler(data.Sampler):
+    """A batch sampler whose order can be entered at any position (``train.py --resumable``).
+
+    Epoch e visits the items in a permutation derived from (seed, rank, e) alone (the identity with ``serial``), in batches of
+    ``batch_size`` (a ragged last batch is dropped, as train.py's loader does).  An item of a batch is ``(index, e, j)`` -- the line of the
+    video list, the epoch and the position j inside the epoch -- and a dataset given such an item draws window, mirror, reversal and any
+    replacement line from a generator seeded by (seed, rank, e, j): what a position yields depends on nothing that was read before it,
+    on no worker count and on no worker.
+
+    The position is (epoch, batches consumed) and moves only in ``took_batch``, which the consumer calls per batch it takes: what the
+    loader's workers have prefetched beyond that is produced again after a resume.  Iterating yields the rest of the current epoch from
+    the position at that moment, without touching the items it skips."""
+
+    def __init__(self, n_items, batch_size, seed, rank=0, serial=False):
+        self.n_items, self.batch_size, self.seed, self.rank, self.serial = int(n_items), int(batch_size), int(seed), int(rank), bool(serial)
+        self.batches_per_epoch = self.n_items // self.batch_size
+        if self.batches_per_epoch < 1:
+            raise ValueError('ResumableBatchSampler: %d items do not fill one batch of %d' % (self.n_items, self.batch_size))
+        self.epoch, self.consumed = 0, 0
+
+    def permutation(self, epoch):
+        order = list(range(self.n_items))
+        if not self.serial:
+            random.Random(position_key(2, self.seed, self.rank, epoch, 0)).shuffle(order)
+        return order
+
+    def __iter__(self):
+        epoch, first = self.epoch, self.consumed
+        order = self.permutation(epoch)
+        for b in range(first, self.batches_per_epoch):
+            yield [(order[j], epoch, j) for j in range(b * self.batch_size, (b + 1) * self.batch_size)]
+
+    def __len__(self):
+        return self.batches_per_epoch - self.consumed
+
+    def took_batch(self):
+        self.consumed += 1
+        if self.consumed >= self.batches_per_epoch:
+            self.epoch, self.consumed = self.epoch + 1, 0
+
+    def state(self):
+        return {'kind': 'sampler', 'seed': self.seed, 'rank': self.rank, 'serial': int(self.serial), 'n_items': self.n_items,
+                'batch_size': self.batch_size, 'epoch': self.epoch, 'consumed': self.consumed}
+
+    def load_state(self, state):
+        mine = self.state()
+        for k in ('kind', 'seed', 'rank', 'serial', 'n_items', 'batch_size'):
+            if state.get(k) != mine[k]:
+                raise ValueError('the saved clip order has %s = %r, this run has %r: it cannot be continued exactly'
+                                 % (k, state.get(k), mine[k]))
+        self.epoch, self.consumed = int(state['epoch']), int(state['consumed'])
+
+
 class ContiguousVideoClipDataset(data.Dataset):
     """base_dataset.py:17-202: one line per video, ``<path>`` or ``<path> <a>-<b>``; an item is a random window of
     ``seq_length`` consecutive frames of that range, optionally mirrored / reversed; a video that cannot be opened, is too
@@ -195,10 +255,14 @@ class ContiguousVideoClipDataset(data.Dataset):
 
     ``raw=True`` (the device clip pipeline, clip_pipeline.py): an item is ``{'frames': uint8 [T, h, w, 3] RGB as decoded, in
     playback order, 'mirror': bool, 'clip_label': str}`` -- the same draws in the same order pick the same window, mirror and
-    reversal; the resize, flip, padding, range map and gray conversion are left to the GPU."""
+    reversal; the resize, flip, padding, range map and gray conversion are left to the GPU.
+
+    Indexed with an item of ``ResumableBatchSampler``, ``(index, epoch, j)``, every draw for that item comes from a generator of its own,
+    seeded by (``seed``, ``rank``, epoch, j) -- the dataset's generator is left alone -- and the item carries ``'window'``, an int64
+    [start frame, mirror, reverse], for whoever wants to compare orders."""
 
     def __init__(self, c_dim, video_list_path, seq_length, backwards, flip, image_size, resample_on_fail, padding_size,
-                 seed=0, raw=False):
+                 seed=0, raw=False, rank=0):
         super().__init__()
         with open(video_list_path, 'r') as f:
             self.files = [line.strip() for line in f.readlines()]
@@ -206,6 +270,7 @@ class ContiguousVideoClipDataset(data.Dataset):
         self.backwards, self.flip, self.resample_on_fail = backwards, flip, resample_on_fail
         self.reader = _ClipReader(c_dim, image_size, padding_size)
         self._seed = int(seed)
+        self._rank = int(rank)
         self.raw = bool(raw)
         self.rng = random.Random(self._seed)
 
@@ -222,33 +287,42 @@ class ContiguousVideoClipDataset(data.Dataset):
     def open_video(self, vid_path):
         return open_frame_source(vid_path)
 
-    def _try(self, record):
-        """-> (item, None) or (None, reason)."""
+    def _try(self, record, rng=None):
+        """-> (item, None) or (None, reason); the draws come from ``rng`` (default: the dataset's generator)."""
+        positional, rng = rng is not None, rng or self.rng
         source = self.open_video(record.path)
         if source is None:
             return None, 'Video at %s could not be opened' % record.path
         first, last = record.spans[0] if record.spans else (0, source.get_length() - 1)
         if last - first + 1 < self.seq_len:
             return None, 'Interval %s in video %s is too short' % (str((first, last)), record.path)
-        start = self.rng.randint(first, last - self.seq_len + 1)
-        mirror = self.flip and self.rng.random() > 0.5
-        reverse = self.backwards and self.rng.random() > 0.5
+        start = rng.randint(first, last - self.seq_len + 1)
+        mirror = self.flip and rng.random() > 0.5
+        reverse = self.backwards and rng.random() > 0.5
         if self.raw:
             frames = self.reader.raw_clip(source, range(start, start + self.seq_len), reverse)
             if frames is None:
                 return None, 'Failed to sample frames starting at %d in %s' % (start, record.path)
-            return {'frames': frames, 'mirror': bool(mirror), 'clip_label': record.label([(first, last)])}, None
-        clip = self.reader.clip(source, range(start, start + self.seq_len), mirror, reverse)
-        if clip is None:
-            return None, 'Failed to sample frames starting at %d in %s' % (start, record.path)
-        return {'targets': clip, 'clip_label': record.label([(first, last)])}, None
+            item = {'frames': frames, 'mirror': bool(mirror), 'clip_label': record.label([(first, last)])}
+        else:
+            clip = self.reader.clip(source, range(start, start + self.seq_len), mirror, reverse)
+            if clip is None:
+                return None, 'Failed to sample frames starting at %d in %s' % (start, record.path)
+            item = {'targets': clip, 'clip_label': record.label([(first, last)])}
+        if positional:
+            item['window'] = torch.tensor([start, int(bool(mirror)), int(bool(reverse))], dtype=torch.int64)
+        return item, None
 
     def __getitem__(self, index):
-        item, reason = self._try(ClipRecord(self.files[index]))
+        rng = None
+        if isinstance(index, (tuple, list)):                       # an item of ResumableBatchSampler: a generator of its own
+            index, epoch, j = index
+            rng = random.Random(position_key(1, self._seed, self._rank, epoch, j))
+        item, reason = self._try(ClipRecord(self.files[index]), rng)
         while item is None:
             if not self.resample_on_fail:
                 raise RuntimeError(reason)
-            item, reason = self._try(ClipRecord(self.files[self.rng.randrange(len(self.files))]))
+            item, reason = self._try(ClipRecord(self.files[(rng or self.rng).randrange(len(self.files))]), rng)
         return item
 
 

@@ -20,7 +20,7 @@ import os
 import numpy as np
 import torch
 
-from . import conv_ops, parallel
+from . import conv_ops, parallel, run_state
 from .graph import GraphedForward
 from .losses import GDL
 from .mcnet import MCNetFillInModel
@@ -42,7 +42,8 @@ def create_eval_environment(fill_in_model, checkpoints_dir, name, snapshot_file_
 
 
 def create_training_environment(fill_in_model, c_dim, checkpoints_dir, name, max_K, max_T, max_F, image_size, alpha,
-                                beta, lr, beta1, df_dim, Ip, disc_window_size, padding_size, device=None, graph_step=False):
+                                beta, lr, beta1, df_dim, Ip, disc_window_size, padding_size, device=None, graph_step=False,
+                                resumable=False):
     if isinstance(fill_in_model, (TAIFillInModel, TimeWeightedInterpolationFillInModel,
                                   BidirectionalSimpleAverageFillInModel, BidirectionalTimeWeightedAverageFillInModel)):
         env = TAITrainingEnvironment(      # environments.py:29-31
@@ -56,11 +57,62 @@ def create_training_environment(fill_in_model, c_dim, checkpoints_dir, name, max
     else:
         raise RuntimeError('Tried to create a training environment for object of unsupported type %s'
                            % type(fill_in_model).__name__)
-    if os.path.isfile(os.path.join(checkpoints_dir, name, 'model_latest.ckpt')):
+    env.resumable = bool(resumable)
+    remove_stale_temporaries(env.save_dir)
+    names = [n for n in (LATEST, PREVIOUS if env.resumable else None) if n and os.path.isfile(os.path.join(env.save_dir, n))]
+    for i, file_name in enumerate(names):
         print('Loading latest snapshot...')
-        env.load('model_latest.ckpt')
+        try:
+            env.load(file_name)
+            break
+        except Exception as e:
+            # a truncated file (a process killed inside a save before saves were atomic, a full disk) or a state that does not
+            # hash to the digest it was saved with: the snapshot before it is the one to continue from
+            if not env.resumable or i + 1 == len(names):
+                raise
+            print('%s cannot be used (%s: %s): falling back to %s' % (file_name, type(e).__name__, e, names[i + 1]))
     print('Loaded training environment')
     return env
+
+
+LATEST, PREVIOUS = 'model_latest.ckpt', 'model_latest.prev.ckpt'
+_TMP_MARK = '.tmp.'
+
+
+def remove_stale_temporaries(save_dir):
+    """Temporary files a killed ``save`` left behind (``<snapshot>.tmp.<pid>``)."""
+    if parallel.rank() != 0 or not os.path.isdir(save_dir):
+        return
+    for f in os.listdir(save_dir):
+        if '.ckpt' + _TMP_MARK in f:
+            try:
+                os.remove(os.path.join(save_dir, f))
+            except OSError:
+                pass
+
+
+def atomic_save(obj, path, keep_previous_as=None):
+    """``torch.save`` that never leaves a partial file under ``path``: written beside it, flushed to the disk, renamed over it.  A reader
+    (the next start) finds the old snapshot or the new one.  ``keep_previous_as``: the file that was at ``path`` moves there first."""
+    tmp = '%s%s%d' % (path, _TMP_MARK, os.getpid())
+    try:
+        with open(tmp, 'wb') as f:
+            torch.save(obj, f)
+            f.flush()
+            os.fsync(f.fileno())
+        if keep_previous_as is not None and os.path.isfile(path):
+            os.replace(path, keep_previous_as)
+        os.replace(tmp, path)
+    except Exception:
+        try:
+            os.remove(tmp)
+        except OSError:
+            pass
+        raise
+
+
+class SnapshotRefused(RuntimeError):
+    """A snapshot whose state does not hash to the digest it was saved with."""
 
 
 class _parameters_frozen(object):
@@ -145,6 +197,11 @@ class BaseTrainingEnvironment(BaseVideoFillInEnvironment):
         # counter on the device (``capturable``).  Off by default: the eager sequence is the reference's.
         self.graph_step = bool(graph_step)
         self._step_graphs = {}
+        # resumable (train.py --resumable): snapshots carry ``run_state`` (run_state.py) and ``load`` restores it; off = the reference's keys
+        self.resumable = False
+        self.data_state_source = None      # train.py: a callable -> the clip order's position, saved with the snapshot
+        self.restored_data_state = None    # ... and what ``load`` found for this rank, for train.py to position its clip order with
+        self.exact_resume = False          # the last ``load`` restored a run_state
         self.start_update = 0
         self.total_updates = 0
         self.start_sum_avg_psnr_err = 0
@@ -251,29 +308,60 @@ class BaseTrainingEnvironment(BaseVideoFillInEnvironment):
         """Host-side work a captured update may not do (host-to-device copies): done here, once."""
 
     def get_current_state_dict(self, total_updates, sum_avg_psnr_err, sum_avg_ssim_err):
-        return {
+        state = {
             'updates': total_updates,
             'sum_avg_psnr_err': sum_avg_psnr_err,
             'sum_avg_ssim_err': sum_avg_ssim_err,
             'generator': self.generator.state_dict(),
             'optimizer_G': self.optimizer_G.state_dict(),
         }
+        if self.resumable:
+            # the one key beyond the reference's; a collective in a data-parallel run (every rank's generator states go to rank 0)
+            state['run_state'] = run_state.capture(self)
+        return state
 
     def load(self, snapshot_file_name):
         snapshot = super().load(snapshot_file_name)
         self.start_update = snapshot['updates']
         self.start_sum_avg_psnr_err = snapshot['sum_avg_psnr_err']
         self.start_sum_avg_ssim_err = snapshot['sum_avg_ssim_err']
-        self.optimizer_G.load_state_dict(snapshot['optimizer_G'])
         self._step_graphs.clear()
+        self._load_training_state(snapshot)
+        self._restore_run_state(snapshot, snapshot_file_name)       # last: the generator states are set behind everything that could draw
         return snapshot
 
+    def _load_training_state(self, snapshot):
+        self.optimizer_G.load_state_dict(snapshot['optimizer_G'])
+
+    def _restore_run_state(self, snapshot, snapshot_file_name):
+        self.exact_resume, self.restored_data_state = False, None
+        if not self.resumable:
+            return
+        state = snapshot.get('run_state')
+        if state is None:
+            print('%s carries no run_state: the run continues from its weights and optimizer state, but NOT exactly (spectral-norm '
+                  'vectors, generator states and the clip order start afresh)' % snapshot_file_name)
+            return
+        try:
+            data_state = run_state.restore(self, state)
+        except run_state.RunStateRefused as e:
+            print('%s: %s: the run continues from its weights and optimizer state, but NOT exactly' % (snapshot_file_name, e))
+            return
+        want = state['ranks'][parallel.rank()]['digest']
+        have = run_state.digest(self, data_state)
+        if have != want:
+            raise SnapshotRefused('state digest %016x after loading, %016x when it was saved' % (have, want))
+        self.exact_resume, self.restored_data_state = True, data_state
+
     def save(self, snapshot_file_name, total_updates, sum_avg_psnr_err, sum_avg_ssim_err):
+        if parallel.rank() != 0 and not (self.resumable and parallel.world_size() > 1):
+            return
+        state = self.get_current_state_dict(total_updates, sum_avg_psnr_err, sum_avg_ssim_err)
         if parallel.rank() != 0:
             return
         os.makedirs(self.save_dir, exist_ok=True)
-        torch.save(self.get_current_state_dict(total_updates, sum_avg_psnr_err, sum_avg_ssim_err),
-                   os.path.join(self.save_dir, snapshot_file_name))
+        keep = os.path.join(self.save_dir, PREVIOUS) if self.resumable and snapshot_file_name == LATEST else None
+        atomic_save(state, os.path.join(self.save_dir, snapshot_file_name), keep_previous_as=keep)
 
     def _zero_grad(self, optimizer, reducer):
         """One process: the reference's ``optimizer.zero_grad()``.  Data parallel: gradients live in the reducer's flat
@@ -333,11 +421,11 @@ class L2GDLDiscTrainingEnvironment(BaseTrainingEnvironment):
         state['optimizer_D'] = self.optimizer_D.state_dict()
         return state
 
-    def load(self, snapshot_file_name):
-        snapshot = super().load(snapshot_file_name)
+    def _load_training_state(self, snapshot):
+        super()._load_training_state(snapshot)
         self.discriminator.load_state_dict(snapshot['discriminator'])
+        conv_ops.invalidate_derived(self.discriminator)
         self.optimizer_D.load_state_dict(snapshot['optimizer_D'])
-        return snapshot
 
     def create_fake_labels(self):
         """1 for windows made of real frames only (both ends), 0 for every window touching a generated frame

@@ -99,6 +99,16 @@ class TrainOptions(BaseOptions):
                        help='Sample the number of preceding, middle, and following frames in each minibatch')
         g.add_argument('--graph_step', action='store_true',
                        help='Capture one whole update as a hipGraph per (K, T, F) and replay it (one process per node only)')
+        g.add_argument('--resumable', action='store_true',
+                       help='(this build) exact resume: snapshots carry run_state (spectral-norm vectors, every generator state, the clip '
+                            "order's position, a state digest computed on the GPU) and a run stopped after any update and continued in a new "
+                            'process ends with the same bits as the uninterrupted one; the clip order becomes a counter-based one (the draws '
+                            'of a position depend on (seed, rank, epoch, position) only, not on --num_threads); SIGTERM, SIGINT and '
+                            '--max_wall_minutes end the run after the update in flight with model_latest.ckpt written; the previous '
+                            'model_latest.ckpt is kept as model_latest.prev.ckpt and a start falls back to it when the latest one does not '
+                            'load or does not match its digest; printed lines end with state=<digest>.  Off = the run as before')
+        g.add_argument('--max_wall_minutes', type=float, default=None, metavar='M',
+                       help='(this build, with --resumable) stop as after SIGTERM once the run has lasted M minutes')
         g.add_argument('--miopen_find_mode', type=str, default=None, choices=['NORMAL', 'FAST', 'HYBRID', 'DYNAMIC_HYBRID'],
                        help='MIOPEN_FIND_MODE for this run (package default FAST: first update 1.4 s instead of 22 s, later updates '
                             '2-3 %% slower; NORMAL pays the search once and is the choice for a long run)')

@@ -37,6 +37,49 @@ from .upsample import upsample2x
 from .util import gray01
 
 
+class _ReplicatePadFixedOrder(torch.autograd.Function):
+    """``F.pad(x, [p] * 4, mode='replicate')`` whose backward sums in a fixed order.  ATen's backward scatters every padded position
+    into its source pixel with float atomics -- a corner pixel of a 51-tap pad collects 26 x 26 of them in arrival order -- and this is
+    where the gradient enters MC-Net, so one update is then not reproducible from identical state in any generator weight.  Here the
+    border is folded back by two reductions (rows, then columns): the values differ from the atomic form's in the last bits only."""
+
+    @staticmethod
+    def forward(ctx, x, p):
+        ctx.p = p
+        return F.pad(x, [p] * 4, mode='replicate')
+
+    @staticmethod
+    def backward(ctx, g):
+        p = ctx.p
+        H, W = g.shape[-2] - 2 * p, g.shape[-1] - 2 * p
+        if H == 1:
+            g = g.sum(-2, keepdim=True)
+        else:
+            g = torch.cat([g[..., :p + 1, :].sum(-2, keepdim=True), g[..., p + 1:p + H - 1, :], g[..., p + H - 1:, :].sum(-2, keepdim=True)], dim=-2)
+        if W == 1:
+            g = g.sum(-1, keepdim=True)
+        else:
+            g = torch.cat([g[..., :p + 1].sum(-1, keepdim=True), g[..., p + 1:p + W - 1], g[..., p + W - 1:].sum(-1, keepdim=True)], dim=-1)
+        return g, None
+
+
+_FIXED_ORDER_PAD = [False]
+
+
+def set_reproducible_backward(on):
+    """Fixed-order backward of the replication padding in front of the separable convolutions (train.py --resumable: a resumed run can
+    only repeat the uninterrupted one if an update is a function of the state).  Off by default: ATen's form.  Returns the previous
+    setting."""
+    previous, _FIXED_ORDER_PAD[0] = _FIXED_ORDER_PAD[0], bool(on)
+    return previous
+
+
+def _replicate_pad(x, p):
+    if _FIXED_ORDER_PAD[0] and x.requires_grad and torch.is_grad_enabled():
+        return _ReplicatePadFixedOrder.apply(x, p)
+    return F.pad(x, [p] * 4, mode='replicate')
+
+
 def _up2(x):
     return upsample2x(x)
 
@@ -144,10 +187,9 @@ class TAI(nn.Module):
                 d = torch.cat([d, rc], dim=1)
             u = self.moduleUpsample[i](d)
             x = u + (enc[nb - 3 - i - 1] if i < nb - 3 else variableRes[nb - i - 1])
-        pad = [self.pad] * 4
-        dot1 = self.separableConvolution(F.pad(variableInput1, pad, mode='replicate'), self.moduleVertical1(x),
+        dot1 = self.separableConvolution(_replicate_pad(variableInput1, self.pad), self.moduleVertical1(x),
                                          self.moduleHorizontal1(x), self.ks)
-        dot2 = self.separableConvolution(F.pad(variableInput2, pad, mode='replicate'), self.moduleVertical2(x),
+        dot2 = self.separableConvolution(_replicate_pad(variableInput2, self.pad), self.moduleVertical2(x),
                                          self.moduleHorizontal2(x), self.ks)
         return dot1, dot2
 
