@@ -459,6 +459,37 @@ long long tai_state_digest_workspace_bytes(int n_entries, long long n_segments);
 int tai_state_digest(const long long* table, const long long* table_host, int n_entries, long long n_segments, long long seg_words,
                      void* workspace, unsigned long long* result, void* hip_stream);
 
+/* Statistics of a table of contiguous fp32 tensors where they live, and x <- x * c over the same table (csrc/grad_stats.hip.inc;
+ * video_frame_inpainting_amd/grad_guard.py builds the table; no counterpart in the reference, which never looks at its gradients).
+ * A float sum depends on its order, so the order is the definition -- the results are a function of the values alone:
+ *   an entry x[0..n_t) is cut into segments of 16384 elements (a constant of the definition); the last one may be short;
+ *   an element that is NaN or +-Inf adds 1 to nonfinite[t] and contributes nothing else; a finite one contributes
+ *     q = (double)x * (double)x (exact in fp64) to the sum and |x| to maxabs[t];
+ *   inside a segment there are 1024 fp64 accumulators a[0..1024), all +0.0 at first; a[j] adds, in increasing i, the q of the elements
+ *     with segment-relative index i = j (mod 1024); then, for d = 1, 2, 4, ..., 512 in this order, a[j] <- a[j] + a[j xor d] for all j
+ *     at once (every a[j] ends with the same value, the segment sum);
+ *   sumsq[t] = the segment sums added one by one in segment order, starting from +0.0;
+ *   sumsq[n_entries] = the sumsq[t] added one by one in table order, starting from +0.0; maxabs[n_entries] and nonfinite[n_entries] are
+ *     the maximum and the sum over the table (exact whatever the order).  An empty entry gives zeros.
+ * table: n_entries rows of four 64-bit integers {address, elements n_t, unused, first segment} on the device, table_host the same rows on
+ * the host: the state digest's row.  An entry is cut into ceil(n_t / 16384) segments numbered consecutively in table order, n_segments in
+ * all; an empty entry has address 0.  table_host is read before the call returns and refused (TAI_SEPCONV_EINVAL, nothing launched) unless
+ * the segment numbers are exactly those, every address is 4-byte aligned and 0 exactly for the empty entries.  The kernels touch
+ * [address, address + 4 n_t) of every entry and nothing else.  blocks: workgroups of the launch over the segments, 0 = the library's
+ * choice; the results do not depend on it, nor on the addresses or their alignment, on repetition, or -- per entry -- on the other entries.
+ * tai_grad_stats: workspace of tai_grad_stats_workspace_bytes(n_entries, n_segments) bytes, 16-byte aligned; sumsq (double), maxabs
+ * (float), nonfinite (int64): n_entries + 1 elements each on the device, the last one the table's.  One launch over the segments (16-byte
+ * loads where the address allows, sixteen in flight per lane, per-segment results to the workspace, no atomics), one workgroup to finish.
+ * tai_grad_scale: x <- x * c in fp32, one rounding per element, c finite and passed by value (the caller launches it when c < 1); it needs
+ * no workspace today (the query returns 0 and the pointer may be null).
+ * Both: no allocation, copy or synchronisation; asynchronous on hip_stream. */
+long long tai_grad_stats_workspace_bytes(int n_entries, long long n_segments);
+int tai_grad_stats(const long long* table, const long long* table_host, int n_entries, long long n_segments, int blocks, void* workspace,
+                   double* sumsq, float* maxabs, long long* nonfinite, void* hip_stream);
+long long tai_grad_scale_workspace_bytes(int n_entries, long long n_segments);
+int tai_grad_scale(const long long* table, const long long* table_host, int n_entries, long long n_segments, float c, int blocks,
+                   void* workspace, void* hip_stream);
+
 /* Text of the last error on the calling thread ("" if none). */
 const char* tai_sepconv_last_error(void);
 

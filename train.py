@@ -14,6 +14,11 @@ spectral-norm vectors, every generator state, the clip order's position, a state
 that can be entered at any position (data.ResumableBatchSampler), SIGTERM / SIGINT / ``--max_wall_minutes`` end the run after the
 update in flight with ``model_latest.ckpt`` written, and every printed line ends with the state digest (``state=%016x``).
 
+``--guard [--clip_grad_norm X] [--guard_patience N]``: the gradients are looked at before each optimizer step (grad_guard.py): an
+optimizer whose gradients hold a NaN or an Inf does not step in that update, gradients are scaled to a norm of at most X, printed lines
+carry ``gnorm_G= gnorm_D= skipped=``, a state with non-finite values is never written over a snapshot, and after N consecutive updates
+with a skipped step the run ends with a non-zero exit, ``model_latest.ckpt`` being the last one written while healthy.
+
   python train.py --name demo --K 5 --T 5 --F 5 --c_dim 1 --image_size 128 --batch_size 4 --model_key TAI_gray \
       --max_iter 10 --synthetic 64
 """
@@ -24,7 +29,7 @@ import numpy as np
 import torch
 
 import video_frame_inpainting_amd as vfi
-from video_frame_inpainting_amd import clip_pipeline, parallel, run_state, synthetic, tai
+from video_frame_inpainting_amd import clip_pipeline, grad_guard, parallel, run_state, synthetic, tai
 from video_frame_inpainting_amd.data import ContiguousVideoClipDataset, ResumableBatchSampler
 from video_frame_inpainting_amd.environments import create_training_environment
 from video_frame_inpainting_amd.options import TrainOptions
@@ -33,6 +38,10 @@ from video_frame_inpainting_amd.validation import Validator
 
 def main(args=None):
     opt = TrainOptions().parse(args, allow_unknown=True)
+    if opt.guard and opt.graph_step:
+        raise SystemExit('--guard refuses --graph_step: a replayed update cannot leave out an optimizer step')
+    if not opt.guard and opt.clip_grad_norm is not None:
+        raise SystemExit('--clip_grad_norm needs --guard')
     if not opt.resumable:
         return _run(opt, None)
     if opt.graph_step and GRAPH_STEP_REFUSAL:
@@ -106,10 +115,11 @@ def _run(opt, stop):
     torch.manual_seed(0)
     np.random.seed(0)          # identical (K, T, F) draws on every rank
     model = vfi.create_model(opt.model_key)
+    guard = grad_guard.GradGuard(opt.clip_grad_norm, opt.guard_patience) if opt.guard else None
     env = create_training_environment(model, opt.c_dim, opt.checkpoints_dir, opt.name, opt.K, opt.T, opt.F,
                                       opt.image_size, opt.alpha, opt.beta, opt.lr, opt.beta1, opt.df_dim, opt.Ip,
                                       opt.disc_window_size, opt.padding_size, device=device,
-                                      graph_step=opt.graph_step, resumable=resumable)
+                                      graph_step=opt.graph_step, resumable=resumable, guard=guard)
     env.sync_replicas()
     total_updates = env.start_update
     # a resumed run starts from the best values its snapshot carries (train.py:96-97)
@@ -146,11 +156,15 @@ def _run(opt, stop):
         env.K, env.T, env.F = K, T, F
         env.train()
         # set_train_inputs -> forward_train -> optimize_parameters; one hipGraph replay per update with --graph_step
-        env.train_step(all_frames[:, :K], all_frames[:, K + T:K + T + F], all_frames[:, K:K + T])
+        try:
+            env.train_step(all_frames[:, :K], all_frames[:, K + T:K + T + F], all_frames[:, K:K + T])
+        except grad_guard.GuardGaveUp as e:
+            # no snapshot on the way out: model_latest.ckpt is the last one written while the run was healthy
+            raise SystemExit('iter %d: the guard gives up: %s' % (total_updates, e))
         if total_updates % opt.print_freq == 0 or total_updates == 1:
             torch.cuda.synchronize()
             errs = env.get_current_errors()
-            state = ' state=%016x' % run_state.digest(env) if resumable else ''
+            state = (guard.log_suffix() if guard is not None else '') + (' state=%016x' % run_state.digest(env) if resumable else '')
             if rank == 0:
                 print('iter %d (K,T,F)=(%d,%d,%d) %.3fs  %s%s' % (total_updates, K, T, F, time.time() - t0,
                                                                   ' '.join('%s=%.5f' % kv for kv in sorted(errs.items())), state))

@@ -289,6 +289,14 @@ def lib():
     L.tai_state_digest_workspace_bytes.restype = ctypes.c_longlong
     L.tai_state_digest.argtypes = [P, P, I, ctypes.c_longlong, ctypes.c_longlong, P, P, V]
     L.tai_state_digest.restype = I
+    L.tai_grad_stats_workspace_bytes.argtypes = [I, ctypes.c_longlong]
+    L.tai_grad_stats_workspace_bytes.restype = ctypes.c_longlong
+    L.tai_grad_stats.argtypes = [P, P, I, ctypes.c_longlong, I, P, P, P, P, V]
+    L.tai_grad_stats.restype = I
+    L.tai_grad_scale_workspace_bytes.argtypes = [I, ctypes.c_longlong]
+    L.tai_grad_scale_workspace_bytes.restype = ctypes.c_longlong
+    L.tai_grad_scale.argtypes = [P, P, I, ctypes.c_longlong, ctypes.c_float, I, P, V]
+    L.tai_grad_scale.restype = I
     L.tai_sepconv_last_error.restype = ctypes.c_char_p
     L.tai_sepconv_source_hash.restype = ctypes.c_char_p
     L.tai_sepconv_version.restype = I

@@ -30,6 +30,7 @@
 #include "frame_metrics.hip.inc"
 #include "clip_pipeline.hip.inc"
 #include "state_digest.hip.inc"
+#include "grad_stats.hip.inc"
 
 namespace {
 
@@ -283,7 +284,7 @@ int launch_grad_vh_tiled(const float* gO, const float* in, const float* v, const
 
 extern "C" {
 
-int tai_sepconv_version(void) { return 600; }     // 0.6.0: (tai_state_digest added at the same number: an entry point of its own, and the committed counter summaries are tied to it); clip pipeline entry points (tai_clip_from_frames, tai_frames_to_uint8), no other kernel changed; (0.5.0: F(4x4, 3x3) chunk loop as generated assembly, displaced-read blocks, any C; (0.4.1: persistent forward kernel beyond the Infinity Cache: type-A waves at their partners' priority (0.4.0: nt tap loads + reversed walk; source hash)))
+int tai_sepconv_version(void) { return 700; }     // 0.7.0: gradient statistics and scaling over a table of tensors (tai_grad_stats, tai_grad_scale), no other kernel changed; (0.6.0: (tai_state_digest added at the same number: an entry point of its own, and the committed counter summaries are tied to it); clip pipeline entry points (tai_clip_from_frames, tai_frames_to_uint8), no other kernel changed; (0.5.0: F(4x4, 3x3) chunk loop as generated assembly, displaced-read blocks, any C; (0.4.1: persistent forward kernel beyond the Infinity Cache: type-A waves at their partners' priority (0.4.0: nt tap loads + reversed walk; source hash))))
 
 const char* tai_sepconv_last_error(void) { return g_err; }
 
@@ -1709,6 +1710,76 @@ int tai_state_digest(const long long* table, const long long* table_host, int n_
     }
     hipLaunchKernelGGL(sdig::finish, dim3(1), dim3(sdig::THREADS), 0, s, table, n_entries, n_segments, slot, slot + n_segments, result);
     return check_launch("state_digest finish");
+}
+
+// The host copy of a table of fp32 tensors (tai_grad_stats, tai_grad_scale), checked before anything is launched.
+static int grad_table_ok(const char* who, const long long* table_host, int n_entries, long long n_segments) {
+    long long next = 0;
+    for (int t = 0; t < n_entries; ++t) {
+        const long long addr = table_host[4 * t], n = table_host[4 * t + 1], first = table_host[4 * t + 3];
+        if (n < 0 || n >= (1LL << 40) || (addr & 3) != 0 || (addr == 0) != (n == 0) || first != next) {
+            std::snprintf(g_err, sizeof(g_err), "%s: row %d is not {4-byte aligned address (0 exactly when empty), 0 <= elements < 2^40, unused, first segment %lld}", who, t, next);
+            return TAI_SEPCONV_EINVAL;
+        }
+        next += (n + gstat::SEG - 1) / gstat::SEG;
+    }
+    if (next != n_segments) {
+        std::snprintf(g_err, sizeof(g_err), "%s: the table has %lld segments, not %lld", who, next, n_segments);
+        return TAI_SEPCONV_EINVAL;
+    }
+    return TAI_SEPCONV_OK;
+}
+
+// a multiple of the 256 CUs, eight workgroups of four waves each at the most; fewer when there is less to do
+static int grad_blocks(long long n_segments, int blocks) {
+    if (blocks > 0) return blocks;
+    const long long want = (n_segments + 255) / 256 * 256;
+    return (int)(want < 2048 ? want : 2048);
+}
+
+long long tai_grad_stats_workspace_bytes(int n_entries, long long n_segments) {
+    if (n_entries <= 0 || n_segments < 0) return TAI_SEPCONV_EINVAL;
+    return (long long)sizeof(gstat::SegOut) * (n_segments + 1);
+}
+
+int tai_grad_stats(const long long* table, const long long* table_host, int n_entries, long long n_segments, int blocks, void* workspace,
+                   double* sumsq, float* maxabs, long long* nonfinite, void* hip_stream) {
+    g_err[0] = 0;
+    if (!table || !table_host || !workspace || !sumsq || !maxabs || !nonfinite) return fail(TAI_SEPCONV_EINVAL, "%s", "grad_stats: null pointer");
+    if (n_entries <= 0 || blocks < 0 || blocks > 65536) return fail(TAI_SEPCONV_EINVAL, "%s", "grad_stats: needs n_entries > 0 and 0 <= blocks <= 65536");
+    if (((uintptr_t)workspace & 15) != 0 || ((uintptr_t)sumsq & 7) != 0 || ((uintptr_t)maxabs & 3) != 0 || ((uintptr_t)nonfinite & 7) != 0)
+        return fail(TAI_SEPCONV_EINVAL, "%s", "grad_stats: workspace must be 16-byte aligned, the result arrays aligned to their elements");
+    const int ok = grad_table_ok("grad_stats", table_host, n_entries, n_segments);
+    if (ok != TAI_SEPCONV_OK) return ok;
+    hipStream_t s = static_cast<hipStream_t>(hip_stream);
+    gstat::SegOut* slot = static_cast<gstat::SegOut*>(workspace);
+    if (n_segments > 0) {
+        hipLaunchKernelGGL(gstat::segment_stats, dim3(grad_blocks(n_segments, blocks)), dim3(gstat::THREADS), 0, s, table, n_entries, n_segments, slot);
+        const int rc = check_launch("grad_stats segment_stats");
+        if (rc != 0) return rc;
+    }
+    hipLaunchKernelGGL(gstat::finish, dim3(1), dim3(gstat::THREADS), 0, s, table, n_entries, n_segments, slot, sumsq, maxabs, nonfinite);
+    return check_launch("grad_stats finish");
+}
+
+long long tai_grad_scale_workspace_bytes(int n_entries, long long n_segments) {
+    if (n_entries <= 0 || n_segments < 0) return TAI_SEPCONV_EINVAL;
+    return 0;
+}
+
+int tai_grad_scale(const long long* table, const long long* table_host, int n_entries, long long n_segments, float c, int blocks,
+                   void* workspace, void* hip_stream) {
+    g_err[0] = 0;
+    (void)workspace;
+    if (!table || !table_host) return fail(TAI_SEPCONV_EINVAL, "%s", "grad_scale: null pointer");
+    if (n_entries <= 0 || blocks < 0 || blocks > 65536) return fail(TAI_SEPCONV_EINVAL, "%s", "grad_scale: needs n_entries > 0 and 0 <= blocks <= 65536");
+    if (!(c == c) || c - c != 0.0f) return fail(TAI_SEPCONV_EINVAL, "%s", "grad_scale: the factor must be finite");
+    const int ok = grad_table_ok("grad_scale", table_host, n_entries, n_segments);
+    if (ok != TAI_SEPCONV_OK) return ok;
+    if (n_segments == 0) return TAI_SEPCONV_OK;
+    hipLaunchKernelGGL(gstat::scale_segments, dim3(grad_blocks(n_segments, blocks)), dim3(gstat::THREADS), 0, static_cast<hipStream_t>(hip_stream),
+                       table, n_entries, n_segments, c);
+    return check_launch("grad_scale");
 }
 
 }  // extern "C"

@@ -43,7 +43,9 @@ def create_eval_environment(fill_in_model, checkpoints_dir, name, snapshot_file_
 
 def create_training_environment(fill_in_model, c_dim, checkpoints_dir, name, max_K, max_T, max_F, image_size, alpha,
                                 beta, lr, beta1, df_dim, Ip, disc_window_size, padding_size, device=None, graph_step=False,
-                                resumable=False):
+                                resumable=False, guard=None):
+    if guard is not None and graph_step:
+        raise ValueError('a guarded update cannot be a captured one: a replayed update cannot leave out an optimizer step')
     if isinstance(fill_in_model, (TAIFillInModel, TimeWeightedInterpolationFillInModel,
                                   BidirectionalSimpleAverageFillInModel, BidirectionalTimeWeightedAverageFillInModel)):
         env = TAITrainingEnvironment(      # environments.py:29-31
@@ -58,6 +60,7 @@ def create_training_environment(fill_in_model, c_dim, checkpoints_dir, name, max
         raise RuntimeError('Tried to create a training environment for object of unsupported type %s'
                            % type(fill_in_model).__name__)
     env.resumable = bool(resumable)
+    env.guard = guard
     remove_stale_temporaries(env.save_dir)
     names = [n for n in (LATEST, PREVIOUS if env.resumable else None) if n and os.path.isfile(os.path.join(env.save_dir, n))]
     for i, file_name in enumerate(names):
@@ -112,7 +115,8 @@ def atomic_save(obj, path, keep_previous_as=None):
 
 
 class SnapshotRefused(RuntimeError):
-    """A snapshot whose state does not hash to the digest it was saved with."""
+    """A snapshot whose state does not hash to the digest it was saved with (``load``), or a state that holds a NaN or an Inf and is
+    not written over a healthy snapshot (``save`` with a guard)."""
 
 
 class _parameters_frozen(object):
@@ -202,6 +206,9 @@ class BaseTrainingEnvironment(BaseVideoFillInEnvironment):
         self.data_state_source = None      # train.py: a callable -> the clip order's position, saved with the snapshot
         self.restored_data_state = None    # ... and what ``load`` found for this rank, for train.py to position its clip order with
         self.exact_resume = False          # the last ``load`` restored a run_state
+        # guard (train.py --guard): a grad_guard.GradGuard that looks at the gradients between each backward pass and its optimizer step
+        # and leaves the step out when they hold a NaN or an Inf; None = the reference's update, nothing looked at
+        self.guard = None
         self.start_update = 0
         self.total_updates = 0
         self.start_sum_avg_psnr_err = 0
@@ -348,7 +355,7 @@ class BaseTrainingEnvironment(BaseVideoFillInEnvironment):
             print('%s: %s: the run continues from its weights and optimizer state, but NOT exactly' % (snapshot_file_name, e))
             return
         want = state['ranks'][parallel.rank()]['digest']
-        have = run_state.digest(self, data_state)
+        have = run_state.digest(self, data_state, guard_counters=state.get('guard'))      # the table of the run that wrote it
         if have != want:
             raise SnapshotRefused('state digest %016x after loading, %016x when it was saved' % (have, want))
         self.exact_resume, self.restored_data_state = True, data_state
@@ -356,12 +363,41 @@ class BaseTrainingEnvironment(BaseVideoFillInEnvironment):
     def save(self, snapshot_file_name, total_updates, sum_avg_psnr_err, sum_avg_ssim_err):
         if parallel.rank() != 0 and not (self.resumable and parallel.world_size() > 1):
             return
+        if self.guard is not None:
+            self._refuse_non_finite_state(snapshot_file_name)
         state = self.get_current_state_dict(total_updates, sum_avg_psnr_err, sum_avg_ssim_err)
         if parallel.rank() != 0:
             return
         os.makedirs(self.save_dir, exist_ok=True)
         keep = os.path.join(self.save_dir, PREVIOUS) if self.resumable and snapshot_file_name == LATEST else None
         atomic_save(state, os.path.join(self.save_dir, snapshot_file_name), keep_previous_as=keep)
+
+    def _guarded_state(self):
+        """(name, tensor) of the float state a snapshot holds: weights, Adam moments, spectral-norm vectors."""
+        named = [('generator.' + k, v) for k, v in self.generator.state_dict().items()]
+        optimizers = [('optimizer_G', self.optimizer_G)]
+        disc = getattr(self, 'discriminator', None)
+        if disc is not None:
+            named += [('discriminator.' + k, v) for k, v in disc.state_dict().items()]
+            optimizers.append(('optimizer_D', self.optimizer_D))
+        for tag, optimizer in optimizers:
+            for i, p in enumerate(p for group in optimizer.param_groups for p in group['params']):
+                named += [('%s.%d.%s' % (tag, i, k), optimizer.state[p][k]) for k in ('exp_avg', 'exp_avg_sq') if p in optimizer.state]
+        named += [('u.' + k, u) for k, u in run_state.sn_vectors(disc).items() if u is not None]
+        return named
+
+    def _refuse_non_finite_state(self, snapshot_file_name):
+        from . import grad_guard
+        found = grad_guard.first_nonfinite(self._guarded_state())
+        every_rank = self.resumable and parallel.world_size() > 1        # ... is here (``save`` is a collective then): one answer
+        if (self.guard.agree(int(found is not None)) if every_rank else found is not None):
+            raise SnapshotRefused('%s is not written: the state holds non-finite values (%s)' % (
+                snapshot_file_name, '%d in %s' % (found[1], found[0]) if found else 'on another rank'))
+
+    def _step(self, which, module, optimizer):
+        """``optimizer.step()``; with a guard, only when the gradients it is about to use are finite (clipped first, if asked)."""
+        if self.guard is None or self.guard.check(which, module.named_parameters()):
+            optimizer.step()
 
     def _zero_grad(self, optimizer, reducer):
         """One process: the reference's ``optimizer.zero_grad()``.  Data parallel: gradients live in the reducer's flat
@@ -376,7 +412,9 @@ class BaseTrainingEnvironment(BaseVideoFillInEnvironment):
         self.compute_loss_G()
         self.loss_G.backward()
         self._reducer_G.allreduce_()
-        self.optimizer_G.step()
+        self._step('G', self.generator, self.optimizer_G)
+        if self.guard is not None and not hasattr(self, 'optimizer_D'):
+            self.guard.end_update()
 
     def compute_loss_G(self):
         self.loss_G = torch.zeros(1, device=self.device)
@@ -464,7 +502,9 @@ class L2GDLDiscTrainingEnvironment(BaseTrainingEnvironment):
         self.compute_loss_D()
         self.loss_D.backward()
         self._reducer_D.allreduce_()
-        self.optimizer_D.step()
+        self._step('D', self.discriminator, self.optimizer_D)
+        if self.guard is not None:
+            self.guard.end_update()
 
     @staticmethod
     def _time_major_01(x):

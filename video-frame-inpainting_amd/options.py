@@ -107,6 +107,18 @@ class TrainOptions(BaseOptions):
                             '--max_wall_minutes end the run after the update in flight with model_latest.ckpt written; the previous '
                             'model_latest.ckpt is kept as model_latest.prev.ckpt and a start falls back to it when the latest one does not '
                             'load or does not match its digest; printed lines end with state=<digest>.  Off = the run as before')
+        g.add_argument('--guard', action='store_true',
+                       help='(this build) look at the gradients between each backward pass and its optimizer step (grad_guard.py, one HIP '
+                            'launch per optimizer: tai_grad_stats): an optimizer whose gradients hold a NaN or an Inf does not step in that '
+                            'update (weights, Adam moments and step counter stay as they were), a snapshot whose state holds one is not '
+                            'written, and printed lines gain gnorm_G= gnorm_D= skipped=.  Refuses --graph_step.  Off = the update as before')
+        g.add_argument('--clip_grad_norm', type=float, default=None, metavar='X',
+                       help="(this build, with --guard) scale the generator's and the discriminator's gradients, each as a whole, to an "
+                            'L2 norm of at most X before the step (the norm is a fixed-order float64 sum, so a clipped --resumable run '
+                            'stays bit-exact)')
+        g.add_argument('--guard_patience', type=int, default=8, metavar='N',
+                       help='(this build, with --guard) end the run with an error, writing no snapshot, after N consecutive updates in '
+                            'which a step was skipped')
         g.add_argument('--max_wall_minutes', type=float, default=None, metavar='M',
                        help='(this build, with --resumable) stop as after SIGTERM once the run has lasted M minutes')
         g.add_argument('--miopen_find_mode', type=str, default=None, choices=['NORMAL', 'FAST', 'HYBRID', 'DYNAMIC_HYBRID'],

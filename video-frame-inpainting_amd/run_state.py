@@ -11,6 +11,9 @@ state digest that says whether two states are.
   ranks        a list indexed by rank, gathered to rank 0: {'data': the clip order's position (train.py), 'numpy', 'torch_cpu',
                'torch_cuda': the global generators, 'digest': that rank's state digest}
   digest       rank 0's state digest
+  guard        (only with train.py --guard) the guard's counters {'skipped_G', 'skipped_D', 'consecutive'} (grad_guard.GradGuard); they
+               are the last entry of the digest's table then, and only then: a snapshot written without the guard loads with it (the
+               counters start at zero) and the other way round, and digests of runs without the guard are what they were
 ``restore(env, run_state)`` puts all of it back, the generator states LAST, and returns this rank's 'data' entry.
 
 The digest (``tai_state_digest``, csrc/state_digest.hip.inc) reads every tensor of the state once, where it lives: about 0.5 GB of
@@ -170,6 +173,9 @@ def _rng_entry(state):
                                        np.array([cached], dtype='<f8').view(np.uint8)]))
 
 
+_CURRENT = object()
+
+
 def sn_vectors(discriminator):
     """{module name: u or None} of the spectrally normalised layers, in module order."""
     if discriminator is None:
@@ -189,10 +195,18 @@ def _optimizer_entries(optimizer):
     return out
 
 
-def state_entries(env, data_state=None):
+def _guard_counters(env):
+    guard = getattr(env, 'guard', None)
+    return None if guard is None else guard.counters()
+
+
+def state_entries(env, data_state=None, guard_counters=_CURRENT):
     """The digest's table for a training environment, in its fixed order: generator, discriminator (state-dict order), the two
     optimizers (per parameter: step, exp_avg, exp_avg_sq), the ``u`` vectors (None: an empty entry), then the generators -- the
-    (K, T, F) stream, numpy's, torch's CPU and device generators -- and the clip order's position."""
+    (K, T, F) stream, numpy's, torch's CPU and device generators -- and the clip order's position; with a guard (``env.guard``, or the
+    counters of a snapshot written with one) its three counters are one more entry behind them."""
+    if guard_counters is _CURRENT:
+        guard_counters = _guard_counters(env)
     entries = [t.detach() for t in env.generator.state_dict().values()]
     disc = getattr(env, 'discriminator', None)
     if disc is not None:
@@ -208,6 +222,8 @@ def state_entries(env, data_state=None):
     if env.device.type == 'cuda':
         entries.append(bytes_entry(torch.cuda.get_rng_state(env.device).numpy()))
     entries.append(bytes_entry(np.frombuffer(repr(data_state).encode(), dtype=np.uint8)))
+    if guard_counters is not None:
+        entries.append(np.array([guard_counters[k] for k in ('skipped_G', 'skipped_D', 'consecutive')], dtype='<i8').view(np.uint32))
     return [e.contiguous() if torch.is_tensor(e) else e for e in entries]
 
 
@@ -238,13 +254,12 @@ def _printable(state):
     return state
 
 
-_CURRENT = object()
-
-
-def digest(env, data_state=_CURRENT):
+def digest(env, data_state=_CURRENT, guard_counters=_CURRENT):
     """The 64-bit state digest of a training environment and of the clip order's position: the one train.py has attached
-    (``env.data_state_source``), or ``data_state`` (a snapshot's, before train.py has positioned its clip order with it)."""
-    return digest_tensors(state_entries(env, _printable(_data_state(env) if data_state is _CURRENT else data_state)))
+    (``env.data_state_source``), or ``data_state`` (a snapshot's, before train.py has positioned its clip order with it).
+    ``guard_counters``: the guard entry of the table -- the environment's own guard by default, a snapshot's ``run_state.get('guard')``
+    when the digest that snapshot was saved with is recomputed."""
+    return digest_tensors(state_entries(env, _printable(_data_state(env) if data_state is _CURRENT else data_state), guard_counters))
 
 
 def _gather(entry):
@@ -265,12 +280,15 @@ def capture(env):
             'torch_cuda': torch.cuda.get_rng_state(env.device).clone() if env.device.type == 'cuda' else None,
             'digest': digest(env)}
     ranks = _gather(mine)
-    return {'version': FORMAT_VERSION,
-            'world_size': parallel.world_size(),
-            'u': {name: (None if u is None else u.detach().clone()) for name, u in sn_vectors(getattr(env, 'discriminator', None)).items()},
-            'ktf': _rng_state_tuple(env._ktf_rng.get_state()),
-            'ranks': ranks,
-            'digest': ranks[0]['digest']}
+    state = {'version': FORMAT_VERSION,
+             'world_size': parallel.world_size(),
+             'u': {name: (None if u is None else u.detach().clone()) for name, u in sn_vectors(getattr(env, 'discriminator', None)).items()},
+             'ktf': _rng_state_tuple(env._ktf_rng.get_state()),
+             'ranks': ranks,
+             'digest': ranks[0]['digest']}
+    if _guard_counters(env) is not None:
+        state['guard'] = _guard_counters(env)
+    return state
 
 
 class RunStateRefused(RuntimeError):
@@ -297,6 +315,8 @@ def restore(env, run_state):
         modules = dict(disc.named_modules())
         for name, u in run_state['u'].items():
             modules[name].u = None if u is None else u.detach().clone().to(env.device)
+    if run_state.get('guard') is not None and getattr(env, 'guard', None) is not None:
+        env.guard.load_counters(run_state['guard'])
     env._ktf_rng.set_state(_rng_state_numpy(run_state['ktf']))
     np.random.set_state(_rng_state_numpy(mine['numpy']))
     torch.set_rng_state(mine['torch_cpu'].cpu())
