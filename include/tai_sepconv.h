@@ -490,6 +490,59 @@ long long tai_grad_scale_workspace_bytes(int n_entries, long long n_segments);
 int tai_grad_scale(const long long* table, const long long* table_host, int n_entries, long long n_segments, float c, int blocks,
                    void* workspace, void* hip_stream);
 
+/* One launch per optimizer for the clip scaling, the Adam update and the generator's weight average (EMA), decided by a verdict that lives
+ * in device memory (csrc/fused_step.hip.inc; video_frame_inpainting_amd/fused_step.py builds the tables; train.py --fused_step
+ * [--ema_decay d]; restated in numpy in tests/fused_step_ref.py).  No counterpart in the reference, whose update is torch.optim.Adam.
+ *
+ * The definition.  Every operation below is one IEEE fp32 operation rounded to nearest even: nothing is contracted into a fused
+ * multiply-add, nothing reassociated, square root and division are correctly rounded.  The scalars come from a table the host builds
+ * once in float64 and rounds to fp32, for t' = 1 ... table_len:  step_size[t'] = f32(lr / (1 - beta1**t')),
+ * bc2s[t'] = f32(sqrt(1 - beta2**t')); constants w1 = f32(1 - beta1), b2 = f32(beta2), w2 = f32(1 - beta2), eps = f32(1e-8),
+ * wE = f32(1 - d).  With t the optimizer's device-resident step counter, t' = t + 1 and c the clip coefficient (fp32), per element
+ * when the verdict is not "skipped":
+ *     g1 = (c < 1) ? g * c : g
+ *     m' = m + w1 * (g1 - m)
+ *     v' = b2 * v + (w2 * g1) * g1
+ *     s  = sqrt(v') / bc2s[t'] + eps
+ *     p' = p - step_size[t'] * (m' / s)
+ *     e' = e + wE * (p' - e)                      (only entries that carry an EMA tensor)
+ * g is not written back.  Afterwards t is t + 1 and every `step` tensor of the table holds float(t').  When the verdict is "skipped"
+ * no byte of p, m, v, e, t or of a `step` tensor changes.
+ *
+ * tai_step_verdict (one workgroup; runs behind tai_grad_stats and in front of tai_fused_step on the same stream) writes the verdict of
+ * optimizer `which` (0 = generator, 1 = discriminator) into `record`, tai_step_verdict_workspace_bytes() bytes of device memory, 8-byte
+ * aligned, zero at the start of a run, as 64-bit words:
+ *   0, 1 skipped_G, skipped_D;  2 consecutive;  3 gave_up (sticky);  4 a step of the open update was skipped;
+ *   5-9 of the last skipped step: which, index of the first entry with non-finite elements, their number in it, in all, entries with any;
+ *   10, 11 verdict (0 ok, 1 clipped, 2 skipped);  12, 13 c (fp32 bits);  14, 15 the total sum of squares (fp64 bits);
+ *   16, 17 t;  18, 19 the t' of the step that follows (0 = none);  20 set when t' would pass table_len (that step is left out);
+ *   21 updates closed;  22 that number when gave_up was set.
+ * sumsq / nonfinite: the result arrays of tai_grad_stats over the same gradients (n_entries + 1 elements, the last the table's), or both
+ * null: no guard, the verdict is ok.  nonfinite[n_entries] > 0 -> skipped; otherwise, with max_norm > 0 (0 = no clipping),
+ * c64 = max_norm / (sqrt(total) + 1e-6) in fp64 with a correctly rounded square root and division, c = 1 if c64 >= 1 else f32(c64),
+ * clipped when c < 1: the bits of grad_guard.clip_coefficient.  A skip adds 1 to skipped_G / skipped_D; close_update != 0 (the update's
+ * last optimizer) sets consecutive to consecutive + 1 if a step of the update was skipped and to 0 otherwise, and gave_up once it reaches
+ * `patience`.  With gave_up set every verdict is "skipped" and nothing else in the record moves: the state stays where a host-side
+ * guard would have stopped the run.
+ *
+ * tai_fused_step: table / table_host, a device and a host copy of n_entries rows of eight 64-bit integers {p, g, m, v, step tensor
+ * (0 = none), e (0 = none), elements n_t, first segment}; an entry is cut into ceil(n_t / 16384) segments numbered consecutively in table
+ * order, n_segments in all; an empty entry has addresses 0.  table_host is read before the call returns and refused (TAI_SEPCONV_EINVAL,
+ * nothing launched) unless the segment numbers are exactly those and every address is 4-byte aligned.  scalars: device fp32
+ * [2][table_len], step_size then bc2s, element t' - 1 for step t'.  The kernel touches [address, address + 4 n_t) of p, g, m, v, e, one
+ * float of each step tensor, and reads record.  16-byte accesses where a full segment's addresses all allow, 4-byte ones otherwise (a
+ * gradient that is a view into a flat bucket, a short tail); nt != 0 loads g, m, v non-temporally; blocks: workgroups, 0 = the
+ * library's choice.  The results depend on none of these, nor on repetition from equal state.  It needs no workspace today (the query
+ * returns 0 and the pointer may be null).
+ * All: no allocation, copy or synchronisation; asynchronous on hip_stream. */
+long long tai_step_verdict_workspace_bytes(void);
+int tai_step_verdict(const double* sumsq, const long long* nonfinite, int n_entries, double max_norm, int which, int close_update,
+                     long long patience, long long table_len, long long* record, void* hip_stream);
+long long tai_fused_step_workspace_bytes(int n_entries, long long n_segments);
+int tai_fused_step(const long long* table, const long long* table_host, int n_entries, long long n_segments, const float* scalars,
+                   long long table_len, float w1, float b2, float w2, float eps, float wE, const long long* record, int which, int nt,
+                   int blocks, void* workspace, void* hip_stream);
+
 /* Text of the last error on the calling thread ("" if none). */
 const char* tai_sepconv_last_error(void);
 

@@ -8,7 +8,8 @@ protocol (:52-56), same PNG outputs and naming -- ``gt_preceding_%04d.png``, ``g
 ``--test_video_list_path`` takes the reference's list files (``<path> <a>-<b>``, or ``<path> <a>-<b> <c>-<d>`` with
 ``--disjoint_clips``; video_frame_inpainting_amd/data.py); a "video" is a directory of frame images or a .npy/.npz frame
 array (no video decoder exists in this image).  ``--synthetic N`` (an added flag) runs on N seeded synthetic clips
-instead, and ``--random_init`` keeps the seeded xavier weights when no checkpoint exists.  One process per GPU under
+instead, and ``--random_init`` keeps the seeded xavier weights when no checkpoint exists; ``--weights ema`` runs the snapshot's
+``generator_ema`` (the weight average of a ``train.py --ema_decay`` run).  One process per GPU under
 ``torch.distributed.run`` shards the clips across ranks.
 
   python predict.py --name demo --K 5 --T 5 --F 5 --c_dim 1 --image_size 128 --batch_size 8 --model_key TAI_gray \
@@ -100,7 +101,7 @@ def main(args=None):
     torch.manual_seed(0)
     model = vfi.create_model(opt.model_key)
     env = create_eval_environment(model, opt.checkpoints_dir, opt.name, opt.snapshot_file_name, opt.padding_size,
-                                  device=device, load_snapshot=not opt.random_init)
+                                  device=device, load_snapshot=not opt.random_init, weights=opt.weights)
     psnr_rows, ssim_rows = [], []
     h, w = opt.image_size
 

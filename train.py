@@ -19,6 +19,11 @@ optimizer whose gradients hold a NaN or an Inf does not step in that update, gra
 carry ``gnorm_G= gnorm_D= skipped=``, a state with non-finite values is never written over a snapshot, and after N consecutive updates
 with a skipped step the run ends with a non-zero exit, ``model_latest.ckpt`` being the last one written while healthy.
 
+``--fused_step [--ema_decay d]``: each optimizer's step is one HIP launch (fused_step.py) that scales, updates and averages on a verdict
+made on the device from the gradient statistics, so the host no longer waits between a backward pass and the step; the guard's counters
+are read where the run waits anyway (a printed line, validation, a save).  With ``--ema_decay`` an average of the generator's weights is
+kept, validated, and saved as ``generator_ema`` (``predict.py --weights ema``).
+
   python train.py --name demo --K 5 --T 5 --F 5 --c_dim 1 --image_size 128 --batch_size 4 --model_key TAI_gray \
       --max_iter 10 --synthetic 64
 """
@@ -42,6 +47,12 @@ def main(args=None):
         raise SystemExit('--guard refuses --graph_step: a replayed update cannot leave out an optimizer step')
     if not opt.guard and opt.clip_grad_norm is not None:
         raise SystemExit('--clip_grad_norm needs --guard')
+    if opt.fused_step and opt.graph_step:
+        raise SystemExit('--fused_step refuses --graph_step: its tables and their copies do not belong inside a captured update')
+    if opt.ema_decay is not None and not opt.fused_step:
+        raise SystemExit('--ema_decay needs --fused_step: the average is kept by the fused optimizer step')
+    if opt.ema_decay is not None and not 0.0 < opt.ema_decay < 1.0:
+        raise SystemExit('--ema_decay must lie strictly between 0 and 1, found %r' % opt.ema_decay)
     if not opt.resumable:
         return _run(opt, None)
     if opt.graph_step and GRAPH_STEP_REFUSAL:
@@ -119,7 +130,8 @@ def _run(opt, stop):
     env = create_training_environment(model, opt.c_dim, opt.checkpoints_dir, opt.name, opt.K, opt.T, opt.F,
                                       opt.image_size, opt.alpha, opt.beta, opt.lr, opt.beta1, opt.df_dim, opt.Ip,
                                       opt.disc_window_size, opt.padding_size, device=device,
-                                      graph_step=opt.graph_step, resumable=resumable, guard=guard)
+                                      graph_step=opt.graph_step, resumable=resumable, guard=guard, fused_step=opt.fused_step,
+                                      ema_decay=opt.ema_decay, max_iter=opt.max_iter)
     env.sync_replicas()
     total_updates = env.start_update
     # a resumed run starts from the best values its snapshot carries (train.py:96-97)
@@ -147,39 +159,41 @@ def _run(opt, stop):
                     raise RuntimeError('the snapshot was written with --synthetic %d --batch_size %d: it cannot be continued exactly'
                                        % (saved['n_clips'], saved['batch_size']))
                 order.set_state(run_state.numpy_state(saved['order']))
-    while total_updates < opt.max_iter:
-        t0 = time.time()
-        total_updates += 1
-        env.total_updates = total_updates
-        K, T, F = env.sample_KTF(opt.sample_KTF)
-        all_frames = next(stream) if loader is not None else clips[order.randint(0, n_clips, opt.batch_size)]
-        env.K, env.T, env.F = K, T, F
-        env.train()
-        # set_train_inputs -> forward_train -> optimize_parameters; one hipGraph replay per update with --graph_step
-        try:
+    try:
+        while total_updates < opt.max_iter:
+            t0 = time.time()
+            total_updates += 1
+            env.total_updates = total_updates
+            K, T, F = env.sample_KTF(opt.sample_KTF)
+            all_frames = next(stream) if loader is not None else clips[order.randint(0, n_clips, opt.batch_size)]
+            env.K, env.T, env.F = K, T, F
+            env.train()
+            # set_train_inputs -> forward_train -> optimize_parameters; one hipGraph replay per update with --graph_step
             env.train_step(all_frames[:, :K], all_frames[:, K + T:K + T + F], all_frames[:, K:K + T])
-        except grad_guard.GuardGaveUp as e:
-            # no snapshot on the way out: model_latest.ckpt is the last one written while the run was healthy
-            raise SystemExit('iter %d: the guard gives up: %s' % (total_updates, e))
-        if total_updates % opt.print_freq == 0 or total_updates == 1:
-            torch.cuda.synchronize()
-            errs = env.get_current_errors()
-            state = (guard.log_suffix() if guard is not None else '') + (' state=%016x' % run_state.digest(env) if resumable else '')
-            if rank == 0:
-                print('iter %d (K,T,F)=(%d,%d,%d) %.3fs  %s%s' % (total_updates, K, T, F, time.time() - t0,
-                                                                  ' '.join('%s=%.5f' % kv for kv in sorted(errs.items())), state))
-        if resumable and stop.agreed():
-            # a save has to fit between SIGTERM and SIGKILL: no validation pass is started once the flag is up
-            env.save('model_latest.ckpt', total_updates, *validator.best)
-            if rank == 0:
-                print('Stop requested: model_latest.ckpt holds update %d' % total_updates)
-            return
-        if total_updates % opt.save_latest_freq == 0:
-            env.save('model_latest.ckpt', total_updates, *validator.best)
-            env.save('model_%08d.ckpt' % total_updates, total_updates, *validator.best)
-        if validator and total_updates % opt.validate_freq == 0:
-            validator.validate(env, total_updates)
-    env.save('model_latest.ckpt', total_updates, *validator.best)
+            if total_updates % opt.print_freq == 0 or total_updates == 1:
+                torch.cuda.synchronize()
+                env.sync_guard(agree=True)         # (with --fused_step the verdicts were made on the device: read them for the line)
+                errs = env.get_current_errors()
+                state = (guard.log_suffix() if guard is not None else '') + (' state=%016x' % run_state.digest(env) if resumable else '')
+                if rank == 0:
+                    print('iter %d (K,T,F)=(%d,%d,%d) %.3fs  %s%s' % (total_updates, K, T, F, time.time() - t0,
+                                                                      ' '.join('%s=%.5f' % kv for kv in sorted(errs.items())), state))
+            if resumable and stop.agreed():
+                # a save has to fit between SIGTERM and SIGKILL: no validation pass is started once the flag is up
+                env.save('model_latest.ckpt', total_updates, *validator.best)
+                if rank == 0:
+                    print('Stop requested: model_latest.ckpt holds update %d' % total_updates)
+                return
+            if total_updates % opt.save_latest_freq == 0:
+                env.save('model_latest.ckpt', total_updates, *validator.best)
+                env.save('model_%08d.ckpt' % total_updates, total_updates, *validator.best)
+            if validator and total_updates % opt.validate_freq == 0:
+                validator.validate(env, total_updates)
+        env.save('model_latest.ckpt', total_updates, *validator.best)
+    except grad_guard.GuardGaveUp as e:
+        # no snapshot on the way out: model_latest.ckpt is the last one written while the run was healthy.  (With --fused_step the
+        # device gave up in an update that may lie a few behind the one whose read found it; the state has stood still since.)
+        raise SystemExit('iter %d: the guard gives up: %s' % (total_updates - getattr(e, 'updates_ago', 0), e))
     print('Done.')
 
 

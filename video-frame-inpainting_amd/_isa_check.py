@@ -7,6 +7,12 @@ wino43::conv3x3_gen and conv3x3_wrw_gen (the F(4x4, 3x3) kernel and its weight-g
    spill would be vector-memory traffic the statement's own s_waitcnt vmcnt counting does not expect.
    (Round 4's compiler-scheduled forms of that kernel, whose asm loads depended on the compiler not touching their destination registers
    before a wait it could not see, are gone: every load of the kernel is inside the statement now.)
+
+fstep::step_segments (the fused optimizer step, csrc/fused_step.hip.inc): its arithmetic is a written definition of single IEEE fp32
+   operations.  Contraction is switched off in the source; what the compiler may still add are the fused multiply-adds INSIDE its
+   correctly rounded division (five each) and square root (two each, the next-up / next-down residual test behind v_sqrt_f32).  So the
+   number of fp32 fma / fmac / mad instructions must be exactly 5 x divisions + 2 x square roots -- one more would be a contracted
+   a * b + c of the definition -- every square root must be the refined form, and there is no scratch.
 """
 import re
 
@@ -64,4 +70,27 @@ def check(asm):
         want = 252 if name in wrw else 216
         if n != want:
             bad.append('%s: %d MFMAs in the chunk loops, expected %d' % (name, n, want))
+    return bad
+
+
+def check_fused_step(asm):
+    """-> list of violations of the fused optimizer step's kernels (see the module's docstring)."""
+    bad = []
+    found = kernels(asm, '_ZN5fstep13step_segments')
+    if len(found) != 2:
+        bad.append('expected two fstep::step_segments kernels (plain and non-temporal loads), found %d' % len(found))
+    for name, (lines, desc) in found.items():
+        ops = [l.split()[0] for l in lines if l.startswith('\t') and l.split() and l.split()[0].startswith(('v_', 'scratch_'))]
+        count = lambda *prefixes: sum(1 for o in ops if o.startswith(prefixes))
+        if int(re.search(r'\.amdhsa_private_segment_fixed_size\s+(\d+)', desc).group(1)) != 0 or count('scratch_'):
+            bad.append('%s: scratch memory in use' % name)
+        fused = count('v_fma_f32', 'v_fmac_f32', 'v_mad_f32', 'v_mac_f32', 'v_pk_fma_f32', 'v_fma_mix', 'v_fmaak_f32', 'v_fmamk_f32')
+        divisions, roots = count('v_div_fixup_f32'), count('v_sqrt_f32')
+        if divisions == 0 or roots == 0 or count('v_div_fmas_f32') != divisions:
+            bad.append('%s: no IEEE division / square root sequence found (%d v_div_fixup_f32, %d v_sqrt_f32)' % (name, divisions, roots))
+        if fused != 5 * divisions + 2 * roots:
+            bad.append('%s: %d fused multiply-adds for %d divisions and %d square roots (5 and 2 each expected): the arithmetic of the '
+                       'definition was contracted, or the division / square root is not the correctly rounded form' % (name, fused, divisions, roots))
+        if count('v_rsq_f32', 'v_rcp_iflag'):
+            bad.append('%s: an approximate reciprocal square root in the step arithmetic' % name)
     return bad

@@ -94,7 +94,7 @@ def build(force=False, verbose=False, timing=False):
             raise NativeLibraryError('csrc/ changed while %s was compiling: build again' % os.path.basename(out))
         asm = os.path.join(work, 'sepconv_capi-hip-amdgcn-amd-amdhsa-gfx950.s')
         from . import _isa_check
-        violations = _isa_check.check(open(asm).read())
+        violations = _isa_check.check(open(asm).read()) + _isa_check.check_fused_step(open(asm).read())
         if violations:
             raise NativeLibraryError('the device code hipcc generated for %s breaks an invariant the kernels rely on; the library is NOT '
                                      'installed:\n  %s' % (os.path.basename(out), '\n  '.join(violations[:20])))
@@ -297,6 +297,15 @@ def lib():
     L.tai_grad_scale_workspace_bytes.restype = ctypes.c_longlong
     L.tai_grad_scale.argtypes = [P, P, I, ctypes.c_longlong, ctypes.c_float, I, P, V]
     L.tai_grad_scale.restype = I
+    LL, Fl = ctypes.c_longlong, ctypes.c_float
+    L.tai_step_verdict_workspace_bytes.argtypes = []
+    L.tai_step_verdict_workspace_bytes.restype = LL
+    L.tai_step_verdict.argtypes = [P, P, I, ctypes.c_double, I, I, LL, LL, P, V]
+    L.tai_step_verdict.restype = I
+    L.tai_fused_step_workspace_bytes.argtypes = [I, LL]
+    L.tai_fused_step_workspace_bytes.restype = LL
+    L.tai_fused_step.argtypes = [P, P, I, LL, P, LL, Fl, Fl, Fl, Fl, Fl, P, I, I, I, P, V]
+    L.tai_fused_step.restype = I
     L.tai_sepconv_last_error.restype = ctypes.c_char_p
     L.tai_sepconv_source_hash.restype = ctypes.c_char_p
     L.tai_sepconv_version.restype = I

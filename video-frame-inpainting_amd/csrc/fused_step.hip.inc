@@ -1,0 +1,258 @@
+// One launch per optimizer: clip scaling, the Adam update and the weight average (EMA) over a table of fp32 tensors, decided by a verdict
+// that a one-workgroup kernel has put into device memory from tai_grad_stats' results (video_frame_inpainting_amd/fused_step.py; the
+// definition is restated in numpy in tests/fused_step_ref.py, which pins it).  The host does not wait between backward() and the step.
+//
+// Definition.  Every operation is ONE IEEE fp32 operation, rounded to nearest even: nothing contracted into a fused multiply-add, nothing
+// reassociated, square root and division correctly rounded.  With the scalars of the host's table (tai_sepconv.h) and t' = t + 1:
+//     g1 = (c < 1) ? g * c : g
+//     m' = m + w1 * (g1 - m)
+//     v' = b2 * v + (w2 * g1) * g1
+//     s  = sqrt(v') / bc2s[t'] + eps
+//     p' = p - step_size[t'] * (m' / s)
+//     e' = e + wE * (p' - e)              (entries that carry an EMA tensor)
+// and every `step` tensor of the table holds float(t') afterwards.  A skipped step changes no byte.
+//
+// On the hardware: the 16384-element segments and the grid-stride walk of gstat::segment_stats; one workgroup of 256 lanes per segment,
+// four rounds of 16-byte loads per array in flight per lane where every address of the segment is 16-byte aligned and the segment is
+// full, 4-byte accesses otherwise (a gradient that is a view into a flat bucket, a short tail).  28 bytes per element, 36 with the EMA:
+// an HBM-rate kernel.  `#pragma clang fp contract(off)` keeps the arithmetic as written; the only fused multiply-adds in the generated
+// code are those inside the compiler's correctly rounded division and square root.
+//
+// Table row t (eight 64-bit integers): {p, g, m, v, step tensor (0 = none), e (0 = none), elements n_t, first segment}.
+// The record (REC_WORDS 64-bit words, written by lane 0 of step_verdict with plain vector stores):
+//   0 skipped_G  1 skipped_D  2 consecutive  3 gave_up (sticky)  4 a step of the open update was skipped
+//   5.. the last skip: optimizer (0 G, 1 D), index of the first entry with non-finite elements, their number there, in all, entries with any
+//   10,11 verdict G, D   12,13 clip coefficient (fp32 bits)   14,15 total sum of squares (fp64 bits)
+//   16,17 steps made t_G, t_D   18,19 the t' of the step that follows this verdict (0: none)   20 t' beyond the scalar table
+//   21 updates closed   22 ... when gave_up was set
+namespace fstep {
+
+constexpr int THREADS = 256;
+constexpr int SEG = 16384;
+constexpr int ROW = 8;
+constexpr int REC_WORDS = 32;
+constexpr int BATCH = 4;                                  // rounds of 16-byte loads per array in flight per lane
+constexpr int ROUNDS = SEG / (4 * THREADS);
+enum { R_SKIPPED = 0, R_CONSECUTIVE = 2, R_GAVE_UP = 3, R_IN_UPDATE = 4, R_BAD_WHICH = 5, R_BAD_FIRST = 6, R_BAD_FIRST_COUNT = 7,
+       R_BAD_TOTAL = 8, R_BAD_ENTRIES = 9, R_VERDICT = 10, R_COEFF = 12, R_TOTAL = 14, R_T = 16, R_TPRIME = 18, R_OVERFLOW = 20,
+       R_CLOSED = 21, R_GAVE_UP_AT = 22 };
+enum { OK = 0, CLIPPED = 1, SKIPPED = 2 };
+
+typedef float f4v __attribute__((ext_vector_type(4)));
+typedef __attribute__((address_space(1))) float* gfloats;            // global, not flat: addresses come out of the table as integers
+typedef const __attribute__((address_space(1))) float* cgfloats;
+typedef __attribute__((address_space(1))) f4v* gvecs;
+typedef const __attribute__((address_space(1))) f4v* cgvecs;
+
+struct Scalars {
+    float w1, b2, w2, eps, wE;
+};
+
+// sqrt(x) in fp64, correctly rounded whatever the instruction sequence gives: s is too small exactly when x > s * next(s), too large
+// exactly when x <= s * prev(s) (the products are exact inside the fma, and x - s * s' is a multiple of four times the squared half-ulp,
+// so the sign of the rounded residual decides).
+__device__ __forceinline__ double sqrt_rn(double x) {
+    double s = __builtin_sqrt(x);
+    if (x > 0.0 && x < __builtin_inf()) {
+        const double up = __longlong_as_double(__double_as_longlong(s) + 1);
+        const double down = __longlong_as_double(__double_as_longlong(s) - 1);
+        if (__builtin_fma(-s, up, x) > 0.0) s = up;
+        else if (__builtin_fma(-s, down, x) <= 0.0) s = down;
+    }
+    return s;
+}
+
+// One workgroup.  sumsq / nonfinite: tai_grad_stats' results (n_entries + 1 elements, the last one the table's), or null: no guard, the
+// verdict is "ok".  Formulas of grad_guard.clip_coefficient and GradGuard.judge / end_update.
+__global__ __launch_bounds__(THREADS) void step_verdict(const double* __restrict__ sumsq, const long long* __restrict__ nonfinite,
+                                                        int n_entries, double max_norm, int which, int close_update, long long patience,
+                                                        long long table_len, long long* __restrict__ rec) {
+    __shared__ int s_first[THREADS];
+    __shared__ int s_entries[THREADS];
+    int first = 0x7FFFFFFF, entries = 0;
+    if (nonfinite)
+        for (int t = threadIdx.x; t < n_entries; t += THREADS)
+            if (nonfinite[t] > 0) {
+                first = t < first ? t : first;
+                ++entries;
+            }
+    s_first[threadIdx.x] = first;
+    s_entries[threadIdx.x] = entries;
+    __syncthreads();
+    for (int d = THREADS / 2; d > 0; d >>= 1) {
+        if ((int)threadIdx.x < d) {
+            const int o = s_first[threadIdx.x + d];
+            s_first[threadIdx.x] = o < s_first[threadIdx.x] ? o : s_first[threadIdx.x];
+            s_entries[threadIdx.x] += s_entries[threadIdx.x + d];
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x != 0) return;
+    const bool frozen = rec[R_GAVE_UP] != 0;
+    long long verdict = OK, tprime = 0;
+    float c = 1.0f;
+    if (frozen) {
+        verdict = SKIPPED;
+    } else {
+        const double total = sumsq ? sumsq[n_entries] : 0.0;
+        const long long bad = nonfinite ? nonfinite[n_entries] : 0;
+        if (bad > 0) {
+            verdict = SKIPPED;
+            rec[R_SKIPPED + which] += 1;
+            rec[R_IN_UPDATE] = 1;
+            rec[R_BAD_WHICH] = which;
+            rec[R_BAD_FIRST] = s_first[0];
+            rec[R_BAD_FIRST_COUNT] = s_first[0] < n_entries ? nonfinite[s_first[0]] : 0;
+            rec[R_BAD_TOTAL] = bad;
+            rec[R_BAD_ENTRIES] = s_entries[0];
+        } else if (sumsq && max_norm > 0.0) {
+            const double c64 = max_norm / (sqrt_rn(total) + 1e-6);
+            if (!(c64 >= 1.0)) c = (float)c64;
+            verdict = c < 1.0f ? CLIPPED : OK;
+        }
+        rec[R_TOTAL + which] = __double_as_longlong(total);
+        if (verdict != SKIPPED) {
+            tprime = rec[R_T + which] + 1;
+            if (tprime > table_len) {               // the scalar table ends: no step, and the host is told
+                rec[R_OVERFLOW] = 1;
+                verdict = SKIPPED;
+                tprime = 0;
+            } else {
+                rec[R_T + which] = tprime;
+            }
+        }
+    }
+    rec[R_VERDICT + which] = verdict;
+    rec[R_COEFF + which] = (long long)__float_as_uint(c);
+    rec[R_TPRIME + which] = tprime;
+    if (close_update && !frozen) {
+        const long long run = rec[R_IN_UPDATE] ? rec[R_CONSECUTIVE] + 1 : 0;
+        rec[R_CONSECUTIVE] = run;
+        rec[R_IN_UPDATE] = 0;
+        rec[R_CLOSED] += 1;
+        if (run >= patience) {
+            rec[R_GAVE_UP] = 1;
+            rec[R_GAVE_UP_AT] = rec[R_CLOSED];
+        }
+    }
+}
+
+// T: float or f4v (element-wise: the same operations on each component)
+template <typename T>
+__device__ __forceinline__ void element(T& p, const T g, T& m, T& v, const float c, const Scalars k, const float step_size, const float bc2s) {
+#pragma clang fp contract(off)
+    const T g1 = c < 1.0f ? g * c : g;
+    const T d = g1 - m;
+    const T wd = d * k.w1;
+    m = m + wd;
+    const T bv = v * k.b2;
+    const T wg = g1 * k.w2;
+    const T wgg = wg * g1;
+    v = bv + wgg;
+    const T r = __builtin_elementwise_sqrt(v);
+    const T q = r / bc2s;
+    const T s = q + k.eps;
+    const T u = m / s;
+    const T su = u * step_size;
+    p = p - su;
+}
+
+template <typename T>
+__device__ __forceinline__ T average(const T e, const T p, const float wE) {
+#pragma clang fp contract(off)
+    const T d = p - e;
+    const T wd = d * wE;
+    return e + wd;
+}
+
+template <bool NT>
+__device__ __forceinline__ f4v load_stream(cgvecs a) {
+    if (NT) return __builtin_nontemporal_load(a);
+    return *a;
+}
+
+// scalars: device fp32 [2][table_len]: step_size[t' - 1], then bc2s[t' - 1].
+template <bool NT>
+__global__ __launch_bounds__(THREADS) void step_segments(const long long* __restrict__ table, int n_entries, long long n_segments,
+                                                         const float* __restrict__ scalars, long long table_len, const Scalars k,
+                                                         const long long* __restrict__ rec, int which) {
+    if (rec[R_VERDICT + which] == SKIPPED) return;
+    const long long tprime = rec[R_TPRIME + which];
+    if (tprime < 1 || tprime > table_len) return;
+    const float c = __uint_as_float((unsigned int)rec[R_COEFF + which]);
+    const float step_size = scalars[tprime - 1], bc2s = scalars[table_len + tprime - 1];
+    for (long long t = (long long)blockIdx.x * THREADS + threadIdx.x; t < n_entries; t += (long long)gridDim.x * THREADS) {
+        const gfloats step = (gfloats)(unsigned long long)table[ROW * t + 4];
+        if (step) *step = (float)tprime;
+    }
+    for (long long seg = blockIdx.x; seg < n_segments; seg += gridDim.x) {
+        int lo = 0, hi = n_entries - 1;                  // the LAST row with first segment <= seg (gstat::owner on this row)
+        while (lo < hi) {
+            const int mid = (lo + hi + 1) >> 1;
+            if (table[ROW * (long long)mid + 7] <= seg) lo = mid; else hi = mid - 1;
+        }
+        const long long* row = table + ROW * (long long)lo;
+        const unsigned long long n = (unsigned long long)row[6];
+        const unsigned long long first = (unsigned long long)(seg - row[7]) * SEG;
+        if (row[0] == 0 || first >= n) continue;
+        const unsigned int count = n - first < SEG ? (unsigned int)(n - first) : SEG;
+        const gfloats p = (gfloats)(unsigned long long)row[0] + first;
+        const cgfloats g = (cgfloats)(unsigned long long)row[1] + first;
+        const gfloats m = (gfloats)(unsigned long long)row[2] + first;
+        const gfloats v = (gfloats)(unsigned long long)row[3] + first;
+        const gfloats e = row[5] ? (gfloats)(unsigned long long)row[5] + first : (gfloats)0;
+        const unsigned long long low = (unsigned long long)p | (unsigned long long)g | (unsigned long long)m | (unsigned long long)v |
+                                       (unsigned long long)e;
+        if (count == SEG && (low & 15) == 0) {
+            const gvecs pv = (gvecs)p + threadIdx.x;
+            const cgvecs gv = (cgvecs)g + threadIdx.x;
+            const gvecs mv = (gvecs)m + threadIdx.x;
+            const gvecs vv = (gvecs)v + threadIdx.x;
+            const gvecs ev = e ? (gvecs)e + threadIdx.x : (gvecs)0;
+            for (int b = 0; b < ROUNDS / BATCH; ++b) {
+                f4v xp[BATCH], xg[BATCH], xm[BATCH], xv[BATCH], xe[BATCH];
+#pragma unroll
+                for (int r = 0; r < BATCH; ++r) {
+                    const int at = (b * BATCH + r) * THREADS;
+                    xg[r] = load_stream<NT>(gv + at);
+                    xm[r] = load_stream<NT>((cgvecs)mv + at);
+                    xv[r] = load_stream<NT>((cgvecs)vv + at);
+                    xp[r] = pv[at];
+                }
+                if (ev) {
+#pragma unroll
+                    for (int r = 0; r < BATCH; ++r) xe[r] = ev[(b * BATCH + r) * THREADS];
+                }
+#pragma unroll
+                for (int r = 0; r < BATCH; ++r) {
+                    element(xp[r], xg[r], xm[r], xv[r], c, k, step_size, bc2s);
+                }
+#pragma unroll
+                for (int r = 0; r < BATCH; ++r) {
+                    const int at = (b * BATCH + r) * THREADS;
+                    pv[at] = xp[r];
+                    mv[at] = xm[r];
+                    vv[at] = xv[r];
+                }
+                if (ev) {
+#pragma unroll
+                    for (int r = 0; r < BATCH; ++r) {
+                        const f4v a = average(xe[r], xp[r], k.wE);
+                        ev[(b * BATCH + r) * THREADS] = a;
+                    }
+                }
+            }
+        } else {
+            for (unsigned int i = threadIdx.x; i < count; i += THREADS) {
+                float xp = p[i], xm = m[i], xv = v[i];
+                element(xp, g[i], xm, xv, c, k, step_size, bc2s);
+                p[i] = xp;
+                m[i] = xm;
+                v[i] = xv;
+                if (e) e[i] = average(e[i], xp, k.wE);
+            }
+        }
+    }
+}
+
+}  // namespace fstep

@@ -31,6 +31,7 @@
 #include "clip_pipeline.hip.inc"
 #include "state_digest.hip.inc"
 #include "grad_stats.hip.inc"
+#include "fused_step.hip.inc"
 
 namespace {
 
@@ -284,7 +285,7 @@ int launch_grad_vh_tiled(const float* gO, const float* in, const float* v, const
 
 extern "C" {
 
-int tai_sepconv_version(void) { return 700; }     // 0.7.0: gradient statistics and scaling over a table of tensors (tai_grad_stats, tai_grad_scale), no other kernel changed; (0.6.0: (tai_state_digest added at the same number: an entry point of its own, and the committed counter summaries are tied to it); clip pipeline entry points (tai_clip_from_frames, tai_frames_to_uint8), no other kernel changed; (0.5.0: F(4x4, 3x3) chunk loop as generated assembly, displaced-read blocks, any C; (0.4.1: persistent forward kernel beyond the Infinity Cache: type-A waves at their partners' priority (0.4.0: nt tap loads + reversed walk; source hash))))
+int tai_sepconv_version(void) { return 800; }     // 0.7.0: gradient statistics and scaling over a table of tensors (tai_grad_stats, tai_grad_scale), no other kernel changed; (0.6.0: (tai_state_digest added at the same number: an entry point of its own, and the committed counter summaries are tied to it); clip pipeline entry points (tai_clip_from_frames, tai_frames_to_uint8), no other kernel changed; (0.5.0: F(4x4, 3x3) chunk loop as generated assembly, displaced-read blocks, any C; (0.4.1: persistent forward kernel beyond the Infinity Cache: type-A waves at their partners' priority (0.4.0: nt tap loads + reversed walk; source hash))))
 
 const char* tai_sepconv_last_error(void) { return g_err; }
 
@@ -1780,6 +1781,61 @@ int tai_grad_scale(const long long* table, const long long* table_host, int n_en
     hipLaunchKernelGGL(gstat::scale_segments, dim3(grad_blocks(n_segments, blocks)), dim3(gstat::THREADS), 0, static_cast<hipStream_t>(hip_stream),
                        table, n_entries, n_segments, c);
     return check_launch("grad_scale");
+}
+
+long long tai_step_verdict_workspace_bytes(void) {
+    return 8LL * fstep::REC_WORDS;
+}
+
+int tai_step_verdict(const double* sumsq, const long long* nonfinite, int n_entries, double max_norm, int which, int close_update,
+                     long long patience, long long table_len, long long* record, void* hip_stream) {
+    g_err[0] = 0;
+    if (!record || ((uintptr_t)record & 7) != 0) return fail(TAI_SEPCONV_EINVAL, "%s", "step_verdict: the record must be an 8-byte aligned device pointer");
+    if ((sumsq == nullptr) != (nonfinite == nullptr)) return fail(TAI_SEPCONV_EINVAL, "%s", "step_verdict: sumsq and nonfinite come together or not at all");
+    if (((uintptr_t)sumsq & 7) != 0 || ((uintptr_t)nonfinite & 7) != 0) return fail(TAI_SEPCONV_EINVAL, "%s", "step_verdict: sumsq and nonfinite must be 8-byte aligned");
+    if ((sumsq && n_entries <= 0) || n_entries < 0 || (which != 0 && which != 1) || patience < 1 || table_len < 1 || !(max_norm >= 0.0) || max_norm - max_norm != 0.0)
+        return fail(TAI_SEPCONV_EINVAL, "%s", "step_verdict: needs n_entries > 0 with statistics, which in {0, 1}, patience >= 1, table_len >= 1 and a finite max_norm >= 0 (0 = no clipping)");
+    hipLaunchKernelGGL(fstep::step_verdict, dim3(1), dim3(fstep::THREADS), 0, static_cast<hipStream_t>(hip_stream), sumsq, nonfinite, n_entries,
+                       max_norm, which, close_update != 0, patience, table_len, record);
+    return check_launch("step_verdict");
+}
+
+long long tai_fused_step_workspace_bytes(int n_entries, long long n_segments) {
+    if (n_entries <= 0 || n_segments < 0) return TAI_SEPCONV_EINVAL;
+    return 0;
+}
+
+int tai_fused_step(const long long* table, const long long* table_host, int n_entries, long long n_segments, const float* scalars,
+                   long long table_len, float w1, float b2, float w2, float eps, float wE, const long long* record, int which, int nt,
+                   int blocks, void* workspace, void* hip_stream) {
+    g_err[0] = 0;
+    (void)workspace;
+    if (!table || !table_host || !scalars || !record) return fail(TAI_SEPCONV_EINVAL, "%s", "fused_step: null pointer");
+    if (n_entries <= 0 || blocks < 0 || blocks > 65536 || (which != 0 && which != 1) || table_len < 1 || ((uintptr_t)record & 7) != 0 || ((uintptr_t)scalars & 3) != 0)
+        return fail(TAI_SEPCONV_EINVAL, "%s", "fused_step: needs n_entries > 0, 0 <= blocks <= 65536, which in {0, 1}, table_len >= 1, aligned record and scalars");
+    long long next = 0;
+    for (int t = 0; t < n_entries; ++t) {
+        const long long* row = table_host + fstep::ROW * (long long)t;
+        const long long n = row[6];
+        bool ok = n >= 0 && n < (1LL << 40) && row[7] == next && (row[4] & 3) == 0;
+        for (int a = 0; a < 4 && ok; ++a) ok = (row[a] & 3) == 0 && (row[a] == 0) == (n == 0);
+        ok = ok && (row[5] & 3) == 0 && (n != 0 || row[5] == 0);
+        if (!ok) {
+            std::snprintf(g_err, sizeof(g_err), "fused_step: row %d is not {p, g, m, v (4-byte aligned, 0 exactly when empty), step, e, 0 <= elements < 2^40, first segment %lld}", t, next);
+            return TAI_SEPCONV_EINVAL;
+        }
+        next += (n + fstep::SEG - 1) / fstep::SEG;
+    }
+    if (next != n_segments) {
+        std::snprintf(g_err, sizeof(g_err), "fused_step: the table has %lld segments, not %lld", next, n_segments);
+        return TAI_SEPCONV_EINVAL;
+    }
+    const fstep::Scalars k = {w1, b2, w2, eps, wE};
+    const dim3 grid(grad_blocks(n_segments > 0 ? n_segments : 1, blocks)), block(fstep::THREADS);
+    hipStream_t s = static_cast<hipStream_t>(hip_stream);
+    if (nt) hipLaunchKernelGGL((fstep::step_segments<true>), grid, block, 0, s, table, n_entries, n_segments, scalars, table_len, k, record, which);
+    else    hipLaunchKernelGGL((fstep::step_segments<false>), grid, block, 0, s, table, n_entries, n_segments, scalars, table_len, k, record, which);
+    return check_launch("fused_step");
 }
 
 }  // extern "C"

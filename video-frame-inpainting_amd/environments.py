@@ -21,6 +21,7 @@ import numpy as np
 import torch
 
 from . import conv_ops, parallel, run_state
+from . import fused_step as fused_step_module
 from .graph import GraphedForward
 from .losses import GDL
 from .mcnet import MCNetFillInModel
@@ -32,9 +33,10 @@ from .util import inverse_transform, move_to_devices, weights_init
 
 
 def create_eval_environment(fill_in_model, checkpoints_dir, name, snapshot_file_name, padding_size, device=None,
-                            load_snapshot=True, use_graph=False):
+                            load_snapshot=True, use_graph=False, weights='raw'):
     env = BaseVideoFillInEnvironment(fill_in_model, checkpoints_dir, name, padding_size, device=device,
                                      use_graph=use_graph)
+    env.weights = weights          # 'ema': the snapshot's generator_ema (train.py --ema_decay) instead of its generator
     if load_snapshot and not isinstance(fill_in_model, TimeWeightedPFFillInModel):   # environments.py:57-58
         env.load(snapshot_file_name)
     print('Loaded evaluation environment')
@@ -43,9 +45,14 @@ def create_eval_environment(fill_in_model, checkpoints_dir, name, snapshot_file_
 
 def create_training_environment(fill_in_model, c_dim, checkpoints_dir, name, max_K, max_T, max_F, image_size, alpha,
                                 beta, lr, beta1, df_dim, Ip, disc_window_size, padding_size, device=None, graph_step=False,
-                                resumable=False, guard=None):
+                                resumable=False, guard=None, fused_step=False, ema_decay=None, max_iter=100000):
     if guard is not None and graph_step:
         raise ValueError('a guarded update cannot be a captured one: a replayed update cannot leave out an optimizer step')
+    if fused_step and graph_step:
+        raise ValueError('a fused step cannot be part of a captured update: its tables and their copies do not belong inside a capture')
+    if ema_decay is not None and not fused_step:
+        raise ValueError('--ema_decay needs --fused_step: the average is kept by the fused optimizer step')
+    fused_step_module.check_ema_decay(ema_decay)
     if isinstance(fill_in_model, (TAIFillInModel, TimeWeightedInterpolationFillInModel,
                                   BidirectionalSimpleAverageFillInModel, BidirectionalTimeWeightedAverageFillInModel)):
         env = TAITrainingEnvironment(      # environments.py:29-31
@@ -61,6 +68,11 @@ def create_training_environment(fill_in_model, c_dim, checkpoints_dir, name, max
                            % type(fill_in_model).__name__)
     env.resumable = bool(resumable)
     env.guard = guard
+    if fused_step:
+        env.fused = fused_step_module.FusedStep(env.device, max_iter, guard=guard, ema_decay=ema_decay)
+        env.fused.attach('G', env.generator, env.optimizer_G)
+        if hasattr(env, 'optimizer_D'):
+            env.fused.attach('D', env.discriminator, env.optimizer_D)
     remove_stale_temporaries(env.save_dir)
     names = [n for n in (LATEST, PREVIOUS if env.resumable else None) if n and os.path.isfile(os.path.join(env.save_dir, n))]
     for i, file_name in enumerate(names):
@@ -178,7 +190,10 @@ class BaseVideoFillInEnvironment(object):
                 snapshot = torch.load(save_path, map_location=self.device, weights_only=False, encoding='latin1')
         else:
             raise RuntimeError('Failed to find snapshot at path %s' % save_path)
-        self.generator.load_state_dict(snapshot['generator'])
+        key = 'generator_ema' if getattr(self, 'weights', 'raw') == 'ema' else 'generator'
+        if key not in snapshot:
+            raise RuntimeError("%s holds no '%s': it was not written by a run with train.py --ema_decay" % (save_path, key))
+        self.generator.load_state_dict(snapshot[key])
         conv_ops.invalidate_derived(self.generator)
         self._graphs.clear()
         return snapshot
@@ -209,6 +224,9 @@ class BaseTrainingEnvironment(BaseVideoFillInEnvironment):
         # guard (train.py --guard): a grad_guard.GradGuard that looks at the gradients between each backward pass and its optimizer step
         # and leaves the step out when they hold a NaN or an Inf; None = the reference's update, nothing looked at
         self.guard = None
+        # fused (train.py --fused_step [--ema_decay d]): a fused_step.FusedStep that makes both optimizers' steps, one HIP launch each, on a
+        # verdict that stays on the device, and keeps the generator's weight average; None = ``optimizer.step()``
+        self.fused = None
         self.start_update = 0
         self.total_updates = 0
         self.start_sum_avg_psnr_err = 0
@@ -320,12 +338,17 @@ class BaseTrainingEnvironment(BaseVideoFillInEnvironment):
             'sum_avg_psnr_err': sum_avg_psnr_err,
             'sum_avg_ssim_err': sum_avg_ssim_err,
             'generator': self.generator.state_dict(),
-            'optimizer_G': self.optimizer_G.state_dict(),
+            'optimizer_G': self._optimizer_state_dict(self.optimizer_G),
         }
+        if self.fused is not None and self.fused.ema_decay is not None:
+            state['generator_ema'] = self.fused.ema_state_dict(self.generator)
         if self.resumable:
             # the one key beyond the reference's; a collective in a data-parallel run (every rank's generator states go to rank 0)
             state['run_state'] = run_state.capture(self)
         return state
+
+    def _optimizer_state_dict(self, optimizer):
+        return optimizer.state_dict() if self.fused is None else self.fused.optimizer_state_dict(optimizer)
 
     def load(self, snapshot_file_name):
         snapshot = super().load(snapshot_file_name)
@@ -334,7 +357,11 @@ class BaseTrainingEnvironment(BaseVideoFillInEnvironment):
         self.start_sum_avg_ssim_err = snapshot['sum_avg_ssim_err']
         self._step_graphs.clear()
         self._load_training_state(snapshot)
+        if self.fused is not None:
+            self.fused.after_load(snapshot, (snapshot.get('run_state') or {}).get('ema') if self.resumable else None)
         self._restore_run_state(snapshot, snapshot_file_name)       # last: the generator states are set behind everything that could draw
+        if self.fused is not None:
+            self.fused.push_counters()
         return snapshot
 
     def _load_training_state(self, snapshot):
@@ -355,7 +382,8 @@ class BaseTrainingEnvironment(BaseVideoFillInEnvironment):
             print('%s: %s: the run continues from its weights and optimizer state, but NOT exactly' % (snapshot_file_name, e))
             return
         want = state['ranks'][parallel.rank()]['digest']
-        have = run_state.digest(self, data_state, guard_counters=state.get('guard'))      # the table of the run that wrote it
+        have = run_state.digest(self, data_state, guard_counters=state.get('guard'),      # the table of the run that wrote it
+                                ema=fused_step_module.snapshot_ema_entries(snapshot))
         if have != want:
             raise SnapshotRefused('state digest %016x after loading, %016x when it was saved' % (have, want))
         self.exact_resume, self.restored_data_state = True, data_state
@@ -363,6 +391,8 @@ class BaseTrainingEnvironment(BaseVideoFillInEnvironment):
     def save(self, snapshot_file_name, total_updates, sum_avg_psnr_err, sum_avg_ssim_err):
         if parallel.rank() != 0 and not (self.resumable and parallel.world_size() > 1):
             return
+        if self.fused is not None:
+            self.sync_guard(agree=self.resumable and parallel.world_size() > 1)
         if self.guard is not None:
             self._refuse_non_finite_state(snapshot_file_name)
         state = self.get_current_state_dict(total_updates, sum_avg_psnr_err, sum_avg_ssim_err)
@@ -384,6 +414,8 @@ class BaseTrainingEnvironment(BaseVideoFillInEnvironment):
             for i, p in enumerate(p for group in optimizer.param_groups for p in group['params']):
                 named += [('%s.%d.%s' % (tag, i, k), optimizer.state[p][k]) for k in ('exp_avg', 'exp_avg_sq') if p in optimizer.state]
         named += [('u.' + k, u) for k, u in run_state.sn_vectors(disc).items() if u is not None]
+        if self.fused is not None:
+            named += self.fused.named_ema()
         return named
 
     def _refuse_non_finite_state(self, snapshot_file_name):
@@ -396,8 +428,17 @@ class BaseTrainingEnvironment(BaseVideoFillInEnvironment):
 
     def _step(self, which, module, optimizer):
         """``optimizer.step()``; with a guard, only when the gradients it is about to use are finite (clipped first, if asked)."""
-        if self.guard is None or self.guard.check(which, module.named_parameters()):
+        if self.fused is not None:
+            self.fused.step(which, last=which == 'D' or not hasattr(self, 'optimizer_D'))
+        elif self.guard is None or self.guard.check(which, module.named_parameters()):
             optimizer.step()
+
+    def sync_guard(self, agree=False):
+        """With a fused step: wait for the last launched update's verdict record and bring the guard's counters, norms and message up to
+        it; raises GuardGaveUp if the device has given up.  Called where the run waits anyway: a printed line, validation, ``save``.
+        ``agree``: every rank is here (a collective that checks that the ranks' counters are the same)."""
+        if self.fused is not None:
+            self.fused.read(wait=True, agree=agree)
 
     def _zero_grad(self, optimizer, reducer):
         """One process: the reference's ``optimizer.zero_grad()``.  Data parallel: gradients live in the reducer's flat
@@ -413,7 +454,7 @@ class BaseTrainingEnvironment(BaseVideoFillInEnvironment):
         self.loss_G.backward()
         self._reducer_G.allreduce_()
         self._step('G', self.generator, self.optimizer_G)
-        if self.guard is not None and not hasattr(self, 'optimizer_D'):
+        if self.guard is not None and self.fused is None and not hasattr(self, 'optimizer_D'):
             self.guard.end_update()
 
     def compute_loss_G(self):
@@ -456,7 +497,7 @@ class L2GDLDiscTrainingEnvironment(BaseTrainingEnvironment):
     def get_current_state_dict(self, total_updates, sum_avg_psnr_err, sum_avg_ssim_err):
         state = super().get_current_state_dict(total_updates, sum_avg_psnr_err, sum_avg_ssim_err)
         state['discriminator'] = self.discriminator.state_dict()
-        state['optimizer_D'] = self.optimizer_D.state_dict()
+        state['optimizer_D'] = self._optimizer_state_dict(self.optimizer_D)
         return state
 
     def _load_training_state(self, snapshot):
@@ -503,7 +544,7 @@ class L2GDLDiscTrainingEnvironment(BaseTrainingEnvironment):
         self.loss_D.backward()
         self._reducer_D.allreduce_()
         self._step('D', self.discriminator, self.optimizer_D)
-        if self.guard is not None:
+        if self.guard is not None and self.fused is None:
             self.guard.end_update()
 
     @staticmethod

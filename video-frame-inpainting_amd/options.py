@@ -119,6 +119,16 @@ class TrainOptions(BaseOptions):
         g.add_argument('--guard_patience', type=int, default=8, metavar='N',
                        help='(this build, with --guard) end the run with an error, writing no snapshot, after N consecutive updates in '
                             'which a step was skipped')
+        g.add_argument('--fused_step', action='store_true',
+                       help='(this build) both optimizers step through one HIP launch each (fused_step.py: tai_step_verdict + tai_fused_step): clip '
+                            'scaling, the Adam update and the weight average, on a verdict (ok / clipped / skipped) that stays on the device, so '
+                            'the host does not wait between backward() and the step; with --guard its counters live on the device and are read '
+                            'at printed lines, validation and saves.  The arithmetic is a written definition (include/tai_sepconv.h), close to '
+                            "but not bit-equal with torch.optim.Adam's.  Refuses --graph_step.  Off = optimizer.step() as before")
+        g.add_argument('--ema_decay', type=float, default=None, metavar='d',
+                       help="(this build, with --fused_step) keep an exponential moving average of the generator's weights, "
+                            'e <- e + (1 - d)(p - e) after every step, 0 < d < 1: snapshots gain generator_ema, validation scores the '
+                            'averaged weights and model_best.ckpt is chosen by them (predict.py --weights ema)')
         g.add_argument('--max_wall_minutes', type=float, default=None, metavar='M',
                        help='(this build, with --resumable) stop as after SIGTERM once the run has lasted M minutes')
         g.add_argument('--miopen_find_mode', type=str, default=None, choices=['NORMAL', 'FAST', 'HYBRID', 'DYNAMIC_HYBRID'],
@@ -145,6 +155,9 @@ class TestOptions(BaseOptions):
                        help='Flag to write intermediate predictions in addition to final ones')
         g.add_argument('--random_init', action='store_true',
                        help='(this build) skip the snapshot load and keep the seeded xavier initialisation')
+        g.add_argument('--weights', type=str, default='raw', choices=['raw', 'ema'],
+                       help="(this build) which weights of the snapshot to run: raw = its generator (default), ema = its generator_ema, "
+                            'the weight average a run with train.py --ema_decay keeps')
         g.add_argument('--conv_precision', type=str, default='fp32', choices=['fp32', 'bf16'],
                        help='(this build) precision of the inference convolutions: fp32 (default) or bf16 = opt-in: the layers with at '
                             'least 16 input and output channels and k in {3, 5, 7} take bf16 operands (rounded to nearest even), exact '

@@ -14,6 +14,9 @@ state digest that says whether two states are.
   guard        (only with train.py --guard) the guard's counters {'skipped_G', 'skipped_D', 'consecutive'} (grad_guard.GradGuard); they
                are the last entry of the digest's table then, and only then: a snapshot written without the guard loads with it (the
                counters start at zero) and the other way round, and digests of runs without the guard are what they were
+  ema          (only with train.py --ema_decay) the names of the generator parameters that carry an average, in table order; the averaged
+               values are the snapshot's ``generator_ema``, and they are the entries behind the guard's in the digest's table then, and
+               only then
 ``restore(env, run_state)`` puts all of it back, the generator states LAST, and returns this rank's 'data' entry.
 
 The digest (``tai_state_digest``, csrc/state_digest.hip.inc) reads every tensor of the state once, where it lives: about 0.5 GB of
@@ -200,13 +203,21 @@ def _guard_counters(env):
     return None if guard is None else guard.counters()
 
 
-def state_entries(env, data_state=None, guard_counters=_CURRENT):
+def _ema_entries(env):
+    fused = getattr(env, 'fused', None)
+    return list(fused.ema.values()) if fused is not None and fused.ema_decay is not None and fused.ema else None
+
+
+def state_entries(env, data_state=None, guard_counters=_CURRENT, ema=_CURRENT):
     """The digest's table for a training environment, in its fixed order: generator, discriminator (state-dict order), the two
     optimizers (per parameter: step, exp_avg, exp_avg_sq), the ``u`` vectors (None: an empty entry), then the generators -- the
     (K, T, F) stream, numpy's, torch's CPU and device generators -- and the clip order's position; with a guard (``env.guard``, or the
-    counters of a snapshot written with one) its three counters are one more entry behind them."""
+    counters of a snapshot written with one) its three counters are one more entry behind them; with a weight average (``env.fused``
+    with --ema_decay, or the averages of a snapshot written with one) its tensors are the last entries."""
     if guard_counters is _CURRENT:
         guard_counters = _guard_counters(env)
+    if ema is _CURRENT:
+        ema = _ema_entries(env)
     entries = [t.detach() for t in env.generator.state_dict().values()]
     disc = getattr(env, 'discriminator', None)
     if disc is not None:
@@ -224,6 +235,8 @@ def state_entries(env, data_state=None, guard_counters=_CURRENT):
     entries.append(bytes_entry(np.frombuffer(repr(data_state).encode(), dtype=np.uint8)))
     if guard_counters is not None:
         entries.append(np.array([guard_counters[k] for k in ('skipped_G', 'skipped_D', 'consecutive')], dtype='<i8').view(np.uint32))
+    if ema is not None:
+        entries += [e.detach() for e in ema]
     return [e.contiguous() if torch.is_tensor(e) else e for e in entries]
 
 
@@ -254,12 +267,12 @@ def _printable(state):
     return state
 
 
-def digest(env, data_state=_CURRENT, guard_counters=_CURRENT):
+def digest(env, data_state=_CURRENT, guard_counters=_CURRENT, ema=_CURRENT):
     """The 64-bit state digest of a training environment and of the clip order's position: the one train.py has attached
     (``env.data_state_source``), or ``data_state`` (a snapshot's, before train.py has positioned its clip order with it).
     ``guard_counters``: the guard entry of the table -- the environment's own guard by default, a snapshot's ``run_state.get('guard')``
-    when the digest that snapshot was saved with is recomputed."""
-    return digest_tensors(state_entries(env, _printable(_data_state(env) if data_state is _CURRENT else data_state), guard_counters))
+    when the digest that snapshot was saved with is recomputed; ``ema``: the same for the weight average's entries."""
+    return digest_tensors(state_entries(env, _printable(_data_state(env) if data_state is _CURRENT else data_state), guard_counters, ema))
 
 
 def _gather(entry):
@@ -288,6 +301,8 @@ def capture(env):
              'digest': ranks[0]['digest']}
     if _guard_counters(env) is not None:
         state['guard'] = _guard_counters(env)
+    if _ema_entries(env) is not None:
+        state['ema'] = list(env.fused.ema)
     return state
 
 

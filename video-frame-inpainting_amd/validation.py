@@ -6,7 +6,8 @@ Every ``--validate_freq`` updates up to three legs run, each on its own clip sou
   'altT' (K, alt_T, F)      on --val_video_list_alt_T_path
   'altKF'(alt_K, T, alt_F)  on --val_video_list_alt_K_F_path
 A leg runs when its source and the alt values it uses are given; ``--val_synthetic N`` replaces the lists by N seeded synthetic
-clips (seed ``--seed`` + VAL_SEED_OFFSET: never the training clips).  Each leg runs the current weights without gradients
+clips (seed ``--seed`` + VAL_SEED_OFFSET: never the training clips).  Each leg runs the current weights (with ``--ema_decay``: the
+averaged weights, exchanged into the parameters for the leg and out again; the line then ends with ``weights=ema``) without gradients
 (``env.eval()`` + ``env.forward_test()``) and scores the frames with ``metrics.compute_errors_device``.  Only the first leg decides the
 best snapshot: ``sum(mean(ssim, axis=0))`` strictly above the best so far saves ``model_best.ckpt``.
 
@@ -18,7 +19,7 @@ import time
 import numpy as np
 import torch
 
-from . import clip_pipeline, metrics, parallel, synthetic
+from . import clip_pipeline, fused_step, metrics, parallel, synthetic
 
 VAL_SEED_OFFSET = 104729          # validation clips: --seed + this (training clips use --seed + rank)
 
@@ -126,15 +127,19 @@ class Validator(object):
     def validate(self, env, total_updates, log=print):
         """All legs; saves model_best.ckpt when the first leg improves.  -> {leg name: (psnr, ssim, l2)}."""
         results = {}
+        if getattr(env, 'sync_guard', None) is not None:
+            env.sync_guard(agree=True)         # a fused step's verdicts: read before anything is scored or saved
         for i, leg in enumerate(self.legs):
             t0 = time.time()
-            psnr, ssim, l2 = run_leg(env, leg, self.opt, cache=self._clips)
+            # with a weight average (train.py --ema_decay) the averaged weights are the ones scored, and model_best.ckpt is chosen by them
+            with fused_step.averaged_weights(env) as scored:
+                psnr, ssim, l2 = run_leg(env, leg, self.opt, cache=self._clips)
             results[leg.name] = (psnr, ssim, l2)
             if parallel.rank() == 0:
                 log('Validation (T=%d) done. Took %.03f minutes' % (leg.T, (time.time() - t0) / 60))
-                log('val %s (K,T,F)=(%d,%d,%d) clips=%d psnr=%.5f ssim=%.5f l2=%.6f sum_avg_psnr=%r sum_avg_ssim=%r'
+                log('val %s (K,T,F)=(%d,%d,%d) clips=%d psnr=%.5f ssim=%.5f l2=%.6f sum_avg_psnr=%r sum_avg_ssim=%r%s'
                     % (leg.name, leg.K, leg.T, leg.F, psnr.shape[0], float(np.mean(psnr)), float(np.mean(ssim)),
-                       float(np.mean(l2)), sum_avg(psnr), sum_avg(ssim)))
+                       float(np.mean(l2)), sum_avg(psnr), sum_avg(ssim), ' weights=ema' if scored.active else ''))
             if i == 0:
                 self.best, improved = update_best(self.best, sum_avg(psnr), sum_avg(ssim))
                 if improved:
