@@ -49,7 +49,10 @@ int tai_sepconv_forward(const float* input, const float* vertical, const float* 
 
 /* Backward (all three gradients, in the reference's V, H, I order):
  * replaces SeparableConvolution_cuda_backward (SeparableConvolution_cuda.h:9-18).
- * Any of grad_input / grad_vertical / grad_horizontal may be NULL to skip that gradient. */
+ * Any of grad_input / grad_vertical / grad_horizontal may be NULL to skip that gradient.
+ * Precondition: every operand is finite.  The grad_input strips kernel lets window positions outside a source row hold
+ * other rows' values and cancels them by multiplying with a zero tap (csrc/sepconv_bwd.hip.inc: they hold finite values
+ * and meet S = 0); an Inf or NaN there would reach gradients it does not belong to. */
 int tai_sepconv_backward(const float* grad_output, const float* input, const float* vertical,
                          const float* horizontal, float* grad_input, float* grad_vertical,
                          float* grad_horizontal, int B, int C, int H, int W, int ks,
@@ -358,8 +361,9 @@ int tai_sepconv_default_forward_variant(int C, int W, int ks);
  * Returns the previous value. */
 int tai_sepconv_set_grad_input_variant(int variant);
 
-/* grad_vertical / grad_horizontal kernels: 0 = automatic (one fused launch of the hand-scheduled wave types when C == 1
- * and both are requested; the gV waves' tap loads issued at kernel entry, the patch staged by the gH waves through LDS-DMA),
+/* grad_vertical / grad_horizontal kernels: 0 = automatic (one fused launch of the hand-scheduled wave types when C == 1;
+ * the gV waves' tap loads issued at kernel entry, the patch staged by the gH waves through LDS-DMA; with only one of the two
+ * requested the other's waves leave early, so a gradient has the same bits whatever else was asked for),
  * 1 = the two separate HIP kernels, 2 = the fused launch with the patch staged behind a workgroup barrier first (round 2's
  * form, A/B), 3 / 4 = as 0 with the gV waves at priority 0 / 2 instead of their gH partners' 1 (A/B; the results are the same
  * bits).  Returns the previous value. */

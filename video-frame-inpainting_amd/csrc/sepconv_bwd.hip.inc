@@ -190,6 +190,8 @@ void sepconv_grad_h_tiled(const float* __restrict__ gO, const float* __restrict_
 // four gH waves alone (LDS-DMA) and announced through an LDS counter that every wave polls before its first patch read; no
 // workgroup barrier stands between a gV wave and its tap loads.
 // GVP: priority of the gV waves in their row loop (0: never set; the gH waves sit at 1).
+// Either output may be null: its four waves then leave before their row loop (the gH waves still stage the patch), so a
+// gradient carries the same bits whether or not the other one was requested.
 template <bool EARLY, int GVP = 0>
 __global__ __launch_bounds__(512, 2)
 void sepconv_grad_vh_ab(const float* __restrict__ gO, const float* __restrict__ in, const float* __restrict__ vt,
@@ -242,6 +244,7 @@ void sepconv_grad_vh_ab(const float* __restrict__ gO, const float* __restrict__ 
         __syncthreads();
     }
 
+    if (is_gh ? gH == nullptr : gV == nullptr) return;       // wave-uniform; no workgroup barrier follows
     if (is_gh) {
         const float* vb = vt + ((size_t)b * KS) * plane;
         const unsigned ring_m0 = PATCH_BYTES + __builtin_amdgcn_readfirstlane(wave) * (TAI_FWD_ROWLOOP_RING_SLOTS * 1024);

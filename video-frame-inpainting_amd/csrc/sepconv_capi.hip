@@ -1410,7 +1410,9 @@ int tai_sepconv_backward(const float* grad_output, const float* input, const flo
         const int tiles_x = (W + fwd::TILE_W - 1) / fwd::TILE_W, tiles_y = (H + bwd::gi2::R - 1) / bwd::gi2::R;
         const long long slab_bytes = (long long)B * tiles_x * tiles_y * C * bwd::gi2::SLAB * (long long)sizeof(float);
         float* scratch = grad_vertical ? grad_vertical : grad_horizontal;
-        if (slab_bytes > (long long)B * ks * H * W * (long long)sizeof(float)) scratch = nullptr;   // cannot happen for ks = 51
+        // A slab is gi2::SLAB = 10,800 floats per tile and channel against 51 H W floats of tap gradient per sample: small planes
+        // (below ~212 pixels per tile and channel, e.g. [1,1,2,104] or [1,3,5,124]) do not hold them and flush with atomics instead.
+        if (slab_bytes > (long long)B * ks * H * W * (long long)sizeof(float)) scratch = nullptr;
         const size_t lds = (size_t)bwd::gi2::LDS_FLOATS * sizeof(float);
         const dim3 grid(B * tiles_x * tiles_y), block(512);
         float* dst = scratch ? scratch : grad_input;
@@ -1441,8 +1443,9 @@ int tai_sepconv_backward(const float* grad_output, const float* input, const flo
         gi_done = true;
     }
 
-    if (tileable && C == 1 && grad_vertical && grad_horizontal && g_vh_variant.load(std::memory_order_relaxed) != 1) {
-        // both tap gradients of a single-channel frame in one launch of the hand-scheduled wave types
+    if (tileable && C == 1 && (grad_vertical || grad_horizontal) && g_vh_variant.load(std::memory_order_relaxed) != 1) {
+        // the tap gradients of a single-channel frame in one launch of the hand-scheduled wave types; requested alone, a gradient
+        // runs on the same waves (the other four leave early), so its bits do not depend on what else was asked for
         const int tiles_x = (W + fwd::TILE_W - 1) / fwd::TILE_W, tiles_y = (H + 7) / 8;
         const size_t patch = (size_t)(8 + 50) * 180 * sizeof(float);
         const size_t lds = ((patch + 1023) & ~(size_t)1023) + (size_t)8 * TAI_FWD_ROWLOOP_RING_SLOTS * 1024;
