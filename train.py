@@ -24,6 +24,9 @@ made on the device from the gradient statistics, so the host no longer waits bet
 are read where the run waits anyway (a printed line, validation, a save).  With ``--ema_decay`` an average of the generator's weights is
 kept, validated, and saved as ``generator_ema`` (``predict.py --weights ema``).
 
+``--ssim_weight G``: the generator's loss gains G (1 - mean SSIM) of each prediction against the ground truth (losses.SSIMLoss: one HIP
+launch writes the loss and its gradient); printed lines gain ``G_ssim=`` (and ``G_ssim_forward= G_ssim_backward=`` for TAI).  0 = off.
+
   python train.py --name demo --K 5 --T 5 --F 5 --c_dim 1 --image_size 128 --batch_size 4 --model_key TAI_gray \
       --max_iter 10 --synthetic 64
 """
@@ -53,6 +56,8 @@ def main(args=None):
         raise SystemExit('--ema_decay needs --fused_step: the average is kept by the fused optimizer step')
     if opt.ema_decay is not None and not 0.0 < opt.ema_decay < 1.0:
         raise SystemExit('--ema_decay must lie strictly between 0 and 1, found %r' % opt.ema_decay)
+    if not opt.ssim_weight >= 0.0:
+        raise SystemExit('--ssim_weight must not be negative, found %r' % opt.ssim_weight)
     if not opt.resumable:
         return _run(opt, None)
     if opt.graph_step and GRAPH_STEP_REFUSAL:
@@ -131,7 +136,7 @@ def _run(opt, stop):
                                       opt.image_size, opt.alpha, opt.beta, opt.lr, opt.beta1, opt.df_dim, opt.Ip,
                                       opt.disc_window_size, opt.padding_size, device=device,
                                       graph_step=opt.graph_step, resumable=resumable, guard=guard, fused_step=opt.fused_step,
-                                      ema_decay=opt.ema_decay, max_iter=opt.max_iter)
+                                      ema_decay=opt.ema_decay, max_iter=opt.max_iter, ssim_weight=opt.ssim_weight)
     env.sync_replicas()
     total_updates = env.start_update
     # a resumed run starts from the best values its snapshot carries (train.py:96-97)

@@ -281,7 +281,11 @@ def lib():
     L.tai_frame_metrics_workspace_bytes.restype = ctypes.c_longlong
     L.tai_frame_metrics.argtypes = [P, P, P, P, P, P, I, I, I, I, V]
     L.tai_frame_metrics.restype = I
-    L.tai_clip_from_frames.argtypes = [P, ctypes.c_longlong, P, P, P, P, I, I, I, I, I, I, V]
+    L.tai_ssim_loss_workspace_bytes.argtypes = [I] * 4
+    L.tai_ssim_loss_workspace_bytes.restype = ctypes.c_longlong
+    L.tai_ssim_loss.argtypes = [P, P, P, P, P, P, I, I, I, I, V]
+    L.tai_ssim_loss.restype = I
+    L.tai_clip_from_frames.argtypes =[P, ctypes.c_longlong, P, P, P, P, I, I, I, I, I, I, V]
     L.tai_clip_from_frames.restype = I
     L.tai_frames_to_uint8.argtypes = [P, P, I, I, I, I, I, I, I, V]
     L.tai_frames_to_uint8.restype = I

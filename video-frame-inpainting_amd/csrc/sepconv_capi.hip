@@ -28,6 +28,7 @@
 #include "spectral_norm.hip.inc"
 #include "hbm_probe.hip.inc"
 #include "frame_metrics.hip.inc"
+#include "ssim_loss.hip.inc"
 #include "clip_pipeline.hip.inc"
 #include "state_digest.hip.inc"
 #include "grad_stats.hip.inc"
@@ -1629,6 +1630,41 @@ int tai_frame_metrics(const float* pred, const float* gt, long long* sse, double
     hipLaunchKernelGGL(fmetrics::finish, dim3((unsigned)((N + 63) / 64)), dim3(64), 0, s, part_ssim, part_l2, part_sse, sse, ssim, l2, N, C, H,
                        W, pl.nby * pl.nbx);
     return check_launch("frame_metrics finish");
+}
+
+long long tai_ssim_loss_workspace_bytes(int N, int C, int H, int W) {
+    if (N <= 0 || C <= 0 || H < 7 || W < 7) return TAI_SEPCONV_EINVAL;
+    if ((long long)N * C * H * W >= (1LL << 40) || (long long)H * W >= (1LL << 31)) return TAI_SEPCONV_EINVAL;
+    const ssimloss::Plan pl = ssimloss::plan(N, C, H, W);
+    if (pl.tiles_total >= (1LL << 31)) return TAI_SEPCONV_EINVAL;
+    return pl.tiles_total * (long long)sizeof(double);
+}
+
+int tai_ssim_loss(const float* pred, const float* gt, double* plane_ssim, double* totals, float* grad, void* workspace, int N, int C,
+                  int H, int W, void* hip_stream) {
+    g_err[0] = 0;
+    if (!pred || !gt || !plane_ssim || !totals || !workspace) return fail(TAI_SEPCONV_EINVAL, "%s", "ssim_loss: null pointer");
+    if (N <= 0 || C <= 0 || H < 7 || W < 7)
+        return fail(TAI_SEPCONV_EINVAL, "%s", "ssim_loss: needs N, C >= 1 and H, W >= 7 (the 7x7 SSIM window)");
+    if ((long long)N * C * H * W >= (1LL << 40) || (long long)H * W >= (1LL << 31))
+        return fail(TAI_SEPCONV_EINVAL, "%s", "ssim_loss: tensor too large");
+    if (reinterpret_cast<uintptr_t>(workspace) % 8 != 0 || reinterpret_cast<uintptr_t>(plane_ssim) % 8 != 0 ||
+        reinterpret_cast<uintptr_t>(totals) % 8 != 0)
+        return fail(TAI_SEPCONV_EINVAL, "%s", "ssim_loss: workspace, plane_ssim and totals must be 8-byte aligned");
+    const ssimloss::Plan pl = ssimloss::plan(N, C, H, W);
+    if (pl.tiles_total >= (1LL << 31)) return fail(TAI_SEPCONV_EINVAL, "%s", "ssim_loss: too many tiles (2^31 or more)");
+    const int planes = N * C;       // below 2^31: every plane has at least one tile
+    double* part = static_cast<double*>(workspace);
+    const double divisor = ((double)N * (double)C) * ((double)(H - 6) * (double)(W - 6));
+    hipStream_t s = static_cast<hipStream_t>(hip_stream);
+    hipLaunchKernelGGL(ssimloss::tile_loss_grad, dim3((unsigned)pl.tiles_total), dim3(ssimloss::THREADS), 0, s, pred, gt, part, grad, H, W,
+                       pl.nby, pl.nbx, divisor);
+    if (int rc = check_launch("ssim_loss tile_loss_grad")) return rc;
+    hipLaunchKernelGGL(ssimloss::finish_planes, dim3((unsigned)((planes + ssimloss::THREADS - 1) / ssimloss::THREADS)), dim3(ssimloss::THREADS),
+                       0, s, part, plane_ssim, planes, pl.nby * pl.nbx, H, W);
+    if (int rc = check_launch("ssim_loss finish_planes")) return rc;
+    hipLaunchKernelGGL(ssimloss::finish_total, dim3(1), dim3(ssimloss::THREADS), 0, s, plane_ssim, totals, planes);
+    return check_launch("ssim_loss finish_total");
 }
 
 int tai_clip_from_frames(const unsigned char* frames, long long frames_bytes, const long long* table, const long long* table_host,

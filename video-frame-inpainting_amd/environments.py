@@ -23,7 +23,7 @@ import torch
 from . import conv_ops, parallel, run_state
 from . import fused_step as fused_step_module
 from .graph import GraphedForward
-from .losses import GDL
+from .losses import GDL, SSIMLoss
 from .mcnet import MCNetFillInModel
 from .sn_discriminator import SNDiscriminator
 from .ablations import (BidirectionalSimpleAverageFillInModel, BidirectionalTimeWeightedAverageFillInModel,
@@ -45,7 +45,9 @@ def create_eval_environment(fill_in_model, checkpoints_dir, name, snapshot_file_
 
 def create_training_environment(fill_in_model, c_dim, checkpoints_dir, name, max_K, max_T, max_F, image_size, alpha,
                                 beta, lr, beta1, df_dim, Ip, disc_window_size, padding_size, device=None, graph_step=False,
-                                resumable=False, guard=None, fused_step=False, ema_decay=None, max_iter=100000):
+                                resumable=False, guard=None, fused_step=False, ema_decay=None, max_iter=100000, ssim_weight=0.0):
+    if not ssim_weight >= 0.0:
+        raise ValueError('ssim_weight must not be negative, found %r' % (ssim_weight,))
     if guard is not None and graph_step:
         raise ValueError('a guarded update cannot be a captured one: a replayed update cannot leave out an optimizer step')
     if fused_step and graph_step:
@@ -58,11 +60,11 @@ def create_training_environment(fill_in_model, c_dim, checkpoints_dir, name, max
         env = TAITrainingEnvironment(      # environments.py:29-31
             fill_in_model, checkpoints_dir, name, image_size, c_dim, alpha, beta, lr, beta1,
                                      df_dim, Ip, disc_window_size, max_K, max_T, max_F, padding_size, device=device,
-                                     graph_step=graph_step)
+                                     graph_step=graph_step, ssim_weight=ssim_weight)
     elif isinstance(fill_in_model, MCNetFillInModel):
         env = MCNetTrainingEnvironment(fill_in_model, checkpoints_dir, name, image_size, c_dim, alpha, beta, lr, beta1,
                                        df_dim, Ip, disc_window_size, max_K, max_T, max_F, padding_size, device=device,
-                                       graph_step=graph_step)
+                                       graph_step=graph_step, ssim_weight=ssim_weight)
     else:
         raise RuntimeError('Tried to create a training environment for object of unsupported type %s'
                            % type(fill_in_model).__name__)
@@ -262,7 +264,7 @@ class BaseTrainingEnvironment(BaseVideoFillInEnvironment):
 
     # attributes an update produces (tensors of the captured graph's pool when the update is replayed)
     _STEP_OUTPUTS = ('gen_output', 'loss_G', 'Lp', 'gdl', 'L_GAN', 'loss_d_fake', 'loss_d_real', 'loss_D', 'Lp_forward',
-                     'Lp_backward', 'gdl_forward', 'gdl_backward')
+                     'Lp_backward', 'gdl_forward', 'gdl_backward', 'ssim', 'ssim_forward', 'ssim_backward')
 
     def train_step(self, preceding_frames, following_frames, gt_middle_frames):
         """One update on a batch: set_train_inputs + forward_train + optimize_parameters (src/train.py:147-169), with
@@ -472,9 +474,13 @@ class L2GDLDiscTrainingEnvironment(BaseTrainingEnvironment):
     loss_D = BCE(D(fake.detach()), window labels) + BCE(D(real), 1)."""
 
     def __init__(self, fill_in_model, checkpoints_dir, name, image_size, c_dim, alpha, beta, lr, beta1, df_dim, Ip,
-                 disc_t, max_K, max_T, max_F, padding_size, device=None, graph_step=False):
+                 disc_t, max_K, max_T, max_F, padding_size, device=None, graph_step=False, ssim_weight=0.0):
         super().__init__(fill_in_model, checkpoints_dir, name, lr, beta1, max_K, max_T, max_F, padding_size, device=device,
                          graph_step=graph_step)
+        # ssim_weight (train.py --ssim_weight G) > 0: loss_G gains G (1 - mean SSIM) per prediction (losses.SSIMLoss, one HIP launch for
+        # the loss and its gradient); 0 = the reference's loss: no module, no launch, no extra key in get_current_errors
+        self.ssim_weight = float(ssim_weight)
+        self.loss_ssim = SSIMLoss() if self.ssim_weight > 0 else None
         self._fake_labels = {}
         self.loss_Lp = torch.nn.MSELoss()
         self.loss_gdl = GDL()
@@ -567,12 +573,18 @@ class L2GDLDiscTrainingEnvironment(BaseTrainingEnvironment):
             h = self.discriminator(fake)
         self.L_GAN = self.loss_d(h, torch.ones_like(h))
         self.loss_G = self.loss_G + self.alpha * (self.Lp + self.gdl) + self.beta * self.L_GAN
+        if self.loss_ssim is not None:
+            # on the model's own [B, T, C, H, W] layout: the mean over planes does not care about their order
+            self.ssim = self.loss_ssim(self.gen_output['pred'], self.gt_middle_frames)
+            self.loss_G = self.loss_G + self.ssim_weight * self.ssim
 
     def get_current_errors(self):
         d = super().get_current_errors()
         d.update({'G_Lp': float(self.Lp.item()), 'G_gdl': float(self.gdl.item()),
                   'D_real': float(self.loss_d_real.item()), 'D_fake': float(self.loss_d_fake.item()),
                   'G_GAN': float(self.L_GAN.item())})
+        if self.loss_ssim is not None:
+            d['G_ssim'] = float(self.ssim.item())
         return d
 
     def train(self):
@@ -609,9 +621,15 @@ class TAITrainingEnvironment(L2GDLDiscTrainingEnvironment):
         self.gdl_forward = self.loss_gdl(out_f, gt)
         self.gdl_backward = self.loss_gdl(out_b, gt)
         self.loss_G = self.loss_G + self.alpha * (self.Lp_forward + self.Lp_backward + self.gdl_forward + self.gdl_backward)
+        if self.loss_ssim is not None:
+            self.ssim_forward = self.loss_ssim(self.gen_output['pred_forward'], self.gt_middle_frames)
+            self.ssim_backward = self.loss_ssim(self.gen_output['pred_backward'], self.gt_middle_frames)
+            self.loss_G = self.loss_G + self.ssim_weight * (self.ssim_forward + self.ssim_backward)
 
     def get_current_errors(self):
         d = super().get_current_errors()
         d.update({'G_Lp_forward': float(self.Lp_forward.item()), 'G_gdl_forward': float(self.gdl_forward.item()),
                   'G_Lp_backward': float(self.Lp_backward.item()), 'G_gdl_backward': float(self.gdl_backward.item())})
+        if self.loss_ssim is not None:
+            d.update({'G_ssim_forward': float(self.ssim_forward.item()), 'G_ssim_backward': float(self.ssim_backward.item())})
         return d

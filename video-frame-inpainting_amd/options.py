@@ -129,6 +129,11 @@ class TrainOptions(BaseOptions):
                        help="(this build, with --fused_step) keep an exponential moving average of the generator's weights, "
                             'e <- e + (1 - d)(p - e) after every step, 0 < d < 1: snapshots gain generator_ema, validation scores the '
                             'averaged weights and model_best.ckpt is chosen by them (predict.py --weights ema)')
+        g.add_argument('--ssim_weight', type=float, default=0.0, metavar='G',
+                       help="(this build) add G (1 - mean SSIM) of every prediction against the ground truth to the generator's loss "
+                            '(losses.SSIMLoss: 7x7 window, float frames in [0, 1] with L = 1, unclipped, float64 window arithmetic; loss and '
+                            'gradient from one HIP launch, tai_ssim_loss); printed lines gain G_ssim= (TAI: G_ssim_forward= G_ssim_backward= '
+                            'as well).  0 (default) = the loss as before: nothing is launched, no key is added')
         g.add_argument('--max_wall_minutes', type=float, default=None, metavar='M',
                        help='(this build, with --resumable) stop as after SIGTERM once the run has lasted M minutes')
         g.add_argument('--miopen_find_mode', type=str, default=None, choices=['NORMAL', 'FAST', 'HYBRID', 'DYNAMIC_HYBRID'],
