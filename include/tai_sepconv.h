@@ -349,6 +349,18 @@ int tai_conv3x3_wino_timeline_skip(int level);
 int tai_sepconv_set_forward_variant(int variant);
 /* The variant `0 = automatic` resolves to for a frame of C channels, width W and filter size ks. */
 int tai_sepconv_default_forward_variant(int C, int W, int ks);
+/* The kernel tai_sepconv_forward would launch for this shape on the current device if `variant` were selected (0 = automatic),
+ * as the variant number of the kernel that runs the leading channels.  It is the launcher's own decision, not a restatement:
+ * tai_sepconv_forward switches on the value this returns.
+ *   1 = the generic kernel;  18 = a persistent request (20-27, or the automatic choice for C == 1) that does not run persistent:
+ *   C != 1, a tile count B * ceil(W / 128) * ceil(H / 16) that is no multiple of 8, at most one tile per workgroup when the
+ *   choice was automatic, a tap tensor of 2^32 bytes or more, or a device of fewer than 8 CUs;  21-27 = the persistent kernel with
+ *   that concrete policy (20 and the automatic choice resolve by tap footprint to 21 or 26);  17 / 19 = the three-channel kernels
+ *   when C >= 3 (channels beyond a multiple of three then run on kernel 16), 16 when C < 3;  any other selectable variant = itself.
+ * Negative (TAI_SEPCONV_EINVAL, message in tai_sepconv_last_error) for what tai_sepconv_forward refuses for its dimensions or
+ * variant: non-positive or too large dimensions, a tiled variant with ks != 51 or W % 4 != 0, an unknown variant.  Launches
+ * nothing; reads the CU count of the current device (a host without one answers as for a device of 0 CUs). */
+int tai_sepconv_forward_route(int B, int C, int H, int W, int ks, int variant);
 
 /* grad_input kernel of tai_sepconv_backward:
  *   0 = automatic: wave-private accumulation strips + fixed-order slab sum when ks == 51, W % 4 == 0, C in {1, 3} --

@@ -80,8 +80,11 @@ def test_every_forward_variant(variant, C):
 @pytest.mark.parametrize('B,H,W', [(2, 40, 256), (1, 16, 132), (3, 16, 128), (1, 24, 4)])
 def test_mixed_wave_kernels_on_ragged_tiles_and_patch_edges(variant, B, H, W):
     """The A/B kernels on several column tiles, a ragged last row tile and a narrow last column tile; delta taps at
-    (50, 50) read the LAST two columns and rows of the padded frame (kernel 18 stages those two columns separately)."""
+    (50, 50) read the LAST two columns and rows of the padded frame (kernel 18 stages those two columns separately).
+    Variant 20 resolves to kernel 18 at all four shapes: they have 12, 2, 3 and 2 tiles, none a multiple of 8, so the
+    persistent kernel does not run even when asked for by number (its ragged planes: tests/test_gpu_sepconv_forward.py)."""
     ks = 51
+    assert _native.lib().tai_sepconv_forward_route(B, 1, H, W, ks, variant) == (18 if variant == 20 else variant)
     inp, v, h, _ = _case(B, 1, H, W, ks, 17)
     prev = sc.set_forward_variant(variant)
     try:

@@ -261,6 +261,8 @@ def lib():
     L.tai_sepconv_set_forward_variant.restype = I
     L.tai_sepconv_default_forward_variant.argtypes = [I, I, I]
     L.tai_sepconv_default_forward_variant.restype = I
+    L.tai_sepconv_forward_route.argtypes = [I] * 6
+    L.tai_sepconv_forward_route.restype = I
     L.tai_sepconv_set_grad_taps_variant.argtypes = [I]
     L.tai_sepconv_set_grad_taps_variant.restype = I
     L.tai_sepconv_set_grad_input_variant.argtypes = [I]

@@ -166,24 +166,36 @@ static int device_cu_count() {
     return cached_cus;
 }
 
-// kernel 20: one persistent workgroup per CU over the tiles of a single-channel frame batch; falls back to kernel 18 when there
+// kernel 20: one persistent workgroup per CU over the tiles of a single-channel frame batch; kernel 18 runs instead when there
 // is at most one tile per CU (nothing to overlap) or the tile count is not a multiple of 8 (the XCD-contiguous tile order)
 // POLICY: 0 = by footprint (nt loads and the reversed tile walk when the two tap tensors together exceed the Infinity Cache:
 // every tap byte is read once and none of it will be there for anybody else), 1 = default cache policy, forward walk (round 3's
-// kernel 20), 2 = nt, forward walk, 3 = nt, reversed walk, 4 = default cache policy, reversed walk.
+// kernel 20), 2 = nt, forward walk, 3 = nt, reversed walk, 4 = default cache policy, reversed walk, 5 / 6 / 7 = as 3 with the
+// type-A waves at constant priority 0 / 1 / 2.
+// THE decision (forward_route below, and through it tai_sepconv_forward and tai_sepconv_forward_route): the concrete policy 1-7
+// the persistent kernel runs with on the current device, or 0 when the launch goes to kernel 18.
+int persistent_policy(int B, int C, int H, int W, bool force, int policy) {
+    const int tiles_x = (W + fwd::TILE_W - 1) / fwd::TILE_W, tiles_y = (H + 15) / 16;
+    const int ntiles = B * tiles_x * tiles_y;
+    const int cus = device_cu_count();
+    const int grid = cus > 0 ? (cus / 8) * 8 : 0;
+    if (C != 1 || grid < 8 || ntiles % 8 != 0 || (!force && ntiles <= grid) || (long long)B * 51 * H * W * 4 > 0xffffffffLL)
+        return 0;
+    if (policy == 0) policy = (2LL * B * 51 * H * W * 4 > (256LL << 20)) ? 6 : 1;
+    return policy;
+}
+
+// the persistent launch itself, with a concrete policy from persistent_policy (which has checked C == 1, the tile count and the
+// 32-bit tap offsets)
 template <int DBG = 0>
-int fwd_persistent(const float* in, const float* v, const float* h, float* out, int B, int C, int H, int W, hipStream_t s, bool force,
-                   int policy = 0) {
+int launch_persistent(const float* in, const float* v, const float* h, float* out, int B, int H, int W, hipStream_t s, int policy) {
     const int tiles_x = (W + fwd::TILE_W - 1) / fwd::TILE_W, tiles_y = (H + 15) / 16;
     const int ntiles = B * tiles_x * tiles_y;
     const int cus = device_cu_count();
     int grid = cus > 0 ? (cus / 8) * 8 : 0;
-    if (C != 1 || grid < 8 || ntiles % 8 != 0 || (!force && ntiles <= grid) || (long long)B * 51 * H * W * 4 > 0xffffffffLL)
-        return fwd_ab_all_channels<5>(in, v, h, out, B, C, H, W, s);
     if (grid > ntiles) grid = ntiles;
     const size_t patch = ((size_t)(16 + 50) * 180 * sizeof(float) + 1023) & ~(size_t)1023;
     const size_t lds = 2 * patch + (size_t)8 * TAI_FWD_ROWLOOP_RING_SLOTS * 1024 + 16;
-    if (policy == 0) policy = (2LL * B * 51 * H * W * 4 > (256LL << 20)) ? 6 : 1;
 #define TAI_LAUNCH_PERSISTENT(NT, REV, APRIO)                                                                        \
     {                                                                                                               \
         auto kern = fwd::sepconv_forward_persistent<DBG, NT, REV, APRIO>;                                           \
@@ -199,6 +211,39 @@ int fwd_persistent(const float* in, const float* v, const float* h, float* out, 
     else TAI_LAUNCH_PERSISTENT(false, false, -1)
 #undef TAI_LAUNCH_PERSISTENT
     return check_launch("sepconv_forward_persistent");
+}
+
+#ifdef TAI_TIMING_VARIANTS
+// the persistent kernel with time stamps (tools build): forced, same decision, kernel 18 (without stamps) where it does not run
+int fwd_persistent_stamped(const float* in, const float* v, const float* h, float* out, int B, int C, int H, int W, hipStream_t s,
+                           int policy) {
+    const int p = persistent_policy(B, C, H, W, true, policy);
+    return p ? launch_persistent<1>(in, v, h, out, B, H, W, s, p) : fwd_ab_all_channels<5>(in, v, h, out, B, C, H, W, s);
+}
+#endif
+
+// What tai_sepconv_forward runs for a REQUESTED variant (0 = automatic) on the current device: the variant number of the kernel
+// of the leading channels, or a negative error code with the message set.  tai_sepconv_forward switches on this value and
+// tai_sepconv_forward_route returns it: there is no second copy of these conditions.
+int forward_route(int B, int C, int H, int W, int ks, int requested) {
+    if (!dims_ok(B, C, H, W, ks)) return fail(TAI_SEPCONV_EINVAL, "%s", "bad dimensions");
+    const bool tileable = (ks == 51) && (W % 4 == 0);
+    // default: mixed type-A / type-B hand-scheduled kernel for single-channel frames; three channel patches per tap row otherwise
+    const int variant = requested == 0 ? tai_sepconv_default_forward_variant(C, W, ks) : requested;
+    if (variant != 1 && !tileable)
+        return fail(TAI_SEPCONV_EINVAL, "%s", "tiled forward variants need ks == 51 and W % 4 == 0");
+    if (variant >= 20 && variant <= 27) {
+        // 20: by footprint, persistent at any tile count only when asked for by number; 21-27: that policy, at any tile count
+        const int policy = persistent_policy(B, C, H, W, requested != 0, variant - 20);
+        return policy ? 20 + policy : 18;
+    }
+    if (variant == 17 || variant == 19) return C >= 3 ? variant : 16;      // no channel triple: every channel on kernel 16
+    const bool known = (variant >= 1 && variant <= 16) || variant == 18;
+#ifdef TAI_TIMING_VARIANTS
+    if (variant >= 101 && variant <= 127) return variant;                   // (the switch refuses the numbers that do not exist)
+#endif
+    if (!known) return fail(TAI_SEPCONV_EINVAL, "%s", "unknown forward variant (values >= 100 exist only in the tools build, -DTAI_TIMING_VARIANTS)");
+    return variant;
 }
 
 template <int WAVES>
@@ -286,7 +331,7 @@ int launch_grad_vh_tiled(const float* gO, const float* in, const float* v, const
 
 extern "C" {
 
-int tai_sepconv_version(void) { return 800; }     // 0.7.0: gradient statistics and scaling over a table of tensors (tai_grad_stats, tai_grad_scale), no other kernel changed; (0.6.0: (tai_state_digest added at the same number: an entry point of its own, and the committed counter summaries are tied to it); clip pipeline entry points (tai_clip_from_frames, tai_frames_to_uint8), no other kernel changed; (0.5.0: F(4x4, 3x3) chunk loop as generated assembly, displaced-read blocks, any C; (0.4.1: persistent forward kernel beyond the Infinity Cache: type-A waves at their partners' priority (0.4.0: nt tap loads + reversed walk; source hash))))
+int tai_sepconv_version(void) { return 810; }     // 0.8.1: tai_sepconv_forward_route (host code: the launcher's decision as a query), no kernel changed; (0.7.0: gradient statistics and scaling over a table of tensors (tai_grad_stats, tai_grad_scale), no other kernel changed; (0.6.0: (tai_state_digest added at the same number: an entry point of its own, and the committed counter summaries are tied to it); clip pipeline entry points (tai_clip_from_frames, tai_frames_to_uint8), no other kernel changed; (0.5.0: F(4x4, 3x3) chunk loop as generated assembly, displaced-read blocks, any C; (0.4.1: persistent forward kernel beyond the Infinity Cache: type-A waves at their partners' priority (0.4.0: nt tap loads + reversed walk; source hash)))))
 
 const char* tai_sepconv_last_error(void) { return g_err; }
 
@@ -309,6 +354,11 @@ int tai_sepconv_default_forward_variant(int C, int W, int ks) {
     return !tileable ? 1 : (C == 1 ? 20 : 19);
 }
 
+int tai_sepconv_forward_route(int B, int C, int H, int W, int ks, int variant) {
+    g_err[0] = 0;
+    return forward_route(B, C, H, W, ks, variant);
+}
+
 long long tai_sepconv_forward_bytes(int B, int C, int H, int W, int ks) {
     const long long Hp = H + ks - 1, Wp = W + ks - 1;
     return 4LL * ((long long)B * C * Hp * Wp + 2LL * B * ks * H * W + (long long)B * C * H * W);
@@ -323,16 +373,11 @@ int tai_sepconv_forward(const float* input, const float* vertical, const float* 
                         float* output, int B, int C, int H, int W, int ks, void* hip_stream) {
     g_err[0] = 0;
     if (!input || !vertical || !horizontal || !output) return fail(TAI_SEPCONV_EINVAL, "%s", "null pointer");
-    if (!dims_ok(B, C, H, W, ks)) return fail(TAI_SEPCONV_EINVAL, "%s", "bad dimensions");
     hipStream_t s = static_cast<hipStream_t>(hip_stream);
-
-    int variant = g_fwd_variant.load(std::memory_order_relaxed);
-    const bool tileable = (ks == 51) && (W % 4 == 0);
-    // default: mixed type-A / type-B hand-scheduled kernel for single-channel frames; three channel patches per tap row otherwise
-    if (variant == 0) variant = tai_sepconv_default_forward_variant(C, W, ks);
-    if (variant != 1 && !tileable)
-        return fail(TAI_SEPCONV_EINVAL, "%s", "tiled forward variants need ks == 51 and W % 4 == 0");
-    switch (variant) {
+    // the kernel this launch runs: decided in one place, which tai_sepconv_forward_route reports
+    const int route = forward_route(B, C, H, W, ks, g_fwd_variant.load(std::memory_order_relaxed));
+    if (route < 0) return route;
+    switch (route) {
         case 1: {
             const int n = B * C * H * W;
             hipLaunchKernelGGL(fwd::sepconv_forward_generic, dim3((n + 255) / 256), dim3(256), 0, s, input,
@@ -357,25 +402,26 @@ int tai_sepconv_forward(const float* input, const float* vertical, const float* 
         case 15: return fwd_asm_channel_loop<4>(input, vertical, horizontal, output, B, C, H, W, s);
         case 17: return fwd_asm_three_channels<false>(input, vertical, horizontal, output, B, C, H, W, s);
         case 19: return fwd_asm_three_channels<true>(input, vertical, horizontal, output, B, C, H, W, s);
-        case 20: return fwd_persistent(input, vertical, horizontal, output, B, C, H, W, s, g_fwd_variant.load(std::memory_order_relaxed) == 20);
-        case 21: return fwd_persistent(input, vertical, horizontal, output, B, C, H, W, s, true, 1);   // A/B: default cache policy, forward walk
-        case 22: return fwd_persistent(input, vertical, horizontal, output, B, C, H, W, s, true, 2);   // A/B: nt tap loads, forward walk
-        case 23: return fwd_persistent(input, vertical, horizontal, output, B, C, H, W, s, true, 3);   // A/B: nt tap loads, reversed walk
-        case 24: return fwd_persistent(input, vertical, horizontal, output, B, C, H, W, s, true, 4);   // A/B: default cache policy, reversed walk
-        case 25: return fwd_persistent(input, vertical, horizontal, output, B, C, H, W, s, true, 5);   // A/B: as 23, type A at constant priority 0
-        case 26: return fwd_persistent(input, vertical, horizontal, output, B, C, H, W, s, true, 6);   // A/B: as 23, type A at constant priority 1
-        case 27: return fwd_persistent(input, vertical, horizontal, output, B, C, H, W, s, true, 7);   // A/B: as 23, type A at constant priority 2
+        // (20 itself never arrives here: forward_route resolves it to its policy, 21 or 26 by footprint, or to kernel 18)
+        case 21:        // default cache policy, forward walk
+        case 22:        // A/B: nt tap loads, forward walk
+        case 23:        // A/B: nt tap loads, reversed walk
+        case 24:        // A/B: default cache policy, reversed walk
+        case 25:        // A/B: as 23, type A at constant priority 0
+        case 26:        // as 23, type A at constant priority 1
+        case 27:        // A/B: as 23, type A at constant priority 2
+            return launch_persistent(input, vertical, horizontal, output, B, H, W, s, route - 20);
 #ifdef TAI_TIMING_VARIANTS   // timing experiments (wrong results by design): tools/ build only, never in the shipped library
         case 117: return fwd_asm_three_channels<true, 1>(input, vertical, horizontal, output, B, C, H, W, s);   // kernel 19 without the v-ring wait
         case 118: return fwd_asm_three_channels<true, 2>(input, vertical, horizontal, output, B, C, H, W, s);   // kernel 19 without the window waits
         case 108: return fwd_ab_all_channels<3, 3>(input, vertical, horizontal, output, B, C, H, W, s);
         case 109: return fwd_ab_all_channels<4, 3>(input, vertical, horizontal, output, B, C, H, W, s);   // kernel 16 with stamps
         case 110: return fwd_ab_all_channels<5, 3>(input, vertical, horizontal, output, B, C, H, W, s);   // kernel 18 with stamps
-        case 120: return fwd_persistent<1>(input, vertical, horizontal, output, B, C, H, W, s, true);    // kernel 20 with stamps
-        case 123: return fwd_persistent<1>(input, vertical, horizontal, output, B, C, H, W, s, true, 3);  // 23 (round 4's first scheme) with stamps
-        case 125: return fwd_persistent<1>(input, vertical, horizontal, output, B, C, H, W, s, true, 5);  // 25 / 26 / 27 with stamps
-        case 126: return fwd_persistent<1>(input, vertical, horizontal, output, B, C, H, W, s, true, 6);
-        case 127: return fwd_persistent<1>(input, vertical, horizontal, output, B, C, H, W, s, true, 7);
+        case 120: return fwd_persistent_stamped(input, vertical, horizontal, output, B, C, H, W, s, 0);    // kernel 20 with stamps
+        case 123: return fwd_persistent_stamped(input, vertical, horizontal, output, B, C, H, W, s, 3);  // 23 (round 4's first scheme) with stamps
+        case 125: return fwd_persistent_stamped(input, vertical, horizontal, output, B, C, H, W, s, 5);  // 25 / 26 / 27 with stamps
+        case 126: return fwd_persistent_stamped(input, vertical, horizontal, output, B, C, H, W, s, 6);
+        case 127: return fwd_persistent_stamped(input, vertical, horizontal, output, B, C, H, W, s, 7);
         case 106: return fwd_ab_all_channels<0, 3>(input, vertical, horizontal, output, B, C, H, W, s);
         case 107: return fwd_ab_all_channels<2, 3>(input, vertical, horizontal, output, B, C, H, W, s);
         case 111: return fwd_asm_all_channels<false, 0, 8, 2>(input, vertical, horizontal, output, B, C, H, W, s);
