@@ -220,4 +220,19 @@ def test_training_entry_points_reject_bad_arguments():
     assert L.tai_conv_cout1_5x5_forward(p, p, None, p, 1, 8, 8, 18, s) != 0               # W % 4
     assert L.tai_conv3x3_wino_wrw_window(p, p, p, None, p, 1, 8, 8, 8, 16, 8, 16, 1, 2, s) != 0   # window outside the plane
     assert b'window' in L.tai_sepconv_last_error() or len(L.tai_sepconv_last_error()) > 0
+    # the inference entries of the pointwise and thin kernels
+    assert L.tai_bias_act_inplace(p, p, 1, 8, 128, 3, s) != 0                             # act not in {0, 1, 2}
+    assert b'activation' in L.tai_sepconv_last_error()
+    assert L.tai_bias_act_inplace(p, p, 1, 8, 0, 1, s) != 0                               # HW = 0
+    assert L.tai_bias_act_inplace(p, None, 1, 8, 128, 1, s) != 0
+    assert L.tai_unpool2x_add(p, p, p, 1, 4, 3, s) != 0                                   # odd w
+    assert b'unpool2x_add' in L.tai_sepconv_last_error()
+    assert L.tai_convlstm_gates_forward(p, p, p, p, 1, 2, 6, 1.0, s) != 0                 # HW % 4
+    assert b'convlstm_gates' in L.tai_sepconv_last_error()
+    assert L.tai_conv_cin1_forward_maxpool_window(p, p, p, p, p, 1, 8, 7, 16, 3, 1, 8, 8, 0, 0, s) != 0       # odd H
+    assert b'even H' in L.tai_sepconv_last_error()
+    for ph, pw, oy, ox in ((4, 8, 1, 0), (4, 8, 0, 1), (3, 8, 0, 0), (4, 7, 0, 0), (8, 16, -1, 0), (8, 16, 0, -2)):
+        assert L.tai_conv_cin1_forward_maxpool_window(p, p, p, p, p, 1, 8, 8, 16, 3, 1, ph, pw, oy, ox, s) != 0    # window outside its plane
+        assert b'window' in L.tai_sepconv_last_error()
     torch.cuda.synchronize()
+    assert bool((x == 0).all())                                                           # nothing was launched
