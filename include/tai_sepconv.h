@@ -461,6 +461,49 @@ long long tai_ssim_loss_workspace_bytes(int N, int C, int H, int W);
 int tai_ssim_loss(const float* pred, const float* gt, double* plane_ssim, double* totals, float* grad, void* workspace, int N, int C,
                   int H, int W, void* hip_stream);
 
+/* Pointwise + gradient-difference image loss of 1-3 predictions against one ground truth, and its gradients, one launch
+ * (csrc/image_loss.hip.inc; losses.ImageLoss; tests/image_loss_ref.py restates it in numpy).  pred_i (i < npred, npred in 1..3) and gt are
+ * contiguous fp32, viewed as P = planes planes of H x W (P = the product of all leading dimensions; the loss does not care how planes are
+ * ordered), nominally in [-1, 1] and NOT clipped; H, W >= 2.
+ * Definition, per plane; every operation is a single IEEE fp32 operation, no contraction, no reassociation, division and square root
+ * correctly rounded:
+ *   x = (pred + 1) / 2, y = (gt + 1) / 2, in that operation order (util.inverse_transform);  d = x - y;
+ *   point term rho(d) and its derivative rho'(d):
+ *     kind 0 (L2):          rho = d * d;  rho' = 2 * d;
+ *     kind 1 (L1):          rho = |d|;  rho' = sgn(d), with sgn(0) = 0 and NaN kept;
+ *     kind 2 (Charbonnier): s = sqrt(d * d + e2) with e2 = eps * eps computed once in fp32;  rho = s;  rho' = d / s;
+ *   gradient-difference term, exactly losses.GDL's operand order:
+ *     gw(r, c) = (x[r,c] - x[r,c+1]) - (y[r,c] - y[r,c+1]) for 1 <= r <= H-1, 0 <= c <= W-2;
+ *     gh(r, c) = (x[r,c] - x[r-1,c]) - (y[r,c] - y[r-1,c]) for 1 <= r <= H-1, 1 <= c <= W-1;
+ *     (this is not d[r,c] - d[r,c+1]: the bits differ);
+ *   sums are in float64 over the widened fp32 terms:
+ *     plane_terms[i][p][0] = plane_point[p] = the sum of rho over the plane;
+ *     plane_terms[i][p][1] = plane_gdl[p] = the sum of |gw| plus the sum of |gh| over the plane;
+ *     totals[i][0] = point = (sum over p of plane_point[p]) / (P * H * W);
+ *     totals[i][1] = gdl = (sum over p of plane_gdl[p]) / (P * (H-1) * (W-1));
+ *     totals[i][2] = loss = point + gdl;
+ *     the order of the sums is the kernel's, but it is fixed: tile partials go to the workspace, are summed per plane and then over
+ *     planes; no atomics.
+ * Gradient with respect to pred_i, one map, computed in float64 and rounded once:
+ *   S(r, c) = [r>=1, c<=W-2] sgn(gw(r,c)) - [r>=1, c>=1] sgn(gw(r,c-1)) + [r>=1, c>=1] sgn(gh(r,c)) - [r<=H-2, c>=1] sgn(gh(r+1,c)),
+ *     an integer in [-4, 4];
+ *   grad[r,c] = fp32( (double)rho'(d) * cp + S * cg ),  cp = 0.5 / ((double)P * H * W),  cg = 0.5 / ((double)P * (H-1) * (W-1)):
+ *     two float64 products and one float64 sum, no fused multiply-add.  No gradient goes to gt.
+ * grads may be NULL, and so may any grads[i] (evaluation only); the other outputs keep their bits.
+ * A pixel's grad bits and a plane's two sums depend on that plane's pixels and on (P, H, W) through cp / cg only: not on the tiling, the
+ * other planes, npred or the other predictions of the launch.  A NaN in one plane makes that plane's outputs and the totals non-finite
+ * and no other plane's.  preds and grads are host arrays of npred device pointers, read before the call returns.  No allocation, copy or
+ * synchronisation: asynchronous on hip_stream and capturable into a hipGraph.  workspace: 8-byte aligned,
+ * tai_image_loss_workspace_bytes bytes.
+ * TAI_SEPCONV_EINVAL with a message, nothing launched: a null preds / preds[i] / gt / plane_terms / totals / workspace; npred outside
+ * 1..3; kind outside 0..2; kind == 2 with eps not finite or <= 0; planes < 1; H or W < 2; planes * H * W >= 2^40 or H * W >= 2^31; a tile
+ * count of 2^31 or more; float64 buffers not 8-byte aligned.  The workspace query returns TAI_SEPCONV_EINVAL for the same dimensions. */
+long long tai_image_loss_workspace_bytes(int npred, long long planes, int H, int W);
+int tai_image_loss(const float* const* preds, int npred, const float* gt, int kind, float eps,
+                   double* plane_terms /* [npred][planes][2] */, double* totals /* [npred][3]: point, gdl, loss */,
+                   float* const* grads /* NULL, or npred pointers each of which may be NULL */,
+                   void* workspace, long long planes, int H, int W, void* hip_stream);
+
 /* The clip pipeline's two ends (csrc/clip_pipeline.hip.inc): what stands between a decoded frame and the models, and between the models
  * and a PNG, bit-equal to the host code (video_frame_inpainting_amd/data.py and util.py) it replaces when asked to.
  *

@@ -27,6 +27,11 @@ kept, validated, and saved as ``generator_ema`` (``predict.py --weights ema``).
 ``--ssim_weight G``: the generator's loss gains G (1 - mean SSIM) of each prediction against the ground truth (losses.SSIMLoss: one HIP
 launch writes the loss and its gradient); printed lines gain ``G_ssim=`` (and ``G_ssim_forward= G_ssim_backward=`` for TAI).  0 = off.
 
+``--image_loss {l2,l1,charbonnier}`` (default ``l2`` = the reference's MSELoss + GDL, untouched): with ``l1`` or ``charbonnier``
+(``--charbonnier_eps E``, default 1e-3) the pointwise term of alpha (Lp + GDL) becomes mean |d| or mean sqrt(d^2 + E^2) for every
+prediction; Lp and GDL then come from losses.ImageLoss, one HIP launch per update for the losses and gradients of all predictions.  The
+printed keys ``G_Lp= G_gdl=`` (``_forward``, ``_backward``) stay and carry the chosen terms.
+
   python train.py --name demo --K 5 --T 5 --F 5 --c_dim 1 --image_size 128 --batch_size 4 --model_key TAI_gray \
       --max_iter 10 --synthetic 64
 """
@@ -58,6 +63,8 @@ def main(args=None):
         raise SystemExit('--ema_decay must lie strictly between 0 and 1, found %r' % opt.ema_decay)
     if not opt.ssim_weight >= 0.0:
         raise SystemExit('--ssim_weight must not be negative, found %r' % opt.ssim_weight)
+    if not (opt.charbonnier_eps > 0.0 and opt.charbonnier_eps != float('inf')):
+        raise SystemExit('--charbonnier_eps must be finite and > 0, found %r' % opt.charbonnier_eps)
     if not opt.resumable:
         return _run(opt, None)
     if opt.graph_step and GRAPH_STEP_REFUSAL:
@@ -136,7 +143,8 @@ def _run(opt, stop):
                                       opt.image_size, opt.alpha, opt.beta, opt.lr, opt.beta1, opt.df_dim, opt.Ip,
                                       opt.disc_window_size, opt.padding_size, device=device,
                                       graph_step=opt.graph_step, resumable=resumable, guard=guard, fused_step=opt.fused_step,
-                                      ema_decay=opt.ema_decay, max_iter=opt.max_iter, ssim_weight=opt.ssim_weight)
+                                      ema_decay=opt.ema_decay, max_iter=opt.max_iter, ssim_weight=opt.ssim_weight,
+                                      image_loss=opt.image_loss, charbonnier_eps=opt.charbonnier_eps)
     env.sync_replicas()
     total_updates = env.start_update
     # a resumed run starts from the best values its snapshot carries (train.py:96-97)

@@ -7,6 +7,7 @@
 #include <hip/hip_runtime.h>
 
 #include <atomic>
+#include <cmath>
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
@@ -29,6 +30,7 @@
 #include "hbm_probe.hip.inc"
 #include "frame_metrics.hip.inc"
 #include "ssim_loss.hip.inc"
+#include "image_loss.hip.inc"
 #include "clip_pipeline.hip.inc"
 #include "state_digest.hip.inc"
 #include "grad_stats.hip.inc"
@@ -331,7 +333,7 @@ int launch_grad_vh_tiled(const float* gO, const float* in, const float* v, const
 
 extern "C" {
 
-int tai_sepconv_version(void) { return 810; }     // 0.8.1: tai_sepconv_forward_route (host code: the launcher's decision as a query), no kernel changed; (0.7.0: gradient statistics and scaling over a table of tensors (tai_grad_stats, tai_grad_scale), no other kernel changed; (0.6.0: (tai_state_digest added at the same number: an entry point of its own, and the committed counter summaries are tied to it); clip pipeline entry points (tai_clip_from_frames, tai_frames_to_uint8), no other kernel changed; (0.5.0: F(4x4, 3x3) chunk loop as generated assembly, displaced-read blocks, any C; (0.4.1: persistent forward kernel beyond the Infinity Cache: type-A waves at their partners' priority (0.4.0: nt tap loads + reversed walk; source hash)))))
+int tai_sepconv_version(void) { return 820; }     // 0.8.2: tai_image_loss (L2 / L1 / Charbonnier + GDL, loss and gradient in one launch), no other kernel changed; (0.8.1: tai_sepconv_forward_route (host code: the launcher's decision as a query), no kernel changed; (0.7.0: gradient statistics and scaling over a table of tensors (tai_grad_stats, tai_grad_scale), no other kernel changed; (0.6.0: (tai_state_digest added at the same number: an entry point of its own, and the committed counter summaries are tied to it); clip pipeline entry points (tai_clip_from_frames, tai_frames_to_uint8), no other kernel changed; (0.5.0: F(4x4, 3x3) chunk loop as generated assembly, displaced-read blocks, any C; (0.4.1: persistent forward kernel beyond the Infinity Cache: type-A waves at their partners' priority (0.4.0: nt tap loads + reversed walk; source hash)))))
 
 const char* tai_sepconv_last_error(void) { return g_err; }
 
@@ -1711,6 +1713,50 @@ int tai_ssim_loss(const float* pred, const float* gt, double* plane_ssim, double
     if (int rc = check_launch("ssim_loss finish_planes")) return rc;
     hipLaunchKernelGGL(ssimloss::finish_total, dim3(1), dim3(ssimloss::THREADS), 0, s, plane_ssim, totals, planes);
     return check_launch("ssim_loss finish_total");
+}
+
+long long tai_image_loss_workspace_bytes(int npred, long long planes, int H, int W) {
+    if (imgloss::refusal(npred, planes, H, W)) return TAI_SEPCONV_EINVAL;
+    return npred * imgloss::plan(planes, H, W).tiles_total * 2 * (long long)sizeof(double);
+}
+
+int tai_image_loss(const float* const* preds, int npred, const float* gt, int kind, float eps, double* plane_terms, double* totals,
+                   float* const* grads, void* workspace, long long planes, int H, int W, void* hip_stream) {
+    g_err[0] = 0;
+    if (!preds || !gt || !plane_terms || !totals || !workspace) return fail(TAI_SEPCONV_EINVAL, "%s", "image_loss: null pointer");
+    if (const char* why = imgloss::refusal(npred, planes, H, W)) return fail(TAI_SEPCONV_EINVAL, "%s", why);
+    if (kind < 0 || kind > 2) return fail(TAI_SEPCONV_EINVAL, "%s", "image_loss: kind must be 0 (L2), 1 (L1) or 2 (Charbonnier)");
+    if (kind == 2 && !(std::isfinite(eps) && eps > 0.f))
+        return fail(TAI_SEPCONV_EINVAL, "%s", "image_loss: the Charbonnier eps must be finite and > 0");
+    for (int i = 0; i < npred; ++i)
+        if (!preds[i]) return fail(TAI_SEPCONV_EINVAL, "%s", "image_loss: null prediction pointer");
+    if (reinterpret_cast<uintptr_t>(workspace) % 8 != 0 || reinterpret_cast<uintptr_t>(plane_terms) % 8 != 0 ||
+        reinterpret_cast<uintptr_t>(totals) % 8 != 0)
+        return fail(TAI_SEPCONV_EINVAL, "%s", "image_loss: workspace, plane_terms and totals must be 8-byte aligned");
+    const imgloss::Plan pl = imgloss::plan(planes, H, W);
+    imgloss::Args a;
+    for (int i = 0; i < imgloss::MAXP; ++i) {
+        a.pred[i] = i < npred ? preds[i] : nullptr;
+        a.grad[i] = (grads && i < npred) ? grads[i] : nullptr;
+    }
+    a.gt = gt;
+    a.part = static_cast<double*>(workspace);
+    a.npred = npred; a.kind = kind; a.H = H; a.W = W; a.nby = pl.nby; a.nbx = pl.nbx;
+    a.tiles_total = pl.tiles_total;
+    a.e2 = kind == 2 ? eps * eps : 0.f;
+    a.cp = 0.5 / (((double)planes * (double)H) * (double)W);
+    a.cg = 0.5 / (((double)planes * (double)(H - 1)) * (double)(W - 1));
+    const long long rows = npred * planes;
+    hipStream_t s = static_cast<hipStream_t>(hip_stream);
+    const unsigned grid = (unsigned)(pl.tiles_total < imgloss::GRID_CAP ? pl.tiles_total : imgloss::GRID_CAP);
+    hipLaunchKernelGGL(imgloss::tile_loss_grad, dim3(grid), dim3(imgloss::THREADS), 0, s, a);
+    if (int rc = check_launch("image_loss tile_loss_grad")) return rc;
+    hipLaunchKernelGGL(imgloss::finish_planes, dim3((unsigned)((rows + imgloss::THREADS - 1) / imgloss::THREADS)), dim3(imgloss::THREADS), 0, s,
+                       a.part, plane_terms, rows, pl.nby * pl.nbx);
+    if (int rc = check_launch("image_loss finish_planes")) return rc;
+    hipLaunchKernelGGL(imgloss::finish_total, dim3((unsigned)npred), dim3(imgloss::THREADS), 0, s, plane_terms, totals, planes,
+                       ((double)planes * (double)H) * (double)W, ((double)planes * (double)(H - 1)) * (double)(W - 1));
+    return check_launch("image_loss finish_total");
 }
 
 int tai_clip_from_frames(const unsigned char* frames, long long frames_bytes, const long long* table, const long long* table_host,

@@ -23,7 +23,7 @@ import torch
 from . import conv_ops, parallel, run_state
 from . import fused_step as fused_step_module
 from .graph import GraphedForward
-from .losses import GDL, SSIMLoss
+from .losses import GDL, IMAGE_LOSS_KINDS, ImageLoss, SSIMLoss
 from .mcnet import MCNetFillInModel
 from .sn_discriminator import SNDiscriminator
 from .ablations import (BidirectionalSimpleAverageFillInModel, BidirectionalTimeWeightedAverageFillInModel,
@@ -45,9 +45,14 @@ def create_eval_environment(fill_in_model, checkpoints_dir, name, snapshot_file_
 
 def create_training_environment(fill_in_model, c_dim, checkpoints_dir, name, max_K, max_T, max_F, image_size, alpha,
                                 beta, lr, beta1, df_dim, Ip, disc_window_size, padding_size, device=None, graph_step=False,
-                                resumable=False, guard=None, fused_step=False, ema_decay=None, max_iter=100000, ssim_weight=0.0):
+                                resumable=False, guard=None, fused_step=False, ema_decay=None, max_iter=100000, ssim_weight=0.0,
+                                image_loss='l2', charbonnier_eps=1e-3):
     if not ssim_weight >= 0.0:
         raise ValueError('ssim_weight must not be negative, found %r' % (ssim_weight,))
+    if image_loss not in IMAGE_LOSS_KINDS:
+        raise ValueError('image_loss must be one of %s, found %r' % (', '.join(IMAGE_LOSS_KINDS), image_loss))
+    if not (charbonnier_eps > 0.0 and charbonnier_eps != float('inf')):
+        raise ValueError('charbonnier_eps must be finite and > 0, found %r' % (charbonnier_eps,))
     if guard is not None and graph_step:
         raise ValueError('a guarded update cannot be a captured one: a replayed update cannot leave out an optimizer step')
     if fused_step and graph_step:
@@ -60,11 +65,13 @@ def create_training_environment(fill_in_model, c_dim, checkpoints_dir, name, max
         env = TAITrainingEnvironment(      # environments.py:29-31
             fill_in_model, checkpoints_dir, name, image_size, c_dim, alpha, beta, lr, beta1,
                                      df_dim, Ip, disc_window_size, max_K, max_T, max_F, padding_size, device=device,
-                                     graph_step=graph_step, ssim_weight=ssim_weight)
+                                     graph_step=graph_step, ssim_weight=ssim_weight, image_loss=image_loss,
+                                     charbonnier_eps=charbonnier_eps)
     elif isinstance(fill_in_model, MCNetFillInModel):
         env = MCNetTrainingEnvironment(fill_in_model, checkpoints_dir, name, image_size, c_dim, alpha, beta, lr, beta1,
                                        df_dim, Ip, disc_window_size, max_K, max_T, max_F, padding_size, device=device,
-                                       graph_step=graph_step, ssim_weight=ssim_weight)
+                                       graph_step=graph_step, ssim_weight=ssim_weight, image_loss=image_loss,
+                                     charbonnier_eps=charbonnier_eps)
     else:
         raise RuntimeError('Tried to create a training environment for object of unsupported type %s'
                            % type(fill_in_model).__name__)
@@ -474,13 +481,18 @@ class L2GDLDiscTrainingEnvironment(BaseTrainingEnvironment):
     loss_D = BCE(D(fake.detach()), window labels) + BCE(D(real), 1)."""
 
     def __init__(self, fill_in_model, checkpoints_dir, name, image_size, c_dim, alpha, beta, lr, beta1, df_dim, Ip,
-                 disc_t, max_K, max_T, max_F, padding_size, device=None, graph_step=False, ssim_weight=0.0):
+                 disc_t, max_K, max_T, max_F, padding_size, device=None, graph_step=False, ssim_weight=0.0, image_loss='l2',
+                 charbonnier_eps=1e-3):
         super().__init__(fill_in_model, checkpoints_dir, name, lr, beta1, max_K, max_T, max_F, padding_size, device=device,
                          graph_step=graph_step)
         # ssim_weight (train.py --ssim_weight G) > 0: loss_G gains G (1 - mean SSIM) per prediction (losses.SSIMLoss, one HIP launch for
         # the loss and its gradient); 0 = the reference's loss: no module, no launch, no extra key in get_current_errors
         self.ssim_weight = float(ssim_weight)
         self.loss_ssim = SSIMLoss() if self.ssim_weight > 0 else None
+        # image_loss (train.py --image_loss) 'l1' / 'charbonnier': Lp and gdl of every prediction come from losses.ImageLoss on the model's
+        # own [B, T, C, H, W] layout (one HIP launch for the losses and their gradients, no time-major copies); 'l2' = the reference's
+        # MSELoss + GDL composition below: no module, no launch
+        self.loss_image = ImageLoss(image_loss, charbonnier_eps) if image_loss != 'l2' else None
         self._fake_labels = {}
         self.loss_Lp = torch.nn.MSELoss()
         self.loss_gdl = GDL()
@@ -559,12 +571,19 @@ class L2GDLDiscTrainingEnvironment(BaseTrainingEnvironment):
         _, _, c, H, W = x.shape
         return inverse_transform(x.permute(1, 0, 2, 3, 4).contiguous().view(-1, c, H, W))
 
+    _IMAGE_LOSS_KEYS = ('pred',)          # the predictions the image loss is applied to, the first one being ``pred``
+
     def compute_loss_G(self):
         super().compute_loss_G()
-        gt = self._time_major_01(self.gt_middle_frames)
-        outputs = self._time_major_01(self.gen_output['pred'])
-        self.Lp = self.loss_Lp(outputs, gt)
-        self.gdl = self.loss_gdl(outputs, gt)
+        if self.loss_image is not None:
+            # every prediction in one launch; the terms are detached values for the printed line, the losses carry the gradient
+            image_losses = self.loss_image(tuple(self.gen_output[k] for k in self._IMAGE_LOSS_KEYS), self.gt_middle_frames)
+            self.Lp, self.gdl = self.loss_image.last_terms[0]
+        else:
+            gt = self._time_major_01(self.gt_middle_frames)
+            outputs = self._time_major_01(self.gen_output['pred'])
+            self.Lp = self.loss_Lp(outputs, gt)
+            self.gdl = self.loss_gdl(outputs, gt)
         fake = torch.cat([self.preceding_frames, self.gen_output['pred'], self.following_frames], dim=1)
         # The reference lets this backward pass fill the discriminator's .grad as well and throws those values away
         # (optimizer_D.zero_grad() comes before they are ever read, environments.py:348-355): here the discriminator's
@@ -572,11 +591,18 @@ class L2GDLDiscTrainingEnvironment(BaseTrainingEnvironment):
         with _parameters_frozen(self.discriminator):
             h = self.discriminator(fake)
         self.L_GAN = self.loss_d(h, torch.ones_like(h))
-        self.loss_G = self.loss_G + self.alpha * (self.Lp + self.gdl) + self.beta * self.L_GAN
+        if self.loss_image is not None:
+            self.loss_G = self.loss_G + self.alpha * image_losses[0] + self.beta * self.L_GAN          # point + gdl, summed in float64
+            self._add_further_image_losses(image_losses[1:])
+        else:
+            self.loss_G = self.loss_G + self.alpha * (self.Lp + self.gdl) + self.beta * self.L_GAN
         if self.loss_ssim is not None:
             # on the model's own [B, T, C, H, W] layout: the mean over planes does not care about their order
             self.ssim = self.loss_ssim(self.gen_output['pred'], self.gt_middle_frames)
             self.loss_G = self.loss_G + self.ssim_weight * self.ssim
+
+    def _add_further_image_losses(self, losses):
+        """The image losses of ``_IMAGE_LOSS_KEYS[1:]`` (they came from the same launch as ``pred``'s): none here."""
 
     def get_current_errors(self):
         d = super().get_current_errors()
@@ -611,20 +637,27 @@ class TAITrainingEnvironment(L2GDLDiscTrainingEnvironment):
                     self._ktf_rng.randint(2, self.max_F + 1))
         return self.max_K, self.max_T, self.max_F
 
+    _IMAGE_LOSS_KEYS = ('pred', 'pred_forward', 'pred_backward')
+
     def compute_loss_G(self):
         super().compute_loss_G()
-        gt = self._time_major_01(self.gt_middle_frames)
-        out_f = self._time_major_01(self.gen_output['pred_forward'])
-        out_b = self._time_major_01(self.gen_output['pred_backward'])
-        self.Lp_forward = self.loss_Lp(out_f, gt)
-        self.Lp_backward = self.loss_Lp(out_b, gt)
-        self.gdl_forward = self.loss_gdl(out_f, gt)
-        self.gdl_backward = self.loss_gdl(out_b, gt)
-        self.loss_G = self.loss_G + self.alpha * (self.Lp_forward + self.Lp_backward + self.gdl_forward + self.gdl_backward)
+        if self.loss_image is None:
+            gt = self._time_major_01(self.gt_middle_frames)
+            out_f = self._time_major_01(self.gen_output['pred_forward'])
+            out_b = self._time_major_01(self.gen_output['pred_backward'])
+            self.Lp_forward = self.loss_Lp(out_f, gt)
+            self.Lp_backward = self.loss_Lp(out_b, gt)
+            self.gdl_forward = self.loss_gdl(out_f, gt)
+            self.gdl_backward = self.loss_gdl(out_b, gt)
+            self.loss_G = self.loss_G + self.alpha * (self.Lp_forward + self.Lp_backward + self.gdl_forward + self.gdl_backward)
         if self.loss_ssim is not None:
             self.ssim_forward = self.loss_ssim(self.gen_output['pred_forward'], self.gt_middle_frames)
             self.ssim_backward = self.loss_ssim(self.gen_output['pred_backward'], self.gt_middle_frames)
             self.loss_G = self.loss_G + self.ssim_weight * (self.ssim_forward + self.ssim_backward)
+
+    def _add_further_image_losses(self, losses):
+        (self.Lp_forward, self.gdl_forward), (self.Lp_backward, self.gdl_backward) = self.loss_image.last_terms[1:]
+        self.loss_G = self.loss_G + self.alpha * (losses[0] + losses[1])
 
     def get_current_errors(self):
         d = super().get_current_errors()

@@ -1,4 +1,5 @@
-"""Image gradient difference loss (reference src/losses/losses.py:4-44, Mathieu et al.)."""
+"""Image gradient difference loss (reference src/losses/losses.py:4-44, Mathieu et al.), and this build's opt-in losses: SSIMLoss
+(train.py --ssim_weight) and ImageLoss (train.py --image_loss l1 / charbonnier), each a written definition with a HIP kernel behind it."""
 import torch
 import torch.nn as nn
 
@@ -97,3 +98,123 @@ class SSIMLoss(nn.Module):
         planes = S.mean(dim=(1, 2, 3))
         self.plane_ssim = planes.detach()
         return (1.0 - planes.mean()).to(input.dtype)
+
+
+IMAGE_LOSS_KINDS = ('l2', 'l1', 'charbonnier')          # kind 0, 1, 2 of tai_image_loss
+
+
+def _image_loss_terms(pred, gt, kind, eps):
+    """(point, gdl, plane_terms [P, 2]) in float64 by torch ops, differentiable by autograd: the definition of ``tai_image_loss``
+    (include/tai_sepconv.h) up to the order of the sums; the element-wise terms are formed in the tensors' own precision."""
+    H, W = pred.shape[-2:]
+    x = ((pred + 1) / 2).reshape(-1, H, W)                        # util.inverse_transform, not clipped
+    y = ((gt + 1) / 2).reshape(-1, H, W)
+    P = x.shape[0]
+    d = x - y
+    if kind == 0:
+        rho = d * d
+    elif kind == 1:
+        rho = d.abs()                                             # autograd's derivative is sign(d): 0 at 0
+    else:
+        e = torch.tensor(eps, dtype=pred.dtype)
+        rho = torch.sqrt(d * d + float(e * e))
+    gw = ((x[:, 1:, :-1] - x[:, 1:, 1:]) - (y[:, 1:, :-1] - y[:, 1:, 1:])).abs()          # losses.GDL's operand order
+    gh = ((x[:, 1:, 1:] - x[:, :-1, 1:]) - (y[:, 1:, 1:] - y[:, :-1, 1:])).abs()
+    plane_point = rho.double().sum(dim=(1, 2))
+    plane_gdl = gw.double().sum(dim=(1, 2)) + gh.double().sum(dim=(1, 2))
+    point = plane_point.sum() / (float(P) * H * W)
+    gdl = plane_gdl.sum() / (float(P) * (H - 1) * (W - 1))
+    return point, gdl, torch.stack([plane_point, plane_gdl], dim=1)
+
+
+class _ImageLossFunction(torch.autograd.Function):
+    """``tai_image_loss`` on the current stream for 1-3 predictions: (losses fp32 [n], terms fp32 [n, 2] (point, gdl), plane_terms float64
+    [n, P, 2]); the gradient maps come from the same launch and are what ``backward`` scales; a prediction that needs no gradient, or
+    ``want_maps`` false (the caller runs under no_grad), gets no map.  Every allocation is torch's, so under
+    capture it comes from the graph's pool."""
+
+    @staticmethod
+    def forward(ctx, gt, kind, eps, want_maps, *preds):
+        import ctypes
+        from . import _native
+        H, W = gt.shape[-2:]
+        planes = gt.numel() // (H * W)
+        n = len(preds)
+        L = _native.lib()
+        nbytes = L.tai_image_loss_workspace_bytes(n, planes, H, W)
+        if nbytes < 0:
+            raise ValueError('ImageLoss: %d predictions of %d planes of %d x %d are outside what tai_image_loss takes' % (n, planes, H, W))
+        dev = gt.device
+        g = gt.detach().contiguous()
+        ps = [p.detach().contiguous() for p in preds]
+        workspace = torch.empty(nbytes // 8, dtype=torch.float64, device=dev)
+        out = torch.empty(n * planes * 2 + n * 3, dtype=torch.float64, device=dev)         # plane_terms, then totals
+        maps = [torch.empty(p.shape, dtype=torch.float32, device=dev) if want_maps and ctx.needs_input_grad[4 + i] else None
+                for i, p in enumerate(preds)]
+        pred_ptrs = (ctypes.c_void_p * n)(*[p.data_ptr() for p in ps])
+        map_ptrs = (ctypes.c_void_p * n)(*[m.data_ptr() if m is not None else None for m in maps])
+        totals = out[n * planes * 2:]
+        with torch.cuda.device(dev):
+            stream = torch.cuda.current_stream(dev).cuda_stream
+            _native.check(L.tai_image_loss(pred_ptrs, n, g.data_ptr(), kind, eps, out.data_ptr(), totals.data_ptr(), map_ptrs,
+                                           workspace.data_ptr(), planes, H, W, stream), 'tai_image_loss')
+        ctx.maps = maps
+        t32 = totals.view(n, 3).to(torch.float32)
+        losses, terms, plane_terms = t32[:, 2].contiguous(), t32[:, :2], out[:n * planes * 2].view(n, planes, 2)
+        ctx.mark_non_differentiable(terms, plane_terms)
+        return losses, terms, plane_terms
+
+    @staticmethod
+    def backward(ctx, grad_losses, _grad_terms, _grad_planes):
+        return (None, None, None, None) + tuple(grad_losses[i] * m if m is not None else None for i, m in enumerate(ctx.maps))
+
+
+class ImageLoss(nn.Module):
+    """Pointwise term + gradient-difference term of 1-3 predictions against one target, the definition of ``tai_image_loss``
+    (include/tai_sepconv.h): frames mapped to [0, 1] as ``inverse_transform`` does and NOT clipped; the point term is the mean of d^2
+    (``l2``), |d| (``l1``) or sqrt(d^2 + eps^2) (``charbonnier``) and the other the mean of ``GDL``'s |gw| + |gh| over the (H-1) x (W-1)
+    window, both over every plane of ``[..., H, W]`` (any leading dimensions, in the tensors' own layout).  ``forward(preds, target)``
+    takes one tensor or a tuple of 1-3 and returns one scalar ``point + gdl`` per prediction (a tuple for a tuple).  CUDA fp32 tensors go
+    through ONE launch of the HIP kernel for all predictions, which writes the losses and their gradient maps; anything else (CPU,
+    float64) evaluates the same definition with torch ops and is differentiated by autograd.  ``last_terms`` keeps the last call's
+    (point, gdl) per prediction and ``plane_terms`` its per-plane sums [n, P, 2] (float64), detached.  No parameters, no buffers."""
+
+    def __init__(self, kind='charbonnier', eps=1e-3):
+        super().__init__()
+        if kind not in IMAGE_LOSS_KINDS:
+            raise ValueError('ImageLoss: kind must be one of %s, found %r' % (', '.join(IMAGE_LOSS_KINDS), kind))
+        eps = float(eps)
+        if not (eps > 0.0 and eps != float('inf')):
+            raise ValueError('ImageLoss: eps must be finite and > 0, found %r' % (eps,))
+        self.kind, self.eps = kind, eps
+        self.last_terms = None
+        self.plane_terms = None
+
+    def forward(self, preds, target):
+        single = torch.is_tensor(preds)
+        preds = (preds,) if single else tuple(preds)
+        if not 1 <= len(preds) <= 3:
+            raise ValueError('ImageLoss: takes 1 to 3 predictions, got %d' % len(preds))
+        for p in preds:
+            if p.shape != target.shape or p.dim() < 2:
+                raise ValueError('ImageLoss: prediction %s and target %s must have one shape [..., H, W]' % (tuple(p.shape), tuple(target.shape)))
+        H, W = target.shape[-2:]
+        if H < 2 or W < 2 or target.numel() == 0:
+            raise ValueError('ImageLoss: needs at least one plane and H, W >= 2 (the gradient-difference term), got %s' % (tuple(target.shape),))
+        kind = IMAGE_LOSS_KINDS.index(self.kind)
+        if all(t.is_cuda and t.dtype == torch.float32 for t in preds + (target,)):
+            # (inside Function.forward grad mode is always off and needs_input_grad ignores no_grad: the caller's mode is passed in)
+            losses, terms, planes = _ImageLossFunction.apply(target, kind, self.eps, torch.is_grad_enabled(), *preds)
+            self.last_terms = [(terms[i, 0], terms[i, 1]) for i in range(len(preds))]
+            self.plane_terms = planes
+            out = tuple(losses[i] for i in range(len(preds)))
+        else:
+            out, self.last_terms, planes = [], [], []
+            for p in preds:
+                point, gdl, pt = _image_loss_terms(p, target.to(device=p.device, dtype=p.dtype), kind, self.eps)
+                out.append((point + gdl).to(p.dtype))
+                self.last_terms.append((point.detach().to(p.dtype), gdl.detach().to(p.dtype)))
+                planes.append(pt.detach())
+            self.plane_terms = torch.stack(planes)
+            out = tuple(out)
+        return out[0] if single else out

@@ -134,6 +134,14 @@ class TrainOptions(BaseOptions):
                             '(losses.SSIMLoss: 7x7 window, float frames in [0, 1] with L = 1, unclipped, float64 window arithmetic; loss and '
                             'gradient from one HIP launch, tai_ssim_loss); printed lines gain G_ssim= (TAI: G_ssim_forward= G_ssim_backward= '
                             'as well).  0 (default) = the loss as before: nothing is launched, no key is added')
+        g.add_argument('--image_loss', type=str, default='l2', choices=['l2', 'l1', 'charbonnier'],
+                       help="(this build) the pointwise term of the generator's image loss alpha (Lp + GDL), applied to every prediction: "
+                            'l2 (default) = the reference\'s MSELoss + GDL modules, untouched; l1 = mean |d|; charbonnier = mean '
+                            'sqrt(d^2 + eps^2) (--charbonnier_eps), d the difference of the frames in [0, 1].  l1 / charbonnier take Lp and '
+                            'GDL from losses.ImageLoss: one HIP launch (tai_image_loss) writes the losses and gradients of all predictions '
+                            'of an update on the model\'s own layout; the printed keys G_Lp= G_gdl= (_forward, _backward) carry the chosen terms')
+        g.add_argument('--charbonnier_eps', type=float, default=1e-3, metavar='E',
+                       help='(this build, with --image_loss charbonnier) the eps of sqrt(d^2 + eps^2); finite and > 0')
         g.add_argument('--max_wall_minutes', type=float, default=None, metavar='M',
                        help='(this build, with --resumable) stop as after SIGTERM once the run has lasted M minutes')
         g.add_argument('--miopen_find_mode', type=str, default=None, choices=['NORMAL', 'FAST', 'HYBRID', 'DYNAMIC_HYBRID'],
