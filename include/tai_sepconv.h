@@ -504,6 +504,42 @@ int tai_image_loss(const float* const* preds, int npred, const float* gt, int ki
                    float* const* grads /* NULL, or npred pointers each of which may be NULL */,
                    void* workspace, long long planes, int H, int W, void* hip_stream);
 
+/* Laplacian-pyramid L1 loss and its gradient, one launch (csrc/lap_loss.hip.inc; losses.LapLoss; tests/lap_loss_ref.py restates it in
+ * numpy).  pred and gt are contiguous fp32, viewed as [planes, H, W] (the loss does not care how planes are ordered), nominally in
+ * [-1, 1] and NOT clipped; levels = L, 1 <= L <= 6, min(H, W) >= 2^(L-1).
+ * Definition, per plane:
+ *   x = (pred + 1) / 2, y = (gt + 1) / 2, in that operation order (util.inverse_transform); d = x - y; all in fp32, then widened to
+ *     float64; everything below is float64, one IEEE operation per written operation, no contraction.  The pyramid operator is linear,
+ *     so the pyramid of d is the difference of the two pyramids: only d's is built.
+ *   Sizes: H_0 = H, H_{l+1} = ceil(H_l / 2), the same for W.  clamp() below clamps an index to its level (edge replicate).
+ *   Reduce D, taps k = (1, 4, 6, 4, 1) / 16, separable, rows first:
+ *     T[i, x] = sum_{a=0..4} k[a] * G_l[clamp(2i + a - 2), x];   G_{l+1}[i, j] = sum_{b=0..4} k[b] * T[i, clamp(2j + b - 2)];
+ *     each 5-term sum accumulated left to right, starting from its first product (T may be recomputed on the fly, in this order).
+ *   Expand U from level l+1 to the size of level l, separable, rows then columns, along one axis with g the coarser sequence:
+ *     even index 2i:   (g[clamp(i-1)] / 8 + (6 * g[i]) / 8) + g[clamp(i+1)] / 8;     odd index 2i+1:   g[i] / 2 + g[clamp(i+1)] / 2.
+ *   Laplacian: G_0 = d;  L_l = G_l - U(G_{l+1}) for l < L-1;  L_{L-1} = G_{L-1}.
+ *   plane_terms[plane][l] = sum of |L_l| over the plane;  S_l = the sum of plane_terms[.][l] in plane order, from 0.0;
+ *   totals[l] = term_l = (2^l * S_l) / count, count = ((double)P * H) * W;  totals[L] = loss = term_0 + term_1 + ... left to right:
+ *     the sum norm with 2^l weights, normalised by the number of full-resolution pixels.  L = 1 is the mean of |d|.
+ * Gradient with respect to pred:
+ *   s_l = 2^l * sign(L_l), with sign(0) = 0 and a NaN kept;  r_0 = s_0, r_l = s_l - U^T(s_{l-1}) for l >= 1;
+ *   t_{L-1} = r_{L-1}, t_l = r_l + D^T(t_{l+1}) going down to t_0;  grad = fp32((t_0 * 0.5) / count)  (the 0.5 is d x / d pred).
+ *   Every s, r and t value is a dyadic rational that float64 holds exactly for L <= 6 (which is why L stops there), so the adjoint sums
+ *   may be taken in any order and the gradient has one correct bit pattern.  No gradient goes to gt.  grad may be NULL (evaluation
+ *   only): no map is written, the other outputs keep their bits.
+ * A pixel's grad bits and a plane's plane_terms bits depend on that plane's pixels and on (planes, H, W, L) only: not on the other planes
+ * or the launch.  No atomics: the sums of |L_l| are taken in a fixed order.  A NaN in one plane makes that plane's outputs and the
+ * totals non-finite and no other plane's.  No allocation, copy or synchronisation: asynchronous on hip_stream and capturable into a
+ * hipGraph.  workspace: 8-byte aligned, tai_lap_loss_workspace_bytes bytes (never 0): where the pyramids live when a plane's does not
+ * fit the workgroup's LDS.
+ * TAI_SEPCONV_EINVAL with a message, nothing launched: a null pred / gt / plane_terms / totals / workspace; planes < 1; levels outside
+ * 1..6; min(H, W) < 2^(levels-1); planes * H * W >= 2^31; float64 buffers not 8-byte aligned.  The workspace query returns
+ * TAI_SEPCONV_EINVAL for the same dimensions. */
+long long tai_lap_loss_workspace_bytes(long long planes, int H, int W, int levels);
+int tai_lap_loss(const float* pred, const float* gt, int levels, double* plane_terms /* [planes][levels] */,
+                 double* totals /* [levels + 1]: term_0..term_{L-1}, loss */, float* grad /* or NULL */,
+                 void* workspace, long long planes, int H, int W, void* hip_stream);
+
 /* The clip pipeline's two ends (csrc/clip_pipeline.hip.inc): what stands between a decoded frame and the models, and between the models
  * and a PNG, bit-equal to the host code (video_frame_inpainting_amd/data.py and util.py) it replaces when asked to.
  *

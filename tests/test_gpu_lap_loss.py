@@ -1,0 +1,330 @@
+"""The Laplacian-pyramid loss on the GPU (csrc/lap_loss.hip.inc through the C ABI and losses.LapLoss) against the numpy restatement of its
+definition (lap_loss_ref.py): gradient bit for bit, per-plane level sums within n_l 2^-53 relative (the order of a sum of n_l non-negative
+terms is the kernel's), totals from them in plane order; reproducible, inside its buffers, batch-independent, isolated from a non-finite
+plane, past the grid cap, capturable; and train.py --lap_weight with the other run options.  A 128 x 128 plane keeps its pyramid in LDS,
+[1, 160, 160] and larger keep it in the workspace."""
+import functools
+import gc
+import os
+import re
+import sys
+
+import numpy as np
+import pytest
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import lap_loss_ref as ref  # noqa: E402
+
+from video_frame_inpainting_amd import _native  # noqa: E402
+from video_frame_inpainting_amd.losses import LapLoss  # noqa: E402
+
+pytestmark = pytest.mark.gpu
+DEV = torch.device('cuda:0')
+EINVAL = -1
+GRID_CAP = 512
+BAND = 64                                                                             # sentinel words on each side of an output
+
+# (planes, H, W, L): the CPU test's shapes, two planes whose pyramid fills most of the LDS array, three odd planes, and one plane whose
+# pyramid (8400 float64) does not fit it and lives in the workspace
+CASES = [(2, 1, 1, 1), (2, 2, 2, 2), (2, 16, 16, 5), (2, 3, 5, 2), (2, 17, 16, 5), (2, 13, 22, 3), (2, 24, 40, 4), (2, 33, 70, 6),
+         (2, 128, 128, 5), (3, 37, 53, 3), (2, 160, 160, 4)]
+
+
+@functools.lru_cache(maxsize=None)
+def _case(kind, shape, levels, seed=0):
+    """(pred, gt, restatement) for a seeded input; computed once, shared, never written to."""
+    pred, gt = ref.make_pair(kind, shape, 101 + seed + 7 * shape[-1] + shape[-2])
+    want = ref.lap_loss_ref(pred, gt, levels)
+    for a in (pred, gt, want['grad'], want['plane_terms'], want['terms']):
+        a.setflags(write=False)
+    return pred, gt, want
+
+
+def _launch(pred, gt, levels, with_grad=True):
+    """tai_lap_loss through the C ABI, every output inside sentinel bands and the workspace of exactly the queried size ->
+    (plane_terms [P, L] float64, totals [L + 1] float64, grad float32 or None), numpy; asserts that the bands are intact."""
+    L = _native.lib()
+    H, W = pred.shape[-2:]
+    P = pred.size // (H * W)
+    nbytes = L.tai_lap_loss_workspace_bytes(P, H, W, levels)
+    assert nbytes > 0 and nbytes % 8 == 0
+    p, g = torch.from_numpy(np.array(pred)).to(DEV), torch.from_numpy(np.array(gt)).to(DEV)
+    ws = torch.full((nbytes // 8,), float('nan'), dtype=torch.float64, device=DEV)
+    planes = torch.full((P * levels + 2 * BAND,), -7.0, dtype=torch.float64, device=DEV)
+    totals = torch.full((levels + 1 + 2 * BAND,), -7.0, dtype=torch.float64, device=DEV)
+    grad = torch.full((pred.size + 2 * BAND,), -7.0, dtype=torch.float32, device=DEV)
+    rc = L.tai_lap_loss(p.data_ptr(), g.data_ptr(), levels, planes[BAND:].data_ptr(), totals[BAND:].data_ptr(),
+                        grad[BAND:].data_ptr() if with_grad else None, ws.data_ptr(), P, H, W, torch.cuda.current_stream().cuda_stream)
+    assert rc == 0, L.tai_sepconv_last_error()
+    torch.cuda.synchronize()
+    for t in (planes, totals, grad):
+        assert bool((t[:BAND] == -7.0).all()) and bool((t[-BAND:] == -7.0).all())
+    if not with_grad:
+        assert bool((grad == -7.0).all())                                             # no map is written
+    return (planes[BAND:-BAND].view(P, levels).cpu().numpy(), totals[BAND:-BAND].cpu().numpy(),
+            grad[BAND:-BAND].view(pred.shape).cpu().numpy() if with_grad else None)
+
+
+def _bits(a):
+    return np.ascontiguousarray(a).view(np.int32 if a.dtype == np.float32 else np.int64)
+
+
+def _check_totals(planes, totals, count):
+    """totals are plane_terms added in plane order, weighted and divided once, then added left to right: bit for bit."""
+    P, levels = planes.shape
+    loss = None
+    for l in range(levels):
+        s = 0.0
+        for p in range(P):
+            s = s + planes[p, l]
+        term = (2.0 ** l * s) / count
+        assert _bits(np.float64(term)) == _bits(totals[l]) or (np.isnan(term) and np.isnan(totals[l]))
+        loss = term if loss is None else loss + term
+    assert _bits(np.float64(loss)) == _bits(totals[levels]) or (np.isnan(loss) and np.isnan(totals[levels]))
+
+
+@pytest.mark.parametrize('case', CASES, ids=lambda s: 'x'.join(map(str, s)))
+def test_kernel_and_module_match_the_restatement(case):
+    P, H, W, levels = case
+    shape = (P, H, W)
+    bound = np.array([h * w for h, w in ref.sizes(H, W, levels)], np.float64) * 2.0 ** -53
+    for kind in ref.KINDS:
+        pred, gt, want = _case(kind, shape, levels)
+        planes, totals, grad = _launch(pred, gt, levels)
+        wrong = int(np.count_nonzero(_bits(grad) != _bits(want['grad'])))
+        rel = np.abs(planes - want['plane_terms']) / np.maximum(want['plane_terms'], 1e-300)
+        print('%s %s: %d of %d gradient words differ; plane sums rel %.2e; loss %.15g (restatement %.15g)'
+              % (kind, case, wrong, grad.size, rel.max(), totals[levels], want['loss']))
+        assert wrong == 0
+        assert torch.equal(torch.from_numpy(grad), torch.from_numpy(np.array(want['grad'])))
+        assert np.all(rel <= bound[None, :])
+        _check_totals(planes, totals, float(P * H * W))
+        tol = (P * H * W + 8) * 2.0 ** -53
+        assert np.all(np.abs(totals[:levels] - want['terms']) <= tol * want['terms'])
+        assert abs(totals[levels] - want['loss']) <= tol * want['loss']
+        if kind == 'equal':
+            assert not totals.any() and not grad.any()
+        if kind == 'offset':
+            assert not totals[:levels - 1].any() and totals[levels - 1] > 0
+        # the module: the same launch behind autograd
+        p = torch.from_numpy(np.array(pred)).to(DEV).requires_grad_()
+        module = LapLoss(levels)
+        loss = module(p, torch.from_numpy(np.array(gt)).to(DEV))
+        assert loss.dtype == torch.float32 and loss.dim() == 0 and loss.is_cuda
+        loss.backward()
+        assert float(loss.detach()) == float(np.float32(totals[levels]))
+        assert torch.equal(p.grad.cpu().view(torch.int32), torch.from_numpy(grad).view(torch.int32))
+        assert np.array_equal(_bits(module.plane_terms.cpu().numpy()), _bits(planes))
+        assert np.array_equal(module.last_terms.cpu().numpy(), totals[:levels].astype(np.float32))
+
+
+def test_two_launches_give_identical_bits_and_the_evaluation_form_the_same_values():
+    for kind, shape, levels in (('smooth', (3, 37, 53), 3), ('noise', (2, 128, 128), 5), ('noise', (2, 160, 160), 4)):
+        pred, gt, _ = _case(kind, shape, levels)
+        a, b, ev = _launch(pred, gt, levels), _launch(pred, gt, levels), _launch(pred, gt, levels, with_grad=False)
+        for x, y in zip(a, b):
+            assert np.array_equal(_bits(x), _bits(y))
+        assert ev[2] is None
+        assert np.array_equal(_bits(ev[0]), _bits(a[0])) and np.array_equal(_bits(ev[1]), _bits(a[1]))
+        with torch.no_grad():                                                         # the module asks for no gradient map here
+            module = LapLoss(levels)
+            loss = module(torch.from_numpy(np.array(pred)).to(DEV).requires_grad_(), torch.from_numpy(np.array(gt)).to(DEV))
+        assert float(loss) == float(np.float32(a[1][levels])) and not loss.requires_grad
+
+
+@pytest.mark.parametrize('case', [(5, 37, 53, 3), (5, 160, 160, 4)], ids=lambda s: 'x'.join(map(str, s)))
+def test_a_plane_does_not_depend_on_its_batch_and_a_nan_stays_in_its_plane(case):
+    P, H, W, levels = case
+    pred5, gt5, want5 = _case('smooth', (P, H, W), levels)
+    planes5, _, grad5 = _launch(pred5, gt5, levels)
+    assert np.array_equal(_bits(grad5), _bits(want5['grad']))
+    for n in (0, 3):
+        pred1, gt1 = pred5[n:n + 1], gt5[n:n + 1]
+        want1 = ref.lap_loss_ref(pred1, gt1, levels)
+        planes1, _, grad1 = _launch(pred1, gt1, levels)
+        assert np.array_equal(_bits(grad1), _bits(want1['grad']))                     # each P through the restatement, bit for bit
+        assert np.array_equal(_bits(planes1[0]), _bits(planes5[n]))
+        # ... and directly: the two maps differ by the count's factor 5 and one fp32 rounding each
+        g1, g5 = grad1.astype(np.float64), grad5[n:n + 1].astype(np.float64) * 5.0
+        assert np.all(np.abs(g5 - g1) <= 2.0 ** -22 * np.abs(g1))
+    dirty = np.array(pred5)
+    dirty[2, H // 2, W // 3] = np.nan
+    planes, totals, grad = _launch(dirty, gt5, levels)
+    keep = np.array([True, True, False, True, True])
+    assert np.array_equal(_bits(planes[keep]), _bits(planes5[keep]))
+    assert np.isnan(planes[2]).all() and np.isnan(totals).all()
+    assert np.isfinite(grad[keep]).all() and np.array_equal(_bits(grad[keep]), _bits(grad5[keep]))
+    assert np.isnan(grad[2]).any()
+
+
+def test_planes_past_the_grid_cap():
+    """GRID_CAP workgroups stride over GRID_CAP + 3 planes of 4 x 4: the first three workgroups take a second plane."""
+    shape, levels = (GRID_CAP + 3, 4, 4), 2
+    pred, gt, want = _case('noise', shape, levels)
+    planes, totals, grad = _launch(pred, gt, levels)
+    assert np.array_equal(_bits(grad), _bits(want['grad']))
+    assert np.all(np.abs(planes - want['plane_terms']) <= 16 * 2.0 ** -53 * want['plane_terms'])
+    _check_totals(planes, totals, float(np.prod(shape)))
+    alone = _launch(pred[GRID_CAP + 1:GRID_CAP + 2], gt[GRID_CAP + 1:GRID_CAP + 2], levels)[0]
+    assert np.array_equal(_bits(alone[0]), _bits(planes[GRID_CAP + 1]))
+
+
+def test_refusals_launch_nothing():
+    L = _native.lib()
+    x = torch.zeros(2, 16, 16, device=DEV)
+    out = torch.full((32,), -7.0, dtype=torch.float64, device=DEV)
+    grad = torch.full((2, 16, 16), -7.0, device=DEV)
+    ws = torch.full((4,), -7.0, dtype=torch.float64, device=DEV)
+    X, PT, TT, G, WS = x.data_ptr(), out.data_ptr(), out[16:].data_ptr(), grad.data_ptr(), ws.data_ptr()
+    stream = torch.cuda.current_stream().cuda_stream
+    calls = [((None, X, 2, PT, TT, G, WS, 2, 16, 16), b'null pointer'),
+             ((X, None, 2, PT, TT, G, WS, 2, 16, 16), b'null pointer'),
+             ((X, X, 2, None, TT, G, WS, 2, 16, 16), b'null pointer'),
+             ((X, X, 2, PT, None, G, WS, 2, 16, 16), b'null pointer'),
+             ((X, X, 2, PT, TT, G, None, 2, 16, 16), b'null pointer'),
+             ((X, X, 2, PT, TT, G, WS, 0, 16, 16), b'at least one plane'),
+             ((X, X, 0, PT, TT, G, WS, 2, 16, 16), b'levels must be 1..6'),
+             ((X, X, 7, PT, TT, G, WS, 2, 16, 16), b'levels must be 1..6'),
+             ((X, X, 5, PT, TT, G, WS, 2, 15, 16), b'min(H, W) >= 2^(levels-1)'),
+             ((X, X, 5, PT, TT, G, WS, 2, 16, 15), b'min(H, W) >= 2^(levels-1)'),
+             ((X, X, 2, PT, TT, G, WS, 1 << 11, 1 << 10, 1 << 10), b'too large'),
+             ((X, X, 1, PT, TT, G, WS, 1 << 31, 1, 1), b'too large')]
+    for args, message in calls:
+        rc = L.tai_lap_loss(*args, stream)
+        assert rc == EINVAL and message in L.tai_sepconv_last_error(), (args, L.tai_sepconv_last_error())
+        planes, H, W, levels = args[7], args[8], args[9], args[2]
+        if b'null' not in message:
+            assert L.tai_lap_loss_workspace_bytes(planes, H, W, levels) == EINVAL
+    torch.cuda.synchronize()
+    assert bool((out == -7.0).all()) and bool((grad == -7.0).all()) and bool((ws == -7.0).all())
+    with pytest.raises(ValueError):
+        LapLoss(5)(torch.zeros(2, 15, 16, device=DEV), torch.zeros(2, 15, 16, device=DEV))
+
+
+def test_autograd_scales_the_map_and_takes_a_permuted_view():
+    pred, gt, want = _case('smooth', (2, 3, 17, 41), 3)
+    p = torch.from_numpy(np.array(pred)).to(DEV).requires_grad_()
+    g = torch.from_numpy(np.array(gt)).to(DEV)
+    (0.3 * LapLoss(3)(p, g)).backward()
+    assert np.array_equal(_bits(p.grad.cpu().numpy()), _bits(np.float32(0.3) * want['grad']))      # one fp32 product
+    assert g.grad is None
+    # a permuted view [3, 2, H, W] of a [2, 3, H, W] tensor against its contiguous copy
+    base = torch.from_numpy(np.array(pred)).to(DEV)
+    view = base.permute(1, 0, 2, 3).requires_grad_()
+    copy = base.permute(1, 0, 2, 3).contiguous().requires_grad_()
+    assert not view.is_contiguous()
+    gv = g.permute(1, 0, 2, 3)
+    lv, lc = LapLoss(3)(view, gv), LapLoss(3)(copy, gv.contiguous())
+    lv.backward()
+    lc.backward()
+    assert float(lv.detach()) == float(lc.detach())
+    assert torch.equal(view.grad.view(torch.int32), copy.grad.view(torch.int32)) and view.grad.shape == view.shape
+
+
+def test_forward_and_backward_replay_inside_one_graph():
+    shape, levels = (2, 1, 32, 32), 5
+    p1, g1, _ = _case('smooth', shape, levels, seed=1)
+    p2, g2, want2 = _case('noise', shape, levels, seed=2)
+    sp = torch.from_numpy(np.array(p1)).to(DEV).requires_grad_()
+    sg = torch.from_numpy(np.array(g1)).to(DEV)
+    module = LapLoss(levels)
+    side = torch.cuda.Stream()
+    side.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(side):                                                     # warm-up outside the capture
+        module(sp, sg).backward()
+    torch.cuda.current_stream().wait_stream(side)
+    sp.grad = None
+    torch.cuda.synchronize()
+    gc.collect()
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph):
+        loss = module(sp, sg)
+        loss.backward()
+        loss = loss.detach()                                                          # nothing with history outlives the capture
+    with torch.no_grad():
+        sp.copy_(torch.from_numpy(np.array(p2)))
+        sg.copy_(torch.from_numpy(np.array(g2)))
+    graph.replay()
+    torch.cuda.synchronize()
+    eager_p = torch.from_numpy(np.array(p2)).to(DEV).requires_grad_()
+    eager_loss = LapLoss(levels)(eager_p, torch.from_numpy(np.array(g2)).to(DEV))
+    eager_loss.backward()
+    assert float(loss) == float(eager_loss.detach())
+    assert torch.equal(sp.grad.view(torch.int32), eager_p.grad.view(torch.int32))
+    assert np.array_equal(_bits(sp.grad.cpu().numpy()), _bits(want2['grad']))
+
+
+# ---------------------------------------------------------------------------------------------------------------- drivers
+
+SPEC = '{"class": "TAIFillInModel", "args": [4, 1, 3, 51], "kwargs": {"num_block": 5, "kf_dim": 2}}'
+K, T, F, SIZE = 3, 2, 3, 32
+
+
+def _train(tmp_path, capsys, name, max_iter, extra):
+    import train
+    capsys.readouterr()
+    train.main(['--name', name, '--K', str(K), '--T', str(T), '--F', str(F), '--c_dim', '1', '--image_size', str(SIZE), '--model_key', SPEC,
+                '--checkpoints_dir', str(tmp_path / 'ckpt'), '--batch_size', '2', '--max_iter', str(max_iter), '--print_freq', '1',
+                '--df_dim', '8', '--synthetic', '4'] + list(extra))
+    return capsys.readouterr().out
+
+
+def _states(out):
+    return dict((int(i), s) for i, s in re.findall(r'^iter (\d+) .* state=([0-9a-f]{16})$', out, re.M))
+
+
+def _terms(out, n):
+    """{key: [value per printed update]} of the three pyramid terms; asserts each is printed on every line, finite, inside (0, 63): the
+    distance of two frames in [0, 1] is below sum_l 2^l for five levels, a little more where a prediction leaves the range."""
+    found = {}
+    for key in ('G_lap', 'G_lap_forward', 'G_lap_backward'):
+        values = [float(v) for v in re.findall(r' %s=(\S+)' % key, out)]
+        assert len(values) == n, (key, out)
+        assert all(np.isfinite(v) and 0.0 < v < 63.0 for v in values), (key, values)
+        found[key] = values
+    return found
+
+
+def _generator(tmp_path, name):
+    snap = torch.load(str(tmp_path / 'ckpt' / name / 'model_latest.ckpt'), map_location='cpu', weights_only=False)
+    return snap['generator']
+
+
+def test_the_flag_adds_its_terms_and_weight_zero_is_the_run_without_it(tmp_path, capsys, monkeypatch):
+    monkeypatch.chdir(tmp_path)
+    plain = _train(tmp_path, capsys, 'plain', 3, ['--resumable'])
+    zero = _train(tmp_path, capsys, 'zero', 3, ['--resumable', '--lap_weight', '0'])
+    on = _train(tmp_path, capsys, 'on', 3, ['--lap_weight', '0.5'])
+    assert 'G_lap' not in plain and 'G_lap' not in zero
+    assert len(_states(plain)) == 3 and _states(plain) == _states(zero)
+    print(_terms(on, 3))
+    a, b = _generator(tmp_path, 'plain'), _generator(tmp_path, 'on')
+    assert list(a) == list(b)
+    assert any(not torch.equal(a[k], b[k]) for k in a)
+    assert all(torch.isfinite(v).all() for v in b.values() if v.is_floating_point())
+
+
+@pytest.mark.parametrize('extra', [[], ['--guard', '--clip_grad_norm', '1', '--fused_step', '--ema_decay', '0.99', '--ssim_weight', '0.2',
+                                        '--image_loss', 'charbonnier']], ids=['resumable', 'guard_fused_ema_ssim_charbonnier'])
+def test_straight_against_split_with_the_term(tmp_path, capsys, monkeypatch, extra):
+    monkeypatch.chdir(tmp_path)
+    extra = ['--resumable', '--lap_weight', '0.5'] + extra
+    straight = _train(tmp_path, capsys, 'A', 4, extra)
+    first = _train(tmp_path, capsys, 'B', 2, extra)
+    second = _train(tmp_path, capsys, 'B', 4, extra)
+    assert 'carries no run_state' not in second and 'falling back' not in second
+    sa, sb1, sb2 = _states(straight), _states(first), _states(second)
+    print('straight', sa, 'split', sb1, sb2)
+    assert sorted(sa) == [1, 2, 3, 4] and sorted(sb1) == [1, 2] and sorted(sb2) == [3, 4]
+    assert sa == {**sb1, **sb2} and len(set(sa.values())) == 4
+    _terms(straight, 4)
+
+
+def test_graph_step_with_the_term(tmp_path, capsys, monkeypatch):
+    """Updates 1-2 eager, 3 captured and replayed, 4 replayed: the launch is part of the captured update."""
+    monkeypatch.chdir(tmp_path)
+    out = _train(tmp_path, capsys, 'g', 4, ['--graph_step', '--lap_weight', '0.5', '--lap_levels', '4'])
+    terms = _terms(out, 4)
+    print(terms)
+    assert len(set(terms['G_lap'])) > 1

@@ -27,6 +27,10 @@ kept, validated, and saved as ``generator_ema`` (``predict.py --weights ema``).
 ``--ssim_weight G``: the generator's loss gains G (1 - mean SSIM) of each prediction against the ground truth (losses.SSIMLoss: one HIP
 launch writes the loss and its gradient); printed lines gain ``G_ssim=`` (and ``G_ssim_forward= G_ssim_backward=`` for TAI).  0 = off.
 
+``--lap_weight G`` (with ``--lap_levels L``, default 5): the generator's loss gains G times the L1 distance between the Laplacian
+pyramids of each prediction and the ground truth (losses.LapLoss: one HIP launch writes the loss and its gradient); printed lines gain
+``G_lap=`` (and ``G_lap_forward= G_lap_backward=`` for TAI).  0 = off.
+
 ``--image_loss {l2,l1,charbonnier}`` (default ``l2`` = the reference's MSELoss + GDL, untouched): with ``l1`` or ``charbonnier``
 (``--charbonnier_eps E``, default 1e-3) the pointwise term of alpha (Lp + GDL) becomes mean |d| or mean sqrt(d^2 + E^2) for every
 prediction; Lp and GDL then come from losses.ImageLoss, one HIP launch per update for the losses and gradients of all predictions.  The
@@ -65,6 +69,10 @@ def main(args=None):
         raise SystemExit('--ssim_weight must not be negative, found %r' % opt.ssim_weight)
     if not (opt.charbonnier_eps > 0.0 and opt.charbonnier_eps != float('inf')):
         raise SystemExit('--charbonnier_eps must be finite and > 0, found %r' % opt.charbonnier_eps)
+    if not opt.lap_weight >= 0.0:
+        raise SystemExit('--lap_weight must not be negative, found %r' % opt.lap_weight)
+    if opt.lap_weight > 0.0 and not 1 <= opt.lap_levels <= 6:
+        raise SystemExit('--lap_levels must be 1..6, found %r' % opt.lap_levels)
     if not opt.resumable:
         return _run(opt, None)
     if opt.graph_step and GRAPH_STEP_REFUSAL:
@@ -144,7 +152,8 @@ def _run(opt, stop):
                                       opt.disc_window_size, opt.padding_size, device=device,
                                       graph_step=opt.graph_step, resumable=resumable, guard=guard, fused_step=opt.fused_step,
                                       ema_decay=opt.ema_decay, max_iter=opt.max_iter, ssim_weight=opt.ssim_weight,
-                                      image_loss=opt.image_loss, charbonnier_eps=opt.charbonnier_eps)
+                                      image_loss=opt.image_loss, charbonnier_eps=opt.charbonnier_eps,
+                                      lap_weight=opt.lap_weight, lap_levels=opt.lap_levels)
     env.sync_replicas()
     total_updates = env.start_update
     # a resumed run starts from the best values its snapshot carries (train.py:96-97)

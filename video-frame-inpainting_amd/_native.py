@@ -291,6 +291,10 @@ def lib():
     L.tai_image_loss_workspace_bytes.restype = ctypes.c_longlong
     L.tai_image_loss.argtypes = [P, I, P, I, ctypes.c_float, P, P, P, P, ctypes.c_longlong, I, I, V]
     L.tai_image_loss.restype = I
+    L.tai_lap_loss_workspace_bytes.argtypes = [ctypes.c_longlong, I, I, I]
+    L.tai_lap_loss_workspace_bytes.restype = ctypes.c_longlong
+    L.tai_lap_loss.argtypes = [P, P, I, P, P, P, P, ctypes.c_longlong, I, I, V]
+    L.tai_lap_loss.restype = I
     L.tai_clip_from_frames.argtypes =[P, ctypes.c_longlong, P, P, P, P, I, I, I, I, I, I, V]
     L.tai_clip_from_frames.restype = I
     L.tai_frames_to_uint8.argtypes = [P, P, I, I, I, I, I, I, I, V]

@@ -31,6 +31,7 @@
 #include "frame_metrics.hip.inc"
 #include "ssim_loss.hip.inc"
 #include "image_loss.hip.inc"
+#include "lap_loss.hip.inc"
 #include "clip_pipeline.hip.inc"
 #include "state_digest.hip.inc"
 #include "grad_stats.hip.inc"
@@ -333,7 +334,7 @@ int launch_grad_vh_tiled(const float* gO, const float* in, const float* v, const
 
 extern "C" {
 
-int tai_sepconv_version(void) { return 820; }     // 0.8.2: tai_image_loss (L2 / L1 / Charbonnier + GDL, loss and gradient in one launch), no other kernel changed; (0.8.1: tai_sepconv_forward_route (host code: the launcher's decision as a query), no kernel changed; (0.7.0: gradient statistics and scaling over a table of tensors (tai_grad_stats, tai_grad_scale), no other kernel changed; (0.6.0: (tai_state_digest added at the same number: an entry point of its own, and the committed counter summaries are tied to it); clip pipeline entry points (tai_clip_from_frames, tai_frames_to_uint8), no other kernel changed; (0.5.0: F(4x4, 3x3) chunk loop as generated assembly, displaced-read blocks, any C; (0.4.1: persistent forward kernel beyond the Infinity Cache: type-A waves at their partners' priority (0.4.0: nt tap loads + reversed walk; source hash)))))
+int tai_sepconv_version(void) { return 830; }     // 0.8.3: tai_lap_loss (Laplacian-pyramid L1 loss and gradient in one launch), no other kernel changed; (0.8.2: tai_image_loss (L2 / L1 / Charbonnier + GDL, loss and gradient in one launch), no other kernel changed; (0.8.1: tai_sepconv_forward_route (host code: the launcher's decision as a query), no kernel changed; (0.7.0: gradient statistics and scaling over a table of tensors (tai_grad_stats, tai_grad_scale), no other kernel changed; (0.6.0: (tai_state_digest added at the same number: an entry point of its own, and the committed counter summaries are tied to it); clip pipeline entry points (tai_clip_from_frames, tai_frames_to_uint8), no other kernel changed; (0.5.0: F(4x4, 3x3) chunk loop as generated assembly, displaced-read blocks, any C; (0.4.1: persistent forward kernel beyond the Infinity Cache: type-A waves at their partners' priority (0.4.0: nt tap loads + reversed walk; source hash)))))
 
 const char* tai_sepconv_last_error(void) { return g_err; }
 
@@ -1757,6 +1758,35 @@ int tai_image_loss(const float* const* preds, int npred, const float* gt, int ki
     hipLaunchKernelGGL(imgloss::finish_total, dim3((unsigned)npred), dim3(imgloss::THREADS), 0, s, plane_terms, totals, planes,
                        ((double)planes * (double)H) * (double)W, ((double)planes * (double)(H - 1)) * (double)(W - 1));
     return check_launch("image_loss finish_total");
+}
+
+long long tai_lap_loss_workspace_bytes(long long planes, int H, int W, int levels) {
+    if (laploss::refusal(planes, H, W, levels)) return TAI_SEPCONV_EINVAL;
+    return laploss::plan(planes, H, W, levels).work_bytes;
+}
+
+int tai_lap_loss(const float* pred, const float* gt, int levels, double* plane_terms, double* totals, float* grad, void* workspace,
+                 long long planes, int H, int W, void* hip_stream) {
+    g_err[0] = 0;
+    if (!pred || !gt || !plane_terms || !totals || !workspace) return fail(TAI_SEPCONV_EINVAL, "%s", "lap_loss: null pointer");
+    if (const char* why = laploss::refusal(planes, H, W, levels)) return fail(TAI_SEPCONV_EINVAL, "%s", why);
+    if (reinterpret_cast<uintptr_t>(workspace) % 8 != 0 || reinterpret_cast<uintptr_t>(plane_terms) % 8 != 0 ||
+        reinterpret_cast<uintptr_t>(totals) % 8 != 0)
+        return fail(TAI_SEPCONV_EINVAL, "%s", "lap_loss: workspace, plane_terms and totals must be 8-byte aligned");
+    laploss::Plan pl = laploss::plan(planes, H, W, levels);
+    pl.a.pred = pred;
+    pl.a.gt = gt;
+    pl.a.grad = grad;
+    pl.a.plane_terms = plane_terms;
+    pl.a.work = static_cast<double*>(workspace);
+    hipStream_t s = static_cast<hipStream_t>(hip_stream);
+    if (pl.in_lds)
+        hipLaunchKernelGGL(laploss::pyramid_lds, dim3(pl.grid), dim3(laploss::THREADS), 0, s, pl.a);
+    else
+        hipLaunchKernelGGL(laploss::pyramid_workspace, dim3(pl.grid), dim3(laploss::THREADS), 0, s, pl.a);
+    if (int rc = check_launch("lap_loss pyramid")) return rc;
+    hipLaunchKernelGGL(laploss::finish_total, dim3(1), dim3(laploss::FIN_THREADS), 0, s, plane_terms, totals, planes, levels, pl.a.count);
+    return check_launch("lap_loss finish_total");
 }
 
 int tai_clip_from_frames(const unsigned char* frames, long long frames_bytes, const long long* table, const long long* table_host,

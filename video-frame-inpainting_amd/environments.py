@@ -23,7 +23,7 @@ import torch
 from . import conv_ops, parallel, run_state
 from . import fused_step as fused_step_module
 from .graph import GraphedForward
-from .losses import GDL, IMAGE_LOSS_KINDS, ImageLoss, SSIMLoss
+from .losses import GDL, IMAGE_LOSS_KINDS, ImageLoss, LapLoss, SSIMLoss
 from .mcnet import MCNetFillInModel
 from .sn_discriminator import SNDiscriminator
 from .ablations import (BidirectionalSimpleAverageFillInModel, BidirectionalTimeWeightedAverageFillInModel,
@@ -46,9 +46,11 @@ def create_eval_environment(fill_in_model, checkpoints_dir, name, snapshot_file_
 def create_training_environment(fill_in_model, c_dim, checkpoints_dir, name, max_K, max_T, max_F, image_size, alpha,
                                 beta, lr, beta1, df_dim, Ip, disc_window_size, padding_size, device=None, graph_step=False,
                                 resumable=False, guard=None, fused_step=False, ema_decay=None, max_iter=100000, ssim_weight=0.0,
-                                image_loss='l2', charbonnier_eps=1e-3):
+                                image_loss='l2', charbonnier_eps=1e-3, lap_weight=0.0, lap_levels=5):
     if not ssim_weight >= 0.0:
         raise ValueError('ssim_weight must not be negative, found %r' % (ssim_weight,))
+    if not lap_weight >= 0.0:
+        raise ValueError('lap_weight must not be negative, found %r' % (lap_weight,))
     if image_loss not in IMAGE_LOSS_KINDS:
         raise ValueError('image_loss must be one of %s, found %r' % (', '.join(IMAGE_LOSS_KINDS), image_loss))
     if not (charbonnier_eps > 0.0 and charbonnier_eps != float('inf')):
@@ -66,12 +68,12 @@ def create_training_environment(fill_in_model, c_dim, checkpoints_dir, name, max
             fill_in_model, checkpoints_dir, name, image_size, c_dim, alpha, beta, lr, beta1,
                                      df_dim, Ip, disc_window_size, max_K, max_T, max_F, padding_size, device=device,
                                      graph_step=graph_step, ssim_weight=ssim_weight, image_loss=image_loss,
-                                     charbonnier_eps=charbonnier_eps)
+                                     charbonnier_eps=charbonnier_eps, lap_weight=lap_weight, lap_levels=lap_levels)
     elif isinstance(fill_in_model, MCNetFillInModel):
         env = MCNetTrainingEnvironment(fill_in_model, checkpoints_dir, name, image_size, c_dim, alpha, beta, lr, beta1,
                                        df_dim, Ip, disc_window_size, max_K, max_T, max_F, padding_size, device=device,
                                        graph_step=graph_step, ssim_weight=ssim_weight, image_loss=image_loss,
-                                     charbonnier_eps=charbonnier_eps)
+                                     charbonnier_eps=charbonnier_eps, lap_weight=lap_weight, lap_levels=lap_levels)
     else:
         raise RuntimeError('Tried to create a training environment for object of unsupported type %s'
                            % type(fill_in_model).__name__)
@@ -271,7 +273,7 @@ class BaseTrainingEnvironment(BaseVideoFillInEnvironment):
 
     # attributes an update produces (tensors of the captured graph's pool when the update is replayed)
     _STEP_OUTPUTS = ('gen_output', 'loss_G', 'Lp', 'gdl', 'L_GAN', 'loss_d_fake', 'loss_d_real', 'loss_D', 'Lp_forward',
-                     'Lp_backward', 'gdl_forward', 'gdl_backward', 'ssim', 'ssim_forward', 'ssim_backward')
+                     'Lp_backward', 'gdl_forward', 'gdl_backward', 'ssim', 'ssim_forward', 'ssim_backward', 'lap', 'lap_forward', 'lap_backward')
 
     def train_step(self, preceding_frames, following_frames, gt_middle_frames):
         """One update on a batch: set_train_inputs + forward_train + optimize_parameters (src/train.py:147-169), with
@@ -482,7 +484,7 @@ class L2GDLDiscTrainingEnvironment(BaseTrainingEnvironment):
 
     def __init__(self, fill_in_model, checkpoints_dir, name, image_size, c_dim, alpha, beta, lr, beta1, df_dim, Ip,
                  disc_t, max_K, max_T, max_F, padding_size, device=None, graph_step=False, ssim_weight=0.0, image_loss='l2',
-                 charbonnier_eps=1e-3):
+                 charbonnier_eps=1e-3, lap_weight=0.0, lap_levels=5):
         super().__init__(fill_in_model, checkpoints_dir, name, lr, beta1, max_K, max_T, max_F, padding_size, device=device,
                          graph_step=graph_step)
         # ssim_weight (train.py --ssim_weight G) > 0: loss_G gains G (1 - mean SSIM) per prediction (losses.SSIMLoss, one HIP launch for
@@ -493,6 +495,10 @@ class L2GDLDiscTrainingEnvironment(BaseTrainingEnvironment):
         # own [B, T, C, H, W] layout (one HIP launch for the losses and their gradients, no time-major copies); 'l2' = the reference's
         # MSELoss + GDL composition below: no module, no launch
         self.loss_image = ImageLoss(image_loss, charbonnier_eps) if image_loss != 'l2' else None
+        # lap_weight (train.py --lap_weight G) > 0: loss_G gains G times the Laplacian-pyramid L1 distance per prediction (losses.LapLoss
+        # with lap_levels levels, one HIP launch for the loss and its gradient); 0 = no module, no launch, no extra key
+        self.lap_weight = float(lap_weight)
+        self.loss_lap = LapLoss(lap_levels) if self.lap_weight > 0 else None
         self._fake_labels = {}
         self.loss_Lp = torch.nn.MSELoss()
         self.loss_gdl = GDL()
@@ -600,6 +606,9 @@ class L2GDLDiscTrainingEnvironment(BaseTrainingEnvironment):
             # on the model's own [B, T, C, H, W] layout: the mean over planes does not care about their order
             self.ssim = self.loss_ssim(self.gen_output['pred'], self.gt_middle_frames)
             self.loss_G = self.loss_G + self.ssim_weight * self.ssim
+        if self.loss_lap is not None:
+            self.lap = self.loss_lap(self.gen_output['pred'], self.gt_middle_frames)
+            self.loss_G = self.loss_G + self.lap_weight * self.lap
 
     def _add_further_image_losses(self, losses):
         """The image losses of ``_IMAGE_LOSS_KEYS[1:]`` (they came from the same launch as ``pred``'s): none here."""
@@ -611,6 +620,8 @@ class L2GDLDiscTrainingEnvironment(BaseTrainingEnvironment):
                   'G_GAN': float(self.L_GAN.item())})
         if self.loss_ssim is not None:
             d['G_ssim'] = float(self.ssim.item())
+        if self.loss_lap is not None:
+            d['G_lap'] = float(self.lap.item())
         return d
 
     def train(self):
@@ -654,6 +665,10 @@ class TAITrainingEnvironment(L2GDLDiscTrainingEnvironment):
             self.ssim_forward = self.loss_ssim(self.gen_output['pred_forward'], self.gt_middle_frames)
             self.ssim_backward = self.loss_ssim(self.gen_output['pred_backward'], self.gt_middle_frames)
             self.loss_G = self.loss_G + self.ssim_weight * (self.ssim_forward + self.ssim_backward)
+        if self.loss_lap is not None:
+            self.lap_forward = self.loss_lap(self.gen_output['pred_forward'], self.gt_middle_frames)
+            self.lap_backward = self.loss_lap(self.gen_output['pred_backward'], self.gt_middle_frames)
+            self.loss_G = self.loss_G + self.lap_weight * (self.lap_forward + self.lap_backward)
 
     def _add_further_image_losses(self, losses):
         (self.Lp_forward, self.gdl_forward), (self.Lp_backward, self.gdl_backward) = self.loss_image.last_terms[1:]
@@ -665,4 +680,6 @@ class TAITrainingEnvironment(L2GDLDiscTrainingEnvironment):
                   'G_Lp_backward': float(self.Lp_backward.item()), 'G_gdl_backward': float(self.gdl_backward.item())})
         if self.loss_ssim is not None:
             d.update({'G_ssim_forward': float(self.ssim_forward.item()), 'G_ssim_backward': float(self.ssim_backward.item())})
+        if self.loss_lap is not None:
+            d.update({'G_lap_forward': float(self.lap_forward.item()), 'G_lap_backward': float(self.lap_backward.item())})
         return d

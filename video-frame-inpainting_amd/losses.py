@@ -1,5 +1,6 @@
 """Image gradient difference loss (reference src/losses/losses.py:4-44, Mathieu et al.), and this build's opt-in losses: SSIMLoss
-(train.py --ssim_weight) and ImageLoss (train.py --image_loss l1 / charbonnier), each a written definition with a HIP kernel behind it."""
+(train.py --ssim_weight), ImageLoss (train.py --image_loss l1 / charbonnier) and LapLoss (train.py --lap_weight), each a written
+definition with a HIP kernel behind it."""
 import torch
 import torch.nn as nn
 
@@ -218,3 +219,154 @@ class ImageLoss(nn.Module):
             self.plane_terms = torch.stack(planes)
             out = tuple(out)
         return out[0] if single else out
+
+
+LAP_MAX_LEVELS = 6              # tai_lap_loss: up to here every value of the gradient's adjoint pyramid is exact in float64
+
+
+def _lap_check(shape, levels):
+    H, W = shape[-2:]
+    if min(H, W) < 2 ** (levels - 1) or min(shape) == 0:
+        raise ValueError('LapLoss: %d levels need at least one plane with H, W >= %d, got %s' % (levels, 2 ** (levels - 1), tuple(shape)))
+
+
+def _lap_reduce_axis(g, axis):
+    """One pass of D along ``axis``: out[i] = sum_{a=0..4} k[a] g[clamp(2i + a - 2)], k = (1, 4, 6, 4, 1) / 16, left to right."""
+    n = g.shape[axis]
+    base = 2 * torch.arange((n + 1) // 2, device=g.device)
+    acc = None
+    for a, k in enumerate((1.0 / 16.0, 4.0 / 16.0, 6.0 / 16.0, 4.0 / 16.0, 1.0 / 16.0)):
+        term = k * g.index_select(axis, (base + (a - 2)).clamp(0, n - 1))
+        acc = term if acc is None else acc + term
+    return acc
+
+
+def _lap_expand_axis(g, n, axis):
+    """One pass of U along ``axis``, from ceil(n/2) entries to n: even 2i = (g[i-1]/8 + 6 g[i]/8) + g[i+1]/8, odd 2i+1 = g[i]/2 +
+    g[i+1]/2, indices clamped."""
+    m = g.shape[axis]
+    i = torch.arange(m, device=g.device)
+    before, after = g.index_select(axis, (i - 1).clamp(0, m - 1)), g.index_select(axis, (i + 1).clamp(0, m - 1))
+    even = (before / 8.0 + (6.0 * g) / 8.0) + after / 8.0
+    odd = (g / 2.0 + after / 2.0).narrow(axis, 0, n // 2)
+    if n == 2 * m:
+        return torch.stack([even, odd], dim=axis + 1).flatten(axis, axis + 1)
+    head = torch.stack([even.narrow(axis, 0, m - 1), odd], dim=axis + 1).flatten(axis, axis + 1)
+    return torch.cat([head, even.narrow(axis, m - 1, 1)], dim=axis)
+
+
+class _DivideGradient(torch.autograd.Function):
+    """Identity whose backward divides by ``count``.  It puts the loss's 1 / (P H W) behind the adjoint sums, as the definition does:
+    those sums are then exact in float64 and the gradient is rounded once."""
+
+    @staticmethod
+    def forward(ctx, x, count):
+        ctx.count = count
+        return x.view_as(x)
+
+    @staticmethod
+    def backward(ctx, g):
+        return g / ctx.count, None
+
+
+class _DivideValue(torch.autograd.Function):
+    """``x / count`` whose backward passes the gradient through: the other half of ``_DivideGradient``."""
+
+    @staticmethod
+    def forward(ctx, x, count):
+        return x / count
+
+    @staticmethod
+    def backward(ctx, g):
+        return g, None
+
+
+def _lap_terms(pred, gt, levels):
+    """(loss, terms [L], plane_terms [P, L]) in float64 by torch ops, differentiable by autograd: the definition of ``tai_lap_loss``
+    (include/tai_sepconv.h), element-wise operations in its order; only the order of the sums of |L_l| is torch's."""
+    H, W = pred.shape[-2:]
+    d = (((pred + 1) / 2) - ((gt + 1) / 2)).reshape(-1, H, W)     # util.inverse_transform in the tensors' own precision, not clipped
+    P = d.shape[0]
+    count = (float(P) * float(H)) * float(W)
+    G = [_DivideGradient.apply(d.double(), count)]
+    for _ in range(1, levels):
+        G.append(_lap_reduce_axis(_lap_reduce_axis(G[-1], 1), 2))
+    plane_terms = []
+    for l in range(levels):
+        L = G[l]
+        if l < levels - 1:
+            L = L - _lap_expand_axis(_lap_expand_axis(G[l + 1], G[l].shape[1], 1), G[l].shape[2], 2)
+        plane_terms.append(L.abs().sum(dim=(1, 2)))               # autograd's derivative is sign(L): 0 at 0
+    plane_terms = torch.stack(plane_terms, dim=1)
+    terms = torch.stack([_DivideValue.apply(2.0 ** l * plane_terms[:, l].sum(), count) for l in range(levels)])
+    loss = terms[0]
+    for l in range(1, levels):
+        loss = loss + terms[l]
+    return loss, terms, plane_terms
+
+
+class _LapLossFunction(torch.autograd.Function):
+    """``tai_lap_loss`` on the current stream: (loss fp32 scalar, terms fp32 [L], plane_terms float64 [P, L]); the gradient map comes
+    from the same launch and is what ``backward`` scales; ``want_map`` false (the caller runs under no_grad) or a prediction that needs
+    no gradient gets no map.  Every allocation is torch's, so under capture it comes from the graph's pool."""
+
+    @staticmethod
+    def forward(ctx, pred, gt, levels, want_map):
+        from . import _native
+        H, W = pred.shape[-2:]
+        planes = pred.numel() // (H * W)
+        L = _native.lib()
+        nbytes = L.tai_lap_loss_workspace_bytes(planes, H, W, levels)
+        if nbytes < 0:
+            raise ValueError('LapLoss: %d planes of %d x %d with %d levels are outside what tai_lap_loss takes' % (planes, H, W, levels))
+        dev = pred.device
+        p, g = pred.detach().contiguous(), gt.detach().contiguous()
+        workspace = torch.empty(nbytes // 8, dtype=torch.float64, device=dev)
+        out = torch.empty(planes * levels + levels + 1, dtype=torch.float64, device=dev)        # plane_terms, then totals
+        grad = torch.empty(pred.shape, dtype=torch.float32, device=dev) if want_map and ctx.needs_input_grad[0] else None
+        totals = out[planes * levels:]
+        with torch.cuda.device(dev):
+            stream = torch.cuda.current_stream(dev).cuda_stream
+            _native.check(L.tai_lap_loss(p.data_ptr(), g.data_ptr(), levels, out.data_ptr(), totals.data_ptr(),
+                                         grad.data_ptr() if grad is not None else None, workspace.data_ptr(), planes, H, W, stream),
+                          'tai_lap_loss')
+        ctx.map = grad
+        t32 = totals.to(torch.float32)
+        loss, terms, plane_terms = t32[levels].clone(), t32[:levels], out[:planes * levels].view(planes, levels)
+        ctx.mark_non_differentiable(terms, plane_terms)
+        return loss, terms, plane_terms
+
+    @staticmethod
+    def backward(ctx, grad_loss, _grad_terms, _grad_planes):
+        return (grad_loss * ctx.map if ctx.map is not None else None), None, None, None
+
+
+class LapLoss(nn.Module):
+    """L1 distance between the Laplacian pyramids of prediction and target, the definition of ``tai_lap_loss`` (include/tai_sepconv.h):
+    frames mapped to [0, 1] as ``inverse_transform`` does and NOT clipped, ``levels`` levels (1..6) of the 5-tap binomial pyramid with
+    replicated edges built on the difference in float64, level l weighted 2^l, summed and divided by the number of full-resolution pixels
+    of every plane of ``[..., H, W]`` (any leading dimensions, in the tensors' own layout); ``levels = 1`` is the mean of |d|.  CUDA fp32
+    tensors go through the HIP kernel, which writes the loss and its gradient map in one launch; anything else (CPU, float64) evaluates
+    the same definition with torch ops and is differentiated by autograd.  ``last_terms`` keeps the last call's per-level terms [L] and
+    ``plane_terms`` its per-plane sums of |L_l| [P, L] (float64), detached.  No parameters, no buffers."""
+
+    def __init__(self, levels=5):
+        super().__init__()
+        if not (isinstance(levels, int) and 1 <= levels <= LAP_MAX_LEVELS):
+            raise ValueError('LapLoss: levels must be an integer from 1 to %d, found %r' % (LAP_MAX_LEVELS, levels))
+        self.levels = levels
+        self.last_terms = None
+        self.plane_terms = None
+
+    def forward(self, input, target):
+        if input.shape != target.shape or input.dim() < 2:
+            raise ValueError('LapLoss: input %s and target %s must have one shape [..., H, W]' % (tuple(input.shape), tuple(target.shape)))
+        _lap_check(input.shape, self.levels)
+        if input.is_cuda and input.dtype == torch.float32 and target.is_cuda and target.dtype == torch.float32:
+            # (inside Function.forward grad mode is always off and needs_input_grad ignores no_grad: the caller's mode is passed in)
+            loss, terms, planes = _LapLossFunction.apply(input, target, self.levels, torch.is_grad_enabled())
+            self.last_terms, self.plane_terms = terms.detach(), planes.detach()
+            return loss
+        loss, terms, planes = _lap_terms(input, target.to(device=input.device, dtype=input.dtype), self.levels)
+        self.last_terms, self.plane_terms = terms.detach().to(input.dtype), planes.detach()
+        return loss.to(input.dtype)

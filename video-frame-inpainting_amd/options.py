@@ -134,6 +134,14 @@ class TrainOptions(BaseOptions):
                             '(losses.SSIMLoss: 7x7 window, float frames in [0, 1] with L = 1, unclipped, float64 window arithmetic; loss and '
                             'gradient from one HIP launch, tai_ssim_loss); printed lines gain G_ssim= (TAI: G_ssim_forward= G_ssim_backward= '
                             'as well).  0 (default) = the loss as before: nothing is launched, no key is added')
+        g.add_argument('--lap_weight', type=float, default=0.0, metavar='G',
+                       help="(this build) add G times the Laplacian-pyramid L1 distance of every prediction to the ground truth to the "
+                            "generator's loss (losses.LapLoss: 5-tap binomial pyramid of --lap_levels levels on float frames in [0, 1], "
+                            'unclipped, level l weighted 2^l, float64 arithmetic; loss and gradient from one HIP launch, tai_lap_loss); '
+                            'printed lines gain G_lap= (TAI: G_lap_forward= G_lap_backward= as well).  0 (default) = the loss as before: '
+                            'nothing is launched, no key is added')
+        g.add_argument('--lap_levels', type=int, default=5, metavar='L',
+                       help='(this build, with --lap_weight) levels of the pyramid, 1..6; the frames must be at least 2^(L-1) pixels each way')
         g.add_argument('--image_loss', type=str, default='l2', choices=['l2', 'l1', 'charbonnier'],
                        help="(this build) the pointwise term of the generator's image loss alpha (Lp + GDL), applied to every prediction: "
                             'l2 (default) = the reference\'s MSELoss + GDL modules, untouched; l1 = mean |d|; charbonnier = mean '
