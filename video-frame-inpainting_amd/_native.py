@@ -52,11 +52,45 @@ class NativeLibraryError(RuntimeError):
     pass
 
 
-def declared_symbols():
-    """Function names declared in include/tai_sepconv.h."""
+def _header_text():
+    """include/tai_sepconv.h without comments and preprocessor lines: what is left is the prototypes."""
     text = open(HEADER).read()
     text = re.sub(r'/\*.*?\*/', '', text, flags=re.S)
-    return sorted(set(re.findall(r'\b(tai_\w+)\s*\(', text)))
+    text = re.sub(r'//[^\n]*', '', text)
+    return re.sub(r'^[ \t]*#.*$', '', text, flags=re.M)
+
+
+def declared_symbols():
+    """Function names declared in include/tai_sepconv.h."""
+    return sorted(set(re.findall(r'\b(tai_\w+)\s*\(', _header_text())))
+
+
+_CTYPES = {'int': ctypes.c_int, 'long long': ctypes.c_longlong, 'float': ctypes.c_float, 'double': ctypes.c_double}
+_TYPE_WORDS = ('const', 'void', 'char', 'int', 'long', 'float', 'double', 'unsigned', 'signed', 'short')
+
+
+def _ctype(decl, proto):
+    """ctypes type of a C type as the header writes it.  Every pointer is a c_void_p (data pointers, the stream, ``const float* const*``)
+    except ``const char*``, which only the getters return.  A type that is not listed is an error naming the prototype, never a guess."""
+    words = re.sub(r'\bconst\b', ' ', decl.replace('*', ' * ')).split()
+    if '*' in words:
+        return ctypes.c_char_p if words == ['char', '*'] else ctypes.c_void_p
+    if ' '.join(words) not in _CTYPES:
+        raise NativeLibraryError('include/tai_sepconv.h: no ctypes type for `%s` in `%s`' % (decl.strip(), proto))
+    return _CTYPES[' '.join(words)]
+
+
+def signatures(text=None):
+    """{name: (restype, argtypes)} of every prototype in the header (or in ``text``, prototypes given as a string)."""
+    sigs = {}
+    for ret, name, params in re.findall(r'([\w \t\*]+?)\b(tai_\w+)\s*\(([^)]*)\)\s*;', _header_text() if text is None else text):
+        proto = '%s %s(%s)' % (ret.strip(), name, ' '.join(params.split()))
+        params = [] if params.strip() in ('', 'void') else [p.strip() for p in params.split(',')]
+        # `float* y`, `long long planes`, `int`: the last word is the parameter's name unless it is part of the type
+        last = [re.search(r'\w+$', p) for p in params]
+        types = [p if m is None or m.group() in _TYPE_WORDS else p[:m.start()] for p, m in zip(params, last)]
+        sigs[name] = (_ctype(ret, proto), [_ctype(t, proto) for t in types])
+    return sigs
 
 
 TIMING_LIB_PATH = os.path.join(_ROOT, 'build', 'libtai_sepconv_timing.so')
@@ -154,175 +188,9 @@ def lib():
     missing = [s for s in declared_symbols() if not hasattr(L, s)]
     if missing:
         raise NativeLibraryError('%s does not export %s' % (path, missing))
-    P, I, V = ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p
-    L.tai_sepconv_forward.argtypes = [P, P, P, P, I, I, I, I, I, V]
-    L.tai_sepconv_forward.restype = I
-    L.tai_sepconv_backward.argtypes = [P, P, P, P, P, P, P, I, I, I, I, I, V]
-    L.tai_sepconv_backward.restype = I
-    L.tai_upsample_bilinear2x_forward.argtypes = [P, P, I, I, I, V]
-    L.tai_upsample_bilinear2x_forward.restype = I
-    L.tai_upsample_bilinear2x_backward.argtypes = [P, P, I, I, I, V]
-    L.tai_upsample_bilinear2x_backward.restype = I
-    L.tai_conv3x3_wino_weight_floats.argtypes = [I, I]
-    L.tai_conv3x3_wino_weight_floats.restype = ctypes.c_longlong
-    L.tai_conv3x3_wino_transform_weights.argtypes = [P, P, I, I, V]
-    L.tai_conv3x3_wino_transform_weights.restype = I
-    L.tai_conv3x3_wino_forward.argtypes = [P, P, P, P, I, I, I, I, I, I, V]
-    L.tai_conv3x3_wino43_weight_floats.argtypes = [I, I]
-    L.tai_conv3x3_wino43_weight_floats.restype = ctypes.c_longlong
-    L.tai_conv3x3_wino43_transform_weights.argtypes = [P, P, I, I, V]
-    L.tai_conv3x3_wino43_transform_weights.restype = I
-    L.tai_conv3x3_wino43_forward.argtypes = [P, P, P, P, I, I, I, I, I, I, V]
-    L.tai_conv3x3_wino43_forward.restype = I
-    L.tai_conv3x3_wino43_forward_parts.argtypes = [P, I, P, P, P, I, I, I, I, I, I, V]
-    L.tai_conv3x3_wino43_forward_parts.restype = I
-    L.tai_conv3x3_wino43_forward_ex.argtypes = [P, I, P, P, P, P, P, P, I, I, I, I, I, I, V]
-    L.tai_conv3x3_wino43_forward_ex.restype = I
-    L.tai_conv3x3_wino43_forward_blocks.argtypes = [P, I, P, P, P, P] + [I] * 14 + [V]
-    L.tai_conv3x3_wino43_forward_blocks.restype = I
-    L.tai_conv3x3_wino43_set_waves.argtypes = [I]
-    L.tai_conv3x3_wino43_set_waves.restype = I
-    L.tai_conv3x3_wino_forward.restype = I
-    L.tai_conv3x3_wino_forward_maxpool.argtypes = [P, P, P, P, P, I, I, I, I, I, I, V]
-    L.tai_conv3x3_wino_forward_maxpool.restype = I
-    L.tai_conv3x3_wino_forward_window.argtypes = [P, P, P, P, P, I, I, I, I, I, I, I, I, I, I, V]
-    L.tai_conv3x3_wino_forward_window.restype = I
-    L.tai_conv3x3_wino_forward_ex.argtypes = [P, I, I, P, P, P, P, I, I, I, I, P, P] + [I] * 10 + [V]
-    L.tai_conv3x3_wino_forward_ex.restype = I
-    L.tai_conv_cin1_forward_maxpool_window.argtypes = [P, P, P, P, P, I, I, I, I, I, I, I, I, I, I, V]
-    L.tai_conv_cin1_forward_maxpool_window.restype = I
-    L.tai_conv3x3_wino_set_tall.argtypes = [I]
-    L.tai_conv3x3_wino_set_arithmetic.argtypes = [I]
-    L.tai_conv3x3_wino_set_arithmetic.restype = I
-    L.tai_conv3x3_wino_get_arithmetic.argtypes = []
-    L.tai_conv3x3_wino_forget_weights.argtypes = [P]
-    L.tai_conv3x3_wino_forget_weights.restype = I
-    L.tai_conv3x3_wino_get_arithmetic.restype = I
-    L.tai_conv3x3_wino_set_tall.restype = I
-    L.tai_conv3x3_wino_forward_parts.argtypes = [P, I, P, P, P, I, I, I, I, I, I, V]
-    L.tai_conv3x3_wino_forward_parts.restype = I
-    L.tai_conv3x3_wino_forward_timeline.argtypes = [P, P, P, P, I, I, I, I, I, P, V]
-    L.tai_conv3x3_wino_forward_timeline.restype = I
-    L.tai_conv_cin1_forward.argtypes = [P, P, P, P, I, I, I, I, I, I, V]
-    L.tai_conv_cin1_forward.restype = I
-    L.tai_conv_cin1_forward_maxpool.argtypes = [P, P, P, P, P, I, I, I, I, I, I, V]
-    L.tai_conv_cin1_forward_maxpool.restype = I
-    L.tai_unpool2x_add.argtypes = [P, P, P, ctypes.c_longlong, I, I, V]
-    L.tai_unpool2x_add.restype = I
-    L.tai_convlstm_gates_forward.argtypes = [P, P, P, P, I, I, I, ctypes.c_float, V]
-    L.tai_convlstm_gates_forward.restype = I
-    L.tai_convlstm_gates_backward.argtypes = [P, P, P, P, P, P, P, I, I, I, ctypes.c_float, V]
-    L.tai_convlstm_gates_backward.restype = I
-    L.tai_conv3x3_wino_wrw_workspace_floats.argtypes = [I] * 5
-    L.tai_conv3x3_wino_wrw_workspace_floats.restype = ctypes.c_longlong
-    L.tai_conv3x3_wino_wrw.argtypes = [P, P, P, P, P, I, I, I, I, I, V]
-    L.tai_conv3x3_wino_wrw.restype = I
-    L.tai_conv3x3_wino_wrw_window.argtypes = [P, P, P, P, P] + [I] * 9 + [V]
-    L.tai_conv3x3_wino_wrw_window.restype = I
-    L.tai_conv3x3_wino_wrw_set_paired.argtypes = [I]
-    L.tai_conv3x3_wino_wrw_set_paired.restype = I
-    L.tai_conv3x3_wino43_set_placement.argtypes = [I]
-    L.tai_conv3x3_wino43_set_placement.restype = I
-    L.tai_conv3x3_wino43_set_splitc.argtypes = [I]
-    L.tai_conv3x3_wino43_set_splitc.restype = I
-    L.tai_conv3x3_wino43_splits.argtypes = [I] * 6 + [P]
-    L.tai_conv3x3_wino43_splits.restype = I
-    L.tai_conv3x3_wino43_workspace_floats.argtypes = [I] * 6
-    L.tai_conv3x3_wino43_workspace_floats.restype = ctypes.c_longlong
-    L.tai_conv3x3_wino43_forward_ws.argtypes = [P, I, P, P, P, P, P, P, P, ctypes.c_longlong, I, I, I, I, I, I, V]
-    L.tai_conv3x3_wino43_forward_ws.restype = I
-    L.tai_conv3x3_wino_wrw_set_tile.argtypes = [I]
-    L.tai_conv3x3_wino_wrw_set_tile.restype = I
-    L.tai_window_scale_bias_lrelu.argtypes = [P, P, P, I, I, I, I, ctypes.c_float, V]
-    L.tai_window_scale_bias_lrelu.restype = I
-    L.tai_window_scale_lrelu_backward.argtypes = [P, P, P, P, P, I, I, I, I, ctypes.c_float, V]
-    L.tai_window_scale_lrelu_backward.restype = I
-    L.tai_window_scale_bias_lrelu_scalar.argtypes = [P, P, P, I, I, I, I, ctypes.c_float, V]
-    L.tai_window_scale_bias_lrelu_scalar.restype = I
-    L.tai_window_scale_lrelu_backward_scalar.argtypes = [P, P, P, P, P, I, I, I, I, ctypes.c_float, V]
-    L.tai_window_scale_lrelu_backward_scalar.restype = I
-    L.tai_thin_conv_wrw.argtypes = [P, P, P, P, P, I, I, I, I, I, V]
-    L.tai_thin_conv_wrw.restype = I
-    L.tai_act_maxpool2x2_forward.argtypes = [P, P, P, ctypes.c_longlong, I, I, I, V]
-    L.tai_act_maxpool2x2_forward.restype = I
-    L.tai_act_maxpool2x2_backward.argtypes = [P, P, P, P, ctypes.c_longlong, I, I, I, V]
-    L.tai_act_maxpool2x2_backward.restype = I
-    L.tai_sn_power_iteration.argtypes = [P, P, P, P, I, I, I, V]
-    L.tai_sn_power_iteration.restype = I
-    L.tai_conv_shift_stack.argtypes = [P, P, I, I, I, I, I, V]
-    L.tai_conv_shift_stack.restype = I
-    L.tai_conv_cout1_3x3_forward.argtypes = [P, P, P, P, I, I, I, I, I, V]
-    L.tai_conv_cout1_3x3_forward.restype = I
-    L.tai_conv_cout1_5x5_forward.argtypes = [P, P, P, P, I, I, I, I, V]
-    L.tai_conv_cout1_5x5_forward.restype = I
-    L.tai_bias_act_inplace.argtypes = [P, P, I, I, I, I, V]
-    L.tai_bias_act_inplace.restype = I
-    L.tai_sepconv_set_forward_variant.argtypes = [I]
-    L.tai_sepconv_set_forward_variant.restype = I
-    L.tai_sepconv_default_forward_variant.argtypes = [I, I, I]
-    L.tai_sepconv_default_forward_variant.restype = I
-    L.tai_sepconv_forward_route.argtypes = [I] * 6
-    L.tai_sepconv_forward_route.restype = I
-    L.tai_sepconv_set_grad_taps_variant.argtypes = [I]
-    L.tai_sepconv_set_grad_taps_variant.restype = I
-    L.tai_sepconv_set_grad_input_variant.argtypes = [I]
-    L.tai_sepconv_set_grad_input_variant.restype = I
-    L.tai_sepconv_forward_bytes.argtypes = [I] * 5
-    L.tai_sepconv_forward_bytes.restype = ctypes.c_longlong
-    L.tai_sepconv_backward_bytes.argtypes = [I] * 5
-    L.tai_sepconv_backward_bytes.restype = ctypes.c_longlong
-    L.tai_hbm_read_probe.argtypes = [P, ctypes.c_longlong, I, P, V]
-    L.tai_hbm_read_probe.restype = I
-    L.tai_conv_bf16_weight_elems.argtypes = [I, I, I]
-    L.tai_conv_bf16_weight_elems.restype = ctypes.c_longlong
-    L.tai_conv_bf16_pack_weights.argtypes = [P, P, I, I, I, I, V]
-    L.tai_conv_bf16_pack_weights.restype = I
-    L.tai_conv_bf16_forward.argtypes = [P, I, P, P, P, P, P, P] + [I] * 7 + [V]
-    L.tai_conv_bf16_forward.restype = I
-    L.tai_frame_metrics_workspace_bytes.argtypes = [I] * 4
-    L.tai_frame_metrics_workspace_bytes.restype = ctypes.c_longlong
-    L.tai_frame_metrics.argtypes = [P, P, P, P, P, P, I, I, I, I, V]
-    L.tai_frame_metrics.restype = I
-    L.tai_ssim_loss_workspace_bytes.argtypes = [I] * 4
-    L.tai_ssim_loss_workspace_bytes.restype = ctypes.c_longlong
-    L.tai_ssim_loss.argtypes = [P, P, P, P, P, P, I, I, I, I, V]
-    L.tai_ssim_loss.restype = I
-    L.tai_image_loss_workspace_bytes.argtypes = [I, ctypes.c_longlong, I, I]
-    L.tai_image_loss_workspace_bytes.restype = ctypes.c_longlong
-    L.tai_image_loss.argtypes = [P, I, P, I, ctypes.c_float, P, P, P, P, ctypes.c_longlong, I, I, V]
-    L.tai_image_loss.restype = I
-    L.tai_lap_loss_workspace_bytes.argtypes = [ctypes.c_longlong, I, I, I]
-    L.tai_lap_loss_workspace_bytes.restype = ctypes.c_longlong
-    L.tai_lap_loss.argtypes = [P, P, I, P, P, P, P, ctypes.c_longlong, I, I, V]
-    L.tai_lap_loss.restype = I
-    L.tai_clip_from_frames.argtypes =[P, ctypes.c_longlong, P, P, P, P, I, I, I, I, I, I, V]
-    L.tai_clip_from_frames.restype = I
-    L.tai_frames_to_uint8.argtypes = [P, P, I, I, I, I, I, I, I, V]
-    L.tai_frames_to_uint8.restype = I
-    L.tai_state_digest_workspace_bytes.argtypes = [I, ctypes.c_longlong]
-    L.tai_state_digest_workspace_bytes.restype = ctypes.c_longlong
-    L.tai_state_digest.argtypes = [P, P, I, ctypes.c_longlong, ctypes.c_longlong, P, P, V]
-    L.tai_state_digest.restype = I
-    L.tai_grad_stats_workspace_bytes.argtypes = [I, ctypes.c_longlong]
-    L.tai_grad_stats_workspace_bytes.restype = ctypes.c_longlong
-    L.tai_grad_stats.argtypes = [P, P, I, ctypes.c_longlong, I, P, P, P, P, V]
-    L.tai_grad_stats.restype = I
-    L.tai_grad_scale_workspace_bytes.argtypes = [I, ctypes.c_longlong]
-    L.tai_grad_scale_workspace_bytes.restype = ctypes.c_longlong
-    L.tai_grad_scale.argtypes = [P, P, I, ctypes.c_longlong, ctypes.c_float, I, P, V]
-    L.tai_grad_scale.restype = I
-    LL, Fl = ctypes.c_longlong, ctypes.c_float
-    L.tai_step_verdict_workspace_bytes.argtypes = []
-    L.tai_step_verdict_workspace_bytes.restype = LL
-    L.tai_step_verdict.argtypes = [P, P, I, ctypes.c_double, I, I, LL, LL, P, V]
-    L.tai_step_verdict.restype = I
-    L.tai_fused_step_workspace_bytes.argtypes = [I, LL]
-    L.tai_fused_step_workspace_bytes.restype = LL
-    L.tai_fused_step.argtypes = [P, P, I, LL, P, LL, Fl, Fl, Fl, Fl, Fl, P, I, I, I, P, V]
-    L.tai_fused_step.restype = I
-    L.tai_sepconv_last_error.restype = ctypes.c_char_p
-    L.tai_sepconv_source_hash.restype = ctypes.c_char_p
-    L.tai_sepconv_version.restype = I
+    for name, (restype, argtypes) in signatures().items():
+        entry = getattr(L, name)
+        entry.restype, entry.argtypes = restype, argtypes
     _lib = L
     return L
 
@@ -330,3 +198,13 @@ def lib():
 def check(rc, what):
     if rc != 0:
         raise RuntimeError('%s failed (%d): %s' % (what, rc, lib().tai_sepconv_last_error().decode()))
+
+
+def launch(name, device, *args):
+    """Call the entry ``name`` on ``device``'s current stream and raise unless it returns 0: the entries whose last parameter is the
+    stream.  Tensors among ``args`` go as their data pointer and None as a null pointer; ints, floats and ctypes pointer arrays pass
+    through.  (The entries without a stream -- *_floats, *_workspace_bytes, *_splits, set_*, get_* -- are called on lib() directly.)"""
+    import torch
+    with torch.cuda.device(device):
+        check(getattr(lib(), name)(*[a.data_ptr() if isinstance(a, torch.Tensor) else a for a in args],
+                                   torch.cuda.current_stream(device).cuda_stream), name)

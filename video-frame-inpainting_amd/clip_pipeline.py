@@ -161,11 +161,8 @@ class DeviceClipBuilder(object):
             slot.event.record(torch.cuda.current_stream(self.device))
             out = torch.empty(B, T, self.c_dim, H + ph, W + pw, dtype=torch.float32, device=self.device)
             # the descriptor table is validated on the host from the staging buffer's header before anything is launched
-            _native.check(_native.lib().tai_clip_from_frames(slot.dev.data_ptr() + head, nbytes - head, slot.dev.data_ptr(),
-                                                             slot.host.data_ptr(), self._levels.data_ptr(), out.data_ptr(), n,
-                                                             self.c_dim, H, W, ph, pw,
-                                                             torch.cuda.current_stream(self.device).cuda_stream),
-                          'tai_clip_from_frames')
+            _native.launch('tai_clip_from_frames', self.device, slot.dev.data_ptr() + head, nbytes - head, slot.dev, slot.host, self._levels,
+                           out, n, self.c_dim, H, W, ph, pw)
         return out
 
 
@@ -184,9 +181,7 @@ def frames_to_uint8_device(x, h=None, w=None, rgb=False, out=None):
         out = torch.empty(shape, dtype=torch.uint8, device=x.device)
     if out.dtype != torch.uint8 or tuple(out.shape) != shape or not out.is_contiguous() or out.device != x.device:
         raise ValueError('frames_to_uint8_device: out must be a contiguous uint8 %s tensor on %s' % (shape, x.device))
-    with torch.cuda.device(x.device):
-        _native.check(_native.lib().tai_frames_to_uint8(x.data_ptr(), out.data_ptr(), N, C, Hs, Ws, h, w, int(bool(rgb)),
-                                                        torch.cuda.current_stream(x.device).cuda_stream), 'tai_frames_to_uint8')
+    _native.launch('tai_frames_to_uint8', x.device, x, out, N, C, Hs, Ws, h, w, int(bool(rgb)))
     return out
 
 

@@ -110,9 +110,7 @@ def _bf16_weights(weight, transposed):
         n = L.tai_conv_bf16_weight_elems(K, C, k)
         _native.check(n if n < 0 else 0, 'tai_conv_bf16_weight_elems')
         Wp = torch.empty(n, dtype=torch.bfloat16, device=w.device)
-        with torch.cuda.device(w.device):
-            _native.check(L.tai_conv_bf16_pack_weights(w.data_ptr(), Wp.data_ptr(), K, C, k, int(transposed),
-                                                       torch.cuda.current_stream(w.device).cuda_stream), 'tai_conv_bf16_pack_weights')
+        _native.launch('tai_conv_bf16_pack_weights', w.device, w, Wp, K, C, k, int(transposed))
         return Wp
     return _cached(weight, ('bf16', transposed), make)
 
@@ -132,13 +130,8 @@ def _bf16_conv(parts, weight, bias, act, transposed=False, out=None, pool=False,
         addx = addx.contiguous()
         y2 = torch.empty_like(y) if keep_plain else None
     ptrs = (ctypes.c_void_p * len(parts))(*[p.data_ptr() for p in parts])
-    Wp = _bf16_weights(weight, transposed)
-    with torch.cuda.device(x0.device):
-        _native.check(_native.lib().tai_conv_bf16_forward(ptrs, len(parts), Wp.data_ptr(), bias.data_ptr(), y.data_ptr(),
-                                                          yp.data_ptr() if yp is not None else None,
-                                                          addx.data_ptr() if addx is not None else None,
-                                                          y2.data_ptr() if y2 is not None else None, N, Ci, Co, H, W, k, _ACT[act],
-                                                          torch.cuda.current_stream(x0.device).cuda_stream), 'tai_conv_bf16_forward')
+    _native.launch('tai_conv_bf16_forward', x0.device, ptrs, len(parts), _bf16_weights(weight, transposed), bias, y, yp, addx, y2,
+                   N, Ci, Co, H, W, k, _ACT[act])
     if pool:
         return y, yp
     if addx is not None:
@@ -213,28 +206,18 @@ def _wino43_ok(N, Ci, Co, H, W, nparts=1, weight=None, split=True):
     return split and bool(any_width) and groups * _native.lib().tai_conv3x3_wino43_splits(N, Ci, Co, H, W, nparts, None) >= WINO43_MIN_WORKGROUPS
 
 
-def _wino43_launch(ptrs, nparts, U, bias, y, N, C, K, H, W, act, stream, weight, ypool=None, addx=None, y2=None):
+def _wino43_launch(ptrs, nparts, U, bias, y, N, C, K, H, W, act, weight, ypool=None, addx=None, y2=None):
     """One F(4x4, 3x3) forward (tai_conv3x3_wino43_forward_ws).  Where the library splits the input channels over more workgroups
     (small grids) it needs a workspace for the partial tiles: allocated here with torch, so that under graph capture it comes
     from the graph's pool.  ``ptrs``: a ctypes array of the nparts input pointers."""
-    L = _native.lib()
     groups = ((N * (H // 4) * (W // 4) + 31) // 32) * ((K + 63) // 64)
     if groups < WINO43_SPLIT_MIN_WORKGROUPS and not getattr(weight, '_tai_f43_any_width', False):
-        _native.check(L.tai_conv3x3_wino43_forward_ex(ptrs, nparts, U.data_ptr(), bias.data_ptr(), y.data_ptr(),
-                                                      ypool.data_ptr() if ypool is not None else None,
-                                                      addx.data_ptr() if addx is not None else None,
-                                                      y2.data_ptr() if y2 is not None else None, N, C, K, H, W, act, stream),
-                      'tai_conv3x3_wino43_forward_ex')
+        _native.launch('tai_conv3x3_wino43_forward_ex', y.device, ptrs, nparts, U, bias, y, ypool, addx, y2, N, C, K, H, W, act)
         return
-    n = L.tai_conv3x3_wino43_workspace_floats(N, C, K, H, W, nparts)
+    n = _native.lib().tai_conv3x3_wino43_workspace_floats(N, C, K, H, W, nparts)
     _native.check(n if n < 0 else 0, 'tai_conv3x3_wino43_workspace_floats')
     ws = torch.empty(n, dtype=torch.float32, device=y.device) if n > 0 else None
-    _native.check(L.tai_conv3x3_wino43_forward_ws(ptrs, nparts, U.data_ptr(), bias.data_ptr(), y.data_ptr(),
-                                                  ypool.data_ptr() if ypool is not None else None,
-                                                  addx.data_ptr() if addx is not None else None,
-                                                  y2.data_ptr() if y2 is not None else None,
-                                                  ws.data_ptr() if ws is not None else None, n, N, C, K, H, W, act, stream),
-                  'tai_conv3x3_wino43_forward_ws')
+    _native.launch('tai_conv3x3_wino43_forward_ws', y.device, ptrs, nparts, U, bias, y, ypool, addx, y2, ws, n, N, C, K, H, W, act)
 
 
 def _cached(weight, tag, make):
@@ -261,32 +244,31 @@ def _registered(U):
     return U
 
 
-def _wino_weights(weight, transposed):
-    def make():
-        w = _as_conv_weight(weight.detach(), transposed).contiguous()
-        K, C = w.shape[0], w.shape[1]
-        L = _native.lib()
-        U = _registered(torch.empty(L.tai_conv3x3_wino_weight_floats(K, C), dtype=torch.float32, device=w.device))
-        with torch.cuda.device(w.device):
-            _native.check(L.tai_conv3x3_wino_transform_weights(w.data_ptr(), U.data_ptr(), K, C,
-                                                               torch.cuda.current_stream(w.device).cuda_stream),
-                          'tai_conv3x3_wino_transform_weights')
-        return U
-    return _cached(weight, ('wino', transposed, _WINO_ARITH[0]), make)
+def _transform(w, tile):
+    """The Winograd-domain image of a contiguous [K, C, 3, 3] filter: ``tile`` 2 / 4 -- the F(2x2, 3x3) / F(4x4, 3x3) layout."""
+    K, C = w.shape[0], w.shape[1]
+    pre = 'tai_conv3x3_wino43' if tile == 4 else 'tai_conv3x3_wino'
+    U = torch.empty(getattr(_native.lib(), pre + '_weight_floats')(K, C), dtype=torch.float32, device=w.device)
+    if tile == 2:
+        _registered(U)
+    _native.launch(pre + '_transform_weights', w.device, w, U, K, C)
+    return U
 
 
-def _wino43_weights(weight, transposed):
+def _transformed_weights(weight, transposed, tile, blocks=False):
+    """The cached transformed weights of a layer.  ``transposed``: of the weight transposed and flipped (a stride-1 ConvTranspose2d;
+    the input-gradient convolution of the same weight, weight[k, c, a, b] -> [c, k, K-1-a, K-1-b]).  ``blocks``: the k x k filter
+    (k = 5, 7) first rewritten as S x S blocks of 3 x 3 taps (_block3x3_weight: the shifted-copy stack of _kxk_as_wino, the displaced
+    reads of tai_conv3x3_wino43_forward_blocks).  The F(2x2, 3x3) buffers depend on the arithmetic, which is part of their tag."""
     def make():
-        w = _as_conv_weight(weight.detach(), transposed).contiguous()
-        K, C = w.shape[0], w.shape[1]
-        L = _native.lib()
-        U = torch.empty(L.tai_conv3x3_wino43_weight_floats(K, C), dtype=torch.float32, device=w.device)
-        with torch.cuda.device(w.device):
-            _native.check(L.tai_conv3x3_wino43_transform_weights(w.data_ptr(), U.data_ptr(), K, C,
-                                                                 torch.cuda.current_stream(w.device).cuda_stream),
-                          'tai_conv3x3_wino43_transform_weights')
-        return U
-    return _cached(weight, ('wino43', transposed), make)
+        w = _as_conv_weight(weight.detach(), transposed)
+        return _transform(_block3x3_weight(w.contiguous() if transposed else w) if blocks else w.contiguous(), tile)
+    name = ('wino43' if tile == 4 else 'wino') + ('_kxk' if blocks else '')
+    return _cached(weight, (name, transposed) if tile == 4 else (name, transposed, _WINO_ARITH[0]), make)
+
+
+def _wino_weights_kxk(weight, transposed=False):
+    return _transformed_weights(weight, transposed, 2, blocks=True)
 
 
 def _block3x3_weight(weight):
@@ -297,39 +279,6 @@ def _block3x3_weight(weight):
     wp = F.pad(weight, (0, 3 * S - k, 0, 3 * S - k))                        # [K, C, 3S, 3S]
     wp = wp.view(K, C, S, 3, S, 3).permute(0, 2, 4, 1, 3, 5)                # [K, a, b, C, 3, 3]
     return wp.reshape(K, S * S * C, 3, 3).contiguous()
-
-
-def _wino_weights_kxk(weight, transposed=False):
-    """``transposed``: the filter of the input-gradient convolution, weight[k, c, a, b] -> [c, k, K-1-a, K-1-b]."""
-    def make():
-        w = weight.detach()
-        w = _block3x3_weight(w.transpose(0, 1).flip(2, 3).contiguous() if transposed else w)
-        K, C = w.shape[0], w.shape[1]
-        L = _native.lib()
-        U = _registered(torch.empty(L.tai_conv3x3_wino_weight_floats(K, C), dtype=torch.float32, device=w.device))
-        with torch.cuda.device(w.device):
-            _native.check(L.tai_conv3x3_wino_transform_weights(w.data_ptr(), U.data_ptr(), K, C,
-                                                               torch.cuda.current_stream(w.device).cuda_stream),
-                          'tai_conv3x3_wino_transform_weights')
-        return U
-    return _cached(weight, ('wino_kxk', transposed, _WINO_ARITH[0]), make)
-
-
-def _wino43_weights_kxk(weight, transposed=False):
-    """The k x k filter as S x S blocks of 3 x 3 taps in the F(4x4, 3x3) layout (tai_conv3x3_wino43_forward_blocks); ``transposed``: the
-    filter of the input-gradient convolution, weight[k, c, a, b] -> [c, k, K-1-a, K-1-b]."""
-    def make():
-        w = weight.detach()
-        w = _block3x3_weight(w.transpose(0, 1).flip(2, 3).contiguous() if transposed else w)
-        K, C = w.shape[0], w.shape[1]
-        L = _native.lib()
-        U = torch.empty(L.tai_conv3x3_wino43_weight_floats(K, C), dtype=torch.float32, device=w.device)
-        with torch.cuda.device(w.device):
-            _native.check(L.tai_conv3x3_wino43_transform_weights(w.data_ptr(), U.data_ptr(), K, C,
-                                                                 torch.cuda.current_stream(w.device).cuda_stream),
-                          'tai_conv3x3_wino43_transform_weights')
-        return U
-    return _cached(weight, ('wino43_kxk', transposed), make)
 
 
 def _wino43_blocks_ok(N, Cin, Co, H, W):
@@ -348,11 +297,8 @@ def _kxk_as_blocks(x, weight, bias, act, transposed=False):
     plane = halo_plane(N, C, H, W, k, x.device)
     plane[:, :, top:top + H, left:left + W].copy_(x)
     y = torch.empty((N, K, H, W), dtype=x.dtype, device=x.device)
-    with torch.cuda.device(x.device):
-        _native.check(_native.lib().tai_conv3x3_wino43_forward_blocks(
-            plane.data_ptr(), k, _wino43_weights_kxk(weight, transposed).data_ptr(), bias.data_ptr(), y.data_ptr(), None, 0, 0, 0, 0,
-            N, S * S * C, K, H, W, in_h, in_w, 1, 2, _ACT[act], torch.cuda.current_stream(x.device).cuda_stream),
-            'tai_conv3x3_wino43_forward_blocks')
+    _native.launch('tai_conv3x3_wino43_forward_blocks', x.device, plane, k, _transformed_weights(weight, transposed, 4, blocks=True), bias,
+                   y, None, 0, 0, 0, 0, N, S * S * C, K, H, W, in_h, in_w, 1, 2, _ACT[act])
     return y
 
 
@@ -363,18 +309,13 @@ def _kxk_as_wino(x, weight, bias, act, pool, transposed=False, keep_stack=False)
     N, C, H, W = x.shape
     K, k = weight.shape[1 if transposed else 0], weight.shape[2]
     S = (k + 2) // 3
-    L = _native.lib()
-    stream = torch.cuda.current_stream(x.device).cuda_stream
     x = x.contiguous()
     stack = torch.empty((N, S * S * C, H + 2, W + 4), dtype=x.dtype, device=x.device)     # shifted copies, own halo
     U = _wino_weights_kxk(weight, transposed)
     y = torch.empty((N, K, H, W), dtype=x.dtype, device=x.device)
     yp = torch.empty((N, K, H // 2, W // 2), dtype=x.dtype, device=x.device) if pool else None
-    with torch.cuda.device(x.device):
-        _native.check(L.tai_conv_shift_stack(x.data_ptr(), stack.data_ptr(), N, C, H, W, k, stream), 'tai_conv_shift_stack')
-        _native.check(L.tai_conv3x3_wino_forward_window(stack.data_ptr(), U.data_ptr(), bias.data_ptr(), y.data_ptr(),
-                                                        yp.data_ptr() if pool else None, N, S * S * C, K, H, W, H + 2, W + 4,
-                                                        1, 2, _ACT[act], stream), 'tai_conv3x3_wino_forward_window')
+    _native.launch('tai_conv_shift_stack', x.device, x, stack, N, C, H, W, k)
+    _native.launch('tai_conv3x3_wino_forward_window', x.device, stack, U, bias, y, yp, N, S * S * C, K, H, W, H + 2, W + 4, 1, 2, _ACT[act])
     if keep_stack:
         return y, stack
     return (y, yp) if pool else y
@@ -443,9 +384,7 @@ def motion_enc_chain(diff, conv1, conv2, conv3):
     if not (_wino_ok(N, S2 * S2 * g, 2 * g, H2, W2, 3, 3, 1) and _wino_ok(N, S3 * S3 * 2 * g, 4 * g, H4, W4, 3, 3, 1)
             and N * g * ih2 * iw2 < 2 ** 29 and N * 2 * g * ih3 * iw3 < 2 ** 29 and N * g * H * W < 2 ** 29):
         return None
-    L = _native.lib()
     dev = diff.device
-    stream = torch.cuda.current_stream(dev).cuda_stream
     diff = diff.contiguous()
     c1 = torch.empty((N, g, H, W), dtype=torch.float32, device=dev)
     c2 = torch.empty((N, 2 * g, H2, W2), dtype=torch.float32, device=dev)
@@ -457,70 +396,21 @@ def motion_enc_chain(diff, conv1, conv2, conv3):
     U3 = None if _wino43_blocks_ok(N, 2 * g, 4 * g, H4, W4) else _wino_weights_kxk(ws[2])
     xs2 = (ctypes.c_void_p * 1)(plane2.data_ptr())
     xs3 = (ctypes.c_void_p * 1)(plane3.data_ptr())
-    with torch.cuda.device(dev):
-        _native.check(L.tai_conv_cin1_forward_maxpool_window(diff.data_ptr(), ws[0].contiguous().data_ptr(), bs[0].data_ptr(),
-                                                            c1.data_ptr(), plane2.data_ptr(), N, g, H, W, 5, 1, ih2, iw2, top2, left2,
-                                                            stream), 'tai_conv_cin1_forward_maxpool_window')
-        if _wino43_blocks_ok(N, g, 2 * g, H2, W2):               # the 4 x 4 tile (set_winograd_tile): 1.78x fewer MFMAs
-            _native.check(L.tai_conv3x3_wino43_forward_blocks(plane2.data_ptr(), 5, _wino43_weights_kxk(ws[1]).data_ptr(), bs[1].data_ptr(),
-                                                             c2.data_ptr(), plane3.data_ptr(), ih3, iw3, top3, left3, N, S2 * S2 * g, 2 * g,
-                                                             H2, W2, ih2, iw2, 1, 2, 1, stream), 'tai_conv3x3_wino43_forward_blocks')
-        else:
-            _native.check(L.tai_conv3x3_wino_forward_ex(xs2, 1, 5, U2.data_ptr(), bs[1].data_ptr(), c2.data_ptr(), plane3.data_ptr(),
-                                                       ih3, iw3, top3, left3, None, None, N, S2 * S2 * g, 2 * g, H2, W2, ih2, iw2, 1, 2, 1,
-                                                       stream), 'tai_conv3x3_wino_forward_ex')
-        if _wino43_blocks_ok(N, 2 * g, 4 * g, H4, W4):
-            _native.check(L.tai_conv3x3_wino43_forward_blocks(plane3.data_ptr(), 7, _wino43_weights_kxk(ws[2]).data_ptr(), bs[2].data_ptr(),
-                                                             c3.data_ptr(), p3.data_ptr(), 0, 0, 0, 0, N, S3 * S3 * 2 * g, 4 * g,
-                                                             H4, W4, ih3, iw3, 1, 2, 1, stream), 'tai_conv3x3_wino43_forward_blocks')
-        else:
-            _native.check(L.tai_conv3x3_wino_forward_ex(xs3, 1, 7, U3.data_ptr(), bs[2].data_ptr(), c3.data_ptr(), p3.data_ptr(),
-                                                       0, 0, 0, 0, None, None, N, S3 * S3 * 2 * g, 4 * g, H4, W4, ih3, iw3, 1, 2, 1,
-                                                       stream), 'tai_conv3x3_wino_forward_ex')
+    _native.launch('tai_conv_cin1_forward_maxpool_window', dev, diff, ws[0].contiguous(), bs[0], c1, plane2, N, g, H, W, 5, 1,
+                   ih2, iw2, top2, left2)
+    if _wino43_blocks_ok(N, g, 2 * g, H2, W2):               # the 4 x 4 tile (set_winograd_tile): 1.78x fewer MFMAs
+        _native.launch('tai_conv3x3_wino43_forward_blocks', dev, plane2, 5, _transformed_weights(ws[1], False, 4, blocks=True), bs[1],
+                       c2, plane3, ih3, iw3, top3, left3, N, S2 * S2 * g, 2 * g, H2, W2, ih2, iw2, 1, 2, 1)
+    else:
+        _native.launch('tai_conv3x3_wino_forward_ex', dev, xs2, 1, 5, U2, bs[1], c2, plane3, ih3, iw3, top3, left3, None, None,
+                       N, S2 * S2 * g, 2 * g, H2, W2, ih2, iw2, 1, 2, 1)
+    if _wino43_blocks_ok(N, 2 * g, 4 * g, H4, W4):
+        _native.launch('tai_conv3x3_wino43_forward_blocks', dev, plane3, 7, _transformed_weights(ws[2], False, 4, blocks=True), bs[2],
+                       c3, p3, 0, 0, 0, 0, N, S3 * S3 * 2 * g, 4 * g, H4, W4, ih3, iw3, 1, 2, 1)
+    else:
+        _native.launch('tai_conv3x3_wino_forward_ex', dev, xs3, 1, 7, U3, bs[2], c3, p3, 0, 0, 0, 0, None, None,
+                       N, S3 * S3 * 2 * g, 4 * g, H4, W4, ih3, iw3, 1, 2, 1)
     return p3, [c1, c2, c3]
-
-
-def conv_bias_unpool_add(x, weight, bias, padding, addx, keep_plain=True):
-    """(y, y + fixed_unpooling(addx)) with y = conv(x) + bias, no activation: the last convolution of a Residual block
-    (mcnet.py:172-176) and DecCnn's unpool + residual add (mcnet.py:234-236) -- a Winograd tile is one unpooling cell, so
-    the sum is a second output of the convolution's epilogue.  ``x`` may be a tuple of cat operands.  ``keep_plain=False``:
-    only the sum is produced (returns (None, sum)): nothing reads the full-resolution residual itself."""
-    parts = list(x) if isinstance(x, (list, tuple)) else [x]
-    x0 = parts[0]
-    Co, Ci, kh, kw = weight.shape
-    N, Cp, H, W = x0.shape
-    if (x0.is_cuda and x0.dtype == torch.float32 and bias is not None and addx.is_cuda and addx.dtype == torch.float32
-            and tuple(addx.shape) == (N, Co, H // 2, W // 2) and H % 2 == 0 and W % 2 == 0 and len(parts) <= 4 and Cp * len(parts) == Ci
-            and all(q.shape == x0.shape and q.dtype == x0.dtype for q in parts)
-            and _bf16_route(Ci, Co, kh, kw, padding, weight, bias, addx, *parts)):
-        return _bf16_conv(parts, weight, bias, None, addx=addx, keep_plain=keep_plain)
-    fused = (x0.is_cuda and x0.dtype == torch.float32 and bias is not None and addx.is_cuda and addx.dtype == torch.float32
-             and tuple(addx.shape) == (N, Co, H // 2, W // 2) and len(parts) <= 4 and Cp * len(parts) == Ci
-             and (len(parts) == 1 or Cp % 8 == 0) and all(q.shape == x0.shape and q.dtype == x0.dtype for q in parts)
-             and _no_grad_needed(weight, bias, addx, *parts) and _wino_ok(N, Ci, Co, H, W, kh, kw, padding)
-             and N * Co * H * W < 2 ** 29)
-    if not fused:
-        from .mcnet import unpool2x_add
-        y = conv_bias_act(x, weight, bias, padding, None)
-        return (y if keep_plain else None), unpool2x_add(addx, y)
-    L = _native.lib()
-    parts = [q.contiguous() for q in parts]
-    addx = addx.contiguous()
-    y = torch.empty((N, Co, H, W), dtype=torch.float32, device=x0.device)
-    y2 = torch.empty_like(y) if keep_plain else None
-    ptrs = (ctypes.c_void_p * len(parts))(*[q.data_ptr() for q in parts])
-    if _wino43_ok(N, Ci, Co, H, W, len(parts), weight):      # wide layer: F(4x4, 3x3) (set_winograd_tile): a tile holds four unpooling cells
-        U = _wino43_weights(weight, False)
-        with torch.cuda.device(x0.device):
-            _wino43_launch(ptrs, len(parts), U, bias, y, N, Ci, Co, H, W, 0, torch.cuda.current_stream(x0.device).cuda_stream, weight,
-                           addx=addx, y2=y2 if keep_plain else None)
-        return (y, y2) if keep_plain else (None, y)
-    U = _wino_weights(weight, False)
-    with torch.cuda.device(x0.device):
-        _native.check(L.tai_conv3x3_wino_forward_ex(ptrs, len(parts), 0, U.data_ptr(), bias.data_ptr(), y.data_ptr(), None, 0, 0, 0, 0,
-                                                   addx.data_ptr(), y2.data_ptr() if keep_plain else None, N, Ci, Co, H, W, H, W, 0, 0, 0,
-                                                   torch.cuda.current_stream(x0.device).cuda_stream), 'tai_conv3x3_wino_forward_ex')
-    return (y, y2) if keep_plain else (None, y)
 
 
 def _kxk_ok(N, Ci, Co, H, W, kh, kw, padding):
@@ -573,21 +463,19 @@ def _usable_out(out, shape, like):
             and out.device == like.device)
 
 
-def _wino_forward(L, x, U, bias, y, N, Ci, Co, H, W, act, stream):
+def _wino_forward(x, U, bias, y, N, Ci, Co, H, W, act):
     """tai_conv3x3_wino_forward; a plane with an odd side through the general entry (tai_conv3x3_wino_forward_ex), which takes it"""
     if H % 2 == 0 and W % 2 == 0:
-        _native.check(L.tai_conv3x3_wino_forward(x.data_ptr(), U.data_ptr(), bias.data_ptr(), y.data_ptr(), N, Ci, Co, H, W, _ACT[act],
-                                                 stream), 'tai_conv3x3_wino_forward')
+        _native.launch('tai_conv3x3_wino_forward', x.device, x, U, bias, y, N, Ci, Co, H, W, _ACT[act])
     else:
         xs = (ctypes.c_void_p * 1)(x.data_ptr())
-        _native.check(L.tai_conv3x3_wino_forward_ex(xs, 1, 0, U.data_ptr(), bias.data_ptr(), y.data_ptr(), None, 0, 0, 0, 0, None, None,
-                                                   N, Ci, Co, H, W, H, W, 0, 0, _ACT[act], stream), 'tai_conv3x3_wino_forward_ex')
+        _native.launch('tai_conv3x3_wino_forward_ex', x.device, xs, 1, 0, U, bias, y, None, 0, 0, 0, 0, None, None,
+                       N, Ci, Co, H, W, H, W, 0, 0, _ACT[act])
 
 
 def _wino_launch(x, U, bias, N, Ci, Co, H, W, act):
     y = torch.empty((N, Co, H, W), dtype=x.dtype, device=x.device)
-    with torch.cuda.device(x.device):
-        _wino_forward(_native.lib(), x, U, bias, y, N, Ci, Co, H, W, act, torch.cuda.current_stream(x.device).cuda_stream)
+    _wino_forward(x, U, bias, y, N, Ci, Co, H, W, act)
     return y
 
 
@@ -601,12 +489,10 @@ def _conv3x3_autograd_launch(x, weight, eff_transposed, bias, N, Ci, Co, H, W, a
     """conv(x, w_eff) with w_eff = the weight in orientation ``eff_transposed``: F(4x4, 3x3) where _wino43_ok says so, else F(2x2, 3x3)."""
     if WINO43_UNDER_AUTOGRAD and _wino43_ok(N, Ci, Co, H, W, 1, weight, split=False):
         y = torch.empty((N, Co, H, W), dtype=x.dtype, device=x.device)
-        with torch.cuda.device(x.device):
-            _native.check(_native.lib().tai_conv3x3_wino43_forward(x.data_ptr(), _wino43_weights(weight, eff_transposed).data_ptr(), bias.data_ptr(),
-                                                                  y.data_ptr(), N, Ci, Co, H, W, _ACT[act],
-                                                                  torch.cuda.current_stream(x.device).cuda_stream), 'tai_conv3x3_wino43_forward')
+        _native.launch('tai_conv3x3_wino43_forward', x.device, x, _transformed_weights(weight, eff_transposed, 4), bias, y,
+                       N, Ci, Co, H, W, _ACT[act])
         return y
-    return _wino_launch(x, _wino_weights(weight, eff_transposed), bias, N, Ci, Co, H, W, act)
+    return _wino_launch(x, _transformed_weights(weight, eff_transposed, 2), bias, N, Ci, Co, H, W, act)
 
 
 def wino_conv3x3_plain(x, weight, transposed=False):
@@ -686,16 +572,11 @@ def wino_weight_grad(x, grad_out, with_bias=False, window=None, ragged=False):
     ws = _WRW_WORKSPACE.get(x.device, floats)
     dw = torch.empty((Co, Ci, 3, 3), dtype=torch.float32, device=x.device)
     db = torch.empty(Co, dtype=torch.float32, device=x.device) if with_bias else None
-    with torch.cuda.device(x.device):
-        stream = torch.cuda.current_stream(x.device).cuda_stream
-        if window is None:
-            _native.check(L.tai_conv3x3_wino_wrw(x.data_ptr(), grad_out.data_ptr(), dw.data_ptr(), db.data_ptr() if with_bias else None,
-                                                 ws.data_ptr(), N, Ci, Co, H, W, stream), 'tai_conv3x3_wino_wrw')
-        else:
-            _native.check(L.tai_conv3x3_wino_wrw_window(x.data_ptr(), grad_out.data_ptr(), dw.data_ptr(),
-                                                        db.data_ptr() if with_bias else None, ws.data_ptr(), N, Ci, Co, H, W,
-                                                        x.shape[2], x.shape[3], window[0], window[1], stream),
-                          'tai_conv3x3_wino_wrw_window')
+    if window is None:
+        _native.launch('tai_conv3x3_wino_wrw', x.device, x, grad_out, dw, db, ws, N, Ci, Co, H, W)
+    else:
+        _native.launch('tai_conv3x3_wino_wrw_window', x.device, x, grad_out, dw, db, ws, N, Ci, Co, H, W,
+                       x.shape[2], x.shape[3], window[0], window[1])
     return (dw, db) if with_bias else dw
 
 
@@ -763,18 +644,14 @@ class _WinoConv3x3Parts(torch.autograd.Function):
         x0 = parts[0]
         Co, Ci = (weight.shape[1], weight.shape[0]) if transposed else (weight.shape[0], weight.shape[1])
         N, Cp, H, W = x0.shape
-        L = _native.lib()
         y = torch.empty((N, Co, H, W), dtype=x0.dtype, device=x0.device)
         ptrs = (ctypes.c_void_p * len(parts))(*[p.data_ptr() for p in parts])
-        with torch.cuda.device(x0.device):
-            if WINO43_UNDER_AUTOGRAD and _wino43_ok(N, Ci, Co, H, W, len(parts), weight, split=False):
-                _native.check(L.tai_conv3x3_wino43_forward_parts(ptrs, len(parts), _wino43_weights(weight, transposed).data_ptr(), bias.data_ptr(),
-                                                                 y.data_ptr(), N, Ci, Co, H, W, _ACT[act],
-                                                                 torch.cuda.current_stream(x0.device).cuda_stream), 'tai_conv3x3_wino43_forward_parts')
-            else:
-                _native.check(L.tai_conv3x3_wino_forward_parts(ptrs, len(parts), _wino_weights(weight, transposed).data_ptr(), bias.data_ptr(),
-                                                               y.data_ptr(), N, Ci, Co, H, W, _ACT[act],
-                                                               torch.cuda.current_stream(x0.device).cuda_stream), 'tai_conv3x3_wino_forward_parts')
+        if WINO43_UNDER_AUTOGRAD and _wino43_ok(N, Ci, Co, H, W, len(parts), weight, split=False):
+            _native.launch('tai_conv3x3_wino43_forward_parts', x0.device, ptrs, len(parts), _transformed_weights(weight, transposed, 4), bias, y,
+                           N, Ci, Co, H, W, _ACT[act])
+        else:
+            _native.launch('tai_conv3x3_wino_forward_parts', x0.device, ptrs, len(parts), _transformed_weights(weight, transposed, 2), bias, y,
+                           N, Ci, Co, H, W, _ACT[act])
         ctx.act, ctx.transposed, ctx.nparts = act, transposed, len(parts)
         ctx.save_for_backward(weight, y if act is not None else None, *parts)
         return y
@@ -795,11 +672,8 @@ class _WinoConv3x3Parts(torch.autograd.Function):
             if ctx.needs_input_grad[4 + i]:
                 if WINO43_UNDER_AUTOGRAD and _wino43_ok(N, Co, Cp, H, W, 1, weight, split=False):
                     gparts[i] = torch.empty((N, Cp, H, W), dtype=g.dtype, device=g.device)
-                    with torch.cuda.device(g.device):
-                        _native.check(_native.lib().tai_conv3x3_wino43_forward(
-                            g.data_ptr(), _wino_weights_input_grad_part(weight, ctx.transposed, i, n, tile=4).data_ptr(),
-                            _zero_bias(Cp, g.device).data_ptr(), gparts[i].data_ptr(), N, Co, Cp, H, W, 0,
-                            torch.cuda.current_stream(g.device).cuda_stream), 'tai_conv3x3_wino43_forward')
+                    _native.launch('tai_conv3x3_wino43_forward', g.device, g, _wino_weights_input_grad_part(weight, ctx.transposed, i, n, tile=4),
+                                   _zero_bias(Cp, g.device), gparts[i], N, Co, Cp, H, W, 0)
                 else:
                     gparts[i] = _wino_launch(g, _wino_weights_input_grad_part(weight, ctx.transposed, i, n), _zero_bias(Cp, g.device),
                                              N, Co, Cp, H, W, None)
@@ -834,17 +708,7 @@ def _wino_weights_input_grad_part(weight, transposed, i, nparts, tile=2):
     def make():
         w_eff = _as_conv_weight(weight.detach(), transposed)                              # [Co, Ci, 3, 3]
         Cp = w_eff.shape[1] // nparts
-        w = w_eff[:, i * Cp:(i + 1) * Cp].transpose(0, 1).flip(2, 3).contiguous()          # [Cp, Co, 3, 3]
-        K, C = w.shape[0], w.shape[1]
-        L = _native.lib()
-        pre = 'tai_conv3x3_wino43' if tile == 4 else 'tai_conv3x3_wino'
-        U = torch.empty(getattr(L, pre + '_weight_floats')(K, C), dtype=torch.float32, device=w.device)
-        if tile == 2:
-            _registered(U)
-        with torch.cuda.device(w.device):
-            _native.check(getattr(L, pre + '_transform_weights')(w.data_ptr(), U.data_ptr(), K, C, torch.cuda.current_stream(w.device).cuda_stream),
-                          pre + '_transform_weights')
-        return U
+        return _transform(w_eff[:, i * Cp:(i + 1) * Cp].transpose(0, 1).flip(2, 3).contiguous(), tile)   # [Cp, Co, 3, 3]
     return _cached(weight, ('wino_input_grad_part', transposed, i, nparts, tile, _WINO_ARITH[0]), make)
 
 
@@ -893,9 +757,7 @@ class _WinoConvKxK(torch.autograd.Function):
                 N, _, H, W = x.shape
                 S = (k + 2) // 3
                 stack = torch.empty((N, S * S * Ci, H + 2, W + 4), dtype=x.dtype, device=x.device)
-                with torch.cuda.device(x.device):
-                    _native.check(_native.lib().tai_conv_shift_stack(x.data_ptr(), stack.data_ptr(), N, Ci, H, W, k,
-                                                                     torch.cuda.current_stream(x.device).cuda_stream), 'tai_conv_shift_stack')
+                _native.launch('tai_conv_shift_stack', x.device, x, stack, N, Ci, H, W, k)
             # the weight gradient of the blocked 3x3 form over the stack (it carries its halo: origin (1, 2)), then un-blocked
             both = wino_weight_grad(stack, g, with_bias=True, window=(1, 2), ragged=True)
             if both is not None:
@@ -918,10 +780,7 @@ def thin_weight_grad(big, thin, k):
     ws = _THIN_WORKSPACE.get(big.device, N * Cb * 32)
     dw = torch.empty((Cb, k, k), dtype=torch.float32, device=big.device)
     db = torch.empty(Cb, dtype=torch.float32, device=big.device)
-    with torch.cuda.device(big.device):
-        _native.check(_native.lib().tai_thin_conv_wrw(big.data_ptr(), thin.data_ptr(), dw.data_ptr(), db.data_ptr(), ws.data_ptr(),
-                                                      N, Cb, H, W, k, torch.cuda.current_stream(big.device).cuda_stream),
-                      'tai_thin_conv_wrw')
+    _native.launch('tai_thin_conv_wrw', big.device, big, thin, dw, db, ws, N, Cb, H, W, k)
     return dw, db
 
 
@@ -936,10 +795,7 @@ class _ThinInConv(torch.autograd.Function):
         N, _, H, W = x.shape
         Co, k = weight.shape[0], weight.shape[2]
         y = torch.empty((N, Co, H, W), dtype=x.dtype, device=x.device)
-        with torch.cuda.device(x.device):
-            _native.check(_native.lib().tai_conv_cin1_forward(x.data_ptr(), weight.detach().contiguous().data_ptr(), bias.data_ptr(),
-                                                              y.data_ptr(), N, Co, H, W, k, _ACT[act],
-                                                              torch.cuda.current_stream(x.device).cuda_stream), 'tai_conv_cin1_forward')
+        _native.launch('tai_conv_cin1_forward', x.device, x, weight.detach().contiguous(), bias, y, N, Co, H, W, k, _ACT[act])
         ctx.act = act
         ctx.save_for_backward(x, weight, y if act is not None else None)
         return y
@@ -955,17 +811,12 @@ class _ThinInConv(torch.autograd.Function):
         if ctx.needs_input_grad[0]:
             # (the frame difference of an autoregressive step is itself generated)
             N, _, H, W = x.shape
-            L = _native.lib()
-            stream = torch.cuda.current_stream(x.device).cuda_stream
             wf = weight.detach().flip(2, 3).transpose(0, 1).contiguous()                 # [1, Co, k, k]: the filter flipped
             gx = torch.empty_like(x)
-            with torch.cuda.device(x.device):
-                if k == 5:
-                    _native.check(L.tai_conv_cout1_5x5_forward(g.data_ptr(), wf.data_ptr(), None, gx.data_ptr(), N, Co, H, W, stream),
-                                  'tai_conv_cout1_5x5_forward')
-                else:
-                    _native.check(L.tai_conv_cout1_3x3_forward(g.data_ptr(), wf.data_ptr(), _zero_bias(1, x.device).data_ptr(),
-                                                               gx.data_ptr(), N, Co, H, W, 0, stream), 'tai_conv_cout1_3x3_forward')
+            if k == 5:
+                _native.launch('tai_conv_cout1_5x5_forward', x.device, g, wf, None, gx, N, Co, H, W)
+            else:
+                _native.launch('tai_conv_cout1_3x3_forward', x.device, g, wf, _zero_bias(1, x.device), gx, N, Co, H, W, 0)
         if ctx.needs_input_grad[1] or ctx.needs_input_grad[2]:
             dw, gb = thin_weight_grad(g, x, k)
             gw = dw.view_as(weight)
@@ -983,10 +834,7 @@ class _ThinOutConv(torch.autograd.Function):
         N, Ci, H, W = x.shape
         wd = _cached(weight, ('direct', transposed), lambda: _as_conv_weight(weight.detach(), transposed).contiguous())   # [1, Ci, 3, 3]
         y = torch.empty((N, 1, H, W), dtype=x.dtype, device=x.device)
-        with torch.cuda.device(x.device):
-            _native.check(_native.lib().tai_conv_cout1_3x3_forward(x.data_ptr(), wd.data_ptr(), bias.data_ptr(), y.data_ptr(), N, Ci,
-                                                                   H, W, _ACT[act], torch.cuda.current_stream(x.device).cuda_stream),
-                          'tai_conv_cout1_3x3_forward')
+        _native.launch('tai_conv_cout1_3x3_forward', x.device, x, wd, bias, y, N, Ci, H, W, _ACT[act])
         ctx.act, ctx.transposed = act, transposed
         ctx.save_for_backward(x, weight, y if act is not None else None)
         return y
@@ -1007,10 +855,7 @@ class _ThinOutConv(torch.autograd.Function):
             wf = wd.flip(2, 3).transpose(0, 1).contiguous()                           # [Ci, 1, 3, 3]
             gx = torch.empty_like(x)
             zero = _zero_bias(Ci, x.device)
-            with torch.cuda.device(x.device):
-                _native.check(_native.lib().tai_conv_cin1_forward(g.data_ptr(), wf.data_ptr(), zero.data_ptr(), gx.data_ptr(), N, Ci, H,
-                                                                  W, 3, 0, torch.cuda.current_stream(x.device).cuda_stream),
-                              'tai_conv_cin1_forward')
+            _native.launch('tai_conv_cin1_forward', x.device, g, wf, zero, gx, N, Ci, H, W, 3, 0)
         if ctx.needs_input_grad[1]:
             # dwd[0][c][a][b] = sum g[y, x] x_c[y + a - 1, x + b - 1] = thin_weight_grad(x, g)[c][2 - a][2 - b]
             dwd = thin_weight_grad(x, g, 3)[0].flip(1, 2).unsqueeze(0)               # [1, Ci, 3, 3] in conv2d layout
@@ -1030,10 +875,7 @@ class _ActPool2x2(torch.autograd.Function):
         N, C, H, W = z.shape
         y = torch.empty_like(z)
         yp = torch.empty((N, C, H // 2, W // 2), dtype=z.dtype, device=z.device)
-        with torch.cuda.device(z.device):
-            _native.check(_native.lib().tai_act_maxpool2x2_forward(z.data_ptr(), y.data_ptr(), yp.data_ptr(), N * C, H, W, int(relu),
-                                                                   torch.cuda.current_stream(z.device).cuda_stream),
-                          'tai_act_maxpool2x2_forward')
+        _native.launch('tai_act_maxpool2x2_forward', z.device, z, y, yp, N * C, H, W, int(relu))
         ctx.relu = bool(relu)
         ctx.save_for_backward(y)
         return y, yp
@@ -1045,58 +887,206 @@ class _ActPool2x2(torch.autograd.Function):
         gy = gy.contiguous() if gy is not None else None
         gyp = gyp.contiguous() if gyp is not None else None
         gz = torch.empty_like(y)
-        with torch.cuda.device(y.device):
-            _native.check(_native.lib().tai_act_maxpool2x2_backward(gy.data_ptr() if gy is not None else None,
-                                                                    gyp.data_ptr() if gyp is not None else None, y.data_ptr(),
-                                                                    gz.data_ptr(), N * C, H, W, int(ctx.relu),
-                                                                    torch.cuda.current_stream(y.device).cuda_stream),
-                          'tai_act_maxpool2x2_backward')
+        _native.launch('tai_act_maxpool2x2_backward', y.device, gy, gyp, y, gz, N * C, H, W, int(ctx.relu))
         return gz, None
+
+
+class _Layer(object):
+    """What one convolution call is -- asked once, for conv_route and for the launch that follows.  ``x``: a tensor or a list / tuple of up
+    to four channel parts (``listed``); ``addx``: the tensor conv_bias_unpool_add unpools into the sum."""
+    __slots__ = ('parts', 'listed', 'x0', 'weight', 'bias', 'padding', 'act', 'transposed', 'addx', 'Ci', 'Co', 'kh', 'kw',
+                 'N', 'Cp', 'H', 'W', 'cuda_fp32', 'native')
+
+    def __init__(self, x, weight, bias, padding, act, transposed=False, addx=None):
+        self.listed = isinstance(x, (list, tuple))
+        self.parts = list(x) if self.listed else [x]
+        x0 = self.x0 = self.parts[0]
+        self.weight, self.bias, self.padding, self.act, self.transposed, self.addx = weight, bias, padding, act, transposed, addx
+        self.Co, self.Ci = (weight.shape[1], weight.shape[0]) if transposed else (weight.shape[0], weight.shape[1])
+        self.kh, self.kw = weight.shape[2], weight.shape[3]
+        self.cuda_fp32 = torch.is_tensor(x0) and x0.is_cuda and x0.dtype == torch.float32
+        self.native = self.cuda_fp32 and bias is not None          # what every in-tree kernel needs: cuda, fp32, a bias
+        # (a CPU tensor is never unpacked: it goes to ATen in whatever shape ATen takes)
+        self.N, self.Cp, self.H, self.W = x0.shape if self.cuda_fp32 or self.listed or addx is not None else (None,) * 4
+
+    def parts_fit(self):
+        """at most four parts of one shape and dtype that make up the weight's input channels"""
+        x0, n = self.x0, len(self.parts)
+        return n <= 4 and self.Cp * n == self.Ci and all(p.shape == x0.shape and p.dtype == x0.dtype for p in self.parts)
+
+    def parts_in_place(self):
+        """... that the Winograd kernels read where they lie"""
+        return self.parts_fit() and self.Cp % 8 == 0 and all(p.is_contiguous() for p in self.parts)
+
+    def addx_fits(self):
+        a = self.addx
+        return a.is_cuda and a.dtype == torch.float32 and tuple(a.shape) == (self.N, self.Co, self.H // 2, self.W // 2)
+
+    def no_grad(self):
+        """no gradient is needed under the current grad mode"""
+        return _no_grad_needed(self.weight, self.bias, self.addx, *self.parts)
+
+    def bf16(self):
+        """the bf16 kernel takes it (bf16 mode, no gradient needed, a layer _bf16_ok takes)"""
+        return (_CONV_PREC[0] == 'bf16' and self.native and self.parts_fit()
+                and _bf16_route(self.Ci, self.Co, self.kh, self.kw, self.padding, self.weight, self.bias, self.addx, *self.parts))
+
+    def thin_in(self):
+        """one input channel: csrc/thin_conv.hip.inc streams the wide output"""
+        return self.Ci == 1 and self.kh == self.kw and self.kh in (3, 5) and self.padding == self.kh // 2 and self.Co >= 16
+
+    def thin_out(self):
+        return self.Co == 1 and self.kh == self.kw == 3 and self.padding == 1 and self.Ci >= 16
+
+
+# route name -> what runs (DESIGN.md, "Convolution dispatch", has the conditions)
+ROUTES = {
+    'bf16': 'tai_conv_bf16_forward (_bf16_conv), every epilogue',
+    'thin_in': 'tai_conv_cin1_forward / tai_conv_cin1_forward_maxpool',
+    'thin_out': 'tai_conv_cout1_3x3_forward',
+    'kxk': 'tai_conv_shift_stack + tai_conv3x3_wino_forward_window (_kxk_as_wino)',
+    'wino43': 'F(4x4, 3x3): tai_conv3x3_wino43_forward_ws (_wino43_launch), every epilogue, 1-4 parts',
+    'wino': 'F(2x2, 3x3): tai_conv3x3_wino_forward / _forward_maxpool / _forward_ex (unpool_add)',
+    'wino_odd': 'F(2x2, 3x3) on a plane with an odd side: tai_conv3x3_wino_forward_ex',
+    'wino_parts': 'F(2x2, 3x3) over 2-4 parts: tai_conv3x3_wino_forward_parts',
+    'miopen': 'F.conv2d without bias + tai_bias_act_inplace',
+    'cat': 'torch.cat of the parts, then the route of the concatenation',
+    'autograd_3x3': '_WinoConv3x3', 'autograd_parts': '_WinoConv3x3Parts', 'autograd_kxk': '_WinoConvKxK',
+    'autograd_thin_in': '_ThinInConv', 'autograd_thin_out': '_ThinOutConv',
+    'aten': 'F.conv2d with bias + torch.relu / torch.tanh (CPU tensors, no bias, other dtypes, gradients no kernel takes)',
+    'act_pool': 'pool: conv_bias_act without activation, then _ActPool2x2',
+    'unfused': 'pool / unpool_add: conv_bias_act, then F.max_pool2d / unpool2x_add',
+}
+
+
+def conv_route(l, epilogue=None):
+    """The route (a key of ROUTES) of layer ``l`` (_Layer) with ``epilogue`` None (conv_bias_act), 'pool' (conv_bias_act_maxpool) or
+    'unpool_add' (conv_bias_unpool_add).  Needs no GPU.  _wino_ok and _wino43_ok are looked up in the module at every call and asked in
+    a fixed order, each at most once per question: tests replace them to route a small batch like a large one and count the answers."""
+    N, Ci, Co, H, W, kh, kw, padding, n = l.N, l.Ci, l.Co, l.H, l.W, l.kh, l.kw, l.padding, len(l.parts)
+    if epilogue == 'unpool_add':
+        if l.native and l.addx_fits():
+            if H % 2 == 0 and W % 2 == 0 and l.bf16():
+                return 'bf16'
+            if (l.parts_fit() and (n == 1 or l.Cp % 8 == 0) and l.no_grad() and _wino_ok(N, Ci, Co, H, W, kh, kw, padding)
+                    and N * Co * H * W < 2 ** 29):
+                return 'wino43' if _wino43_ok(N, Ci, Co, H, W, n, l.weight) else 'wino'     # a 4 x 4 tile holds four unpooling cells
+        return 'unfused'
+    if epilogue == 'pool':
+        if l.listed or not l.cuda_fp32:
+            return 'unfused'
+        if H % 2 == 0 and W % 2 == 0 and l.bf16():
+            return 'bf16'
+        if l.act in (None, 'relu') and H % 2 == 0 and W % 4 == 0:
+            if l.native and l.no_grad():
+                if l.thin_in():
+                    return 'thin_in'
+                if _kxk_ok(N, Ci, Co, H, W, kh, kw, padding):
+                    return 'kxk'
+                if _wino_ok(N, Ci, Co, H, W, kh, kw, padding):
+                    return 'wino43' if _wino43_ok(N, Ci, Co, H, W, 1, l.weight) else 'wino'    # a 4 x 4 tile is four pooling windows
+            if torch.is_grad_enabled():
+                # training: the convolution without its activation, then activation + pool as one Function (one backward pass for
+                # the pool's scatter, the sum of the two gradient paths into y and the ReLU mask)
+                return 'act_pool'
+        return 'unfused'
+    if l.bf16():
+        return 'bf16'
+    if l.listed:
+        if l.native and l.parts_in_place():
+            if l.no_grad() and _wino_ok(N, Ci, Co, H, W, kh, kw, padding, ragged=True):
+                return 'wino43' if _wino43_ok(N, Ci, Co, H, W, n, l.weight) else 'wino_parts'
+            if (kh == kw == 3 and torch.is_grad_enabled() and _wino_ok(N, Ci, Co, H, W, 3, 3, padding, ragged=True)
+                    and _wino_ok(N, Co, l.Cp, H, W, 3, 3, padding, ragged=True) and PARTS_UNDER_AUTOGRAD):
+                return 'autograd_parts'                      # training: the parts are read where they lie
+        return 'cat'
+    if not l.native:
+        return 'aten'
+    if not l.no_grad():
+        if kh == kw == 3:
+            # (min_ci 2: the 3-channel layers of c_dim 3 -- ContentEnc's first, DecCnn's last -- run in-tree too: their input / output
+            # gradient is a convolution with 3 output / input channels, padded to one 64-channel block; MIOpen's kernels sum with atomics)
+            mc = 2 if RAGGED_ROUTES[0] else 8
+            if _wino_ok(N, Ci, Co, H, W, 3, 3, padding, min_ci=mc, ragged=True) and _wino_ok(N, Co, Ci, H, W, 3, 3, padding, min_ci=mc, ragged=True):
+                return 'autograd_3x3'
+        if (not l.transposed and kh == kw and kh in (5, 7) and _kxk_ok(N, Ci, Co, H, W, kh, kh, padding)
+                and _kxk_ok(N, Co, Ci, H, W, kh, kh, padding)):
+            return 'autograd_kxk'
+        if W % 4 == 0 and l.thin_in() and not l.transposed and l.act in (None, 'relu'):
+            return 'autograd_thin_in'
+        if W % 4 == 0 and l.thin_out():
+            return 'autograd_thin_out'
+        return 'aten'
+    if W % 4 == 0 and l.thin_in() and l.act in (None, 'relu'):
+        return 'thin_in'
+    if W % 4 == 0 and l.thin_out():
+        return 'thin_out'
+    if not l.transposed and _kxk_ok(N, Ci, Co, H, W, kh, kw, padding):
+        return 'kxk'
+    if _wino_ok(N, Ci, Co, H, W, kh, kw, padding, min_ci=2, ragged=True):
+        if _wino43_ok(N, Ci, Co, H, W, 1, l.weight):
+            return 'wino43'
+        return 'wino' if H % 2 == 0 and W % 2 == 0 else 'wino_odd'
+    return 'miopen'
+
+
+def _part_pointers(parts):
+    return (ctypes.c_void_p * len(parts))(*[p.data_ptr() for p in parts])
+
+
+def conv_bias_unpool_add(x, weight, bias, padding, addx, keep_plain=True):
+    """(y, y + fixed_unpooling(addx)) with y = conv(x) + bias, no activation: the last convolution of a Residual block
+    (mcnet.py:172-176) and DecCnn's unpool + residual add (mcnet.py:234-236) -- a Winograd tile is one unpooling cell, so
+    the sum is a second output of the convolution's epilogue.  ``x`` may be a tuple of cat operands.  ``keep_plain=False``:
+    only the sum is produced (returns (None, sum)): nothing reads the full-resolution residual itself."""
+    l = _Layer(x, weight, bias, padding, None, addx=addx)
+    route = conv_route(l, 'unpool_add')
+    if route == 'bf16':
+        return _bf16_conv(l.parts, weight, bias, None, addx=addx, keep_plain=keep_plain)
+    if route == 'unfused':
+        from .mcnet import unpool2x_add
+        y = conv_bias_act(x, weight, bias, padding, None)
+        return (y if keep_plain else None), unpool2x_add(addx, y)
+    N, Ci, Co, H, W = l.N, l.Ci, l.Co, l.H, l.W
+    parts = [q.contiguous() for q in l.parts]
+    addx = addx.contiguous()
+    y = torch.empty((N, Co, H, W), dtype=torch.float32, device=l.x0.device)
+    y2 = torch.empty_like(y) if keep_plain else None
+    ptrs = _part_pointers(parts)
+    if route == 'wino43':
+        _wino43_launch(ptrs, len(parts), _transformed_weights(weight, False, 4), bias, y, N, Ci, Co, H, W, 0, weight, addx=addx, y2=y2)
+    else:
+        _native.launch('tai_conv3x3_wino_forward_ex', y.device, ptrs, len(parts), 0, _transformed_weights(weight, False, 2), bias, y,
+                       None, 0, 0, 0, 0, addx, y2, N, Ci, Co, H, W, H, W, 0, 0, 0)
+    return (y, y2) if keep_plain else (None, y)
 
 
 def conv_bias_act_maxpool(x, weight, bias, padding, act):
     """(y, max_pool2d(y, 2)) with y = conv_bias_act(x, ...): the kernels that own a whole 2x2 window per lane (Winograd,
     one-input-channel) write the pooled tensor in their epilogue instead of leaving a second pass over y to ATen."""
-    Co, Ci, kh, kw = weight.shape
-    if (torch.is_tensor(x) and x.is_cuda and x.dtype == torch.float32 and bias is not None and x.dim() == 4 and x.shape[1] == Ci
-            and x.shape[2] % 2 == 0 and x.shape[3] % 2 == 0 and _bf16_route(Ci, Co, kh, kw, padding, x, weight, bias)):
+    l = _Layer(x, weight, bias, padding, act)
+    route = conv_route(l, 'pool')
+    if route == 'bf16':
         return _bf16_conv([x], weight, bias, act, pool=True)
-    fused = (torch.is_tensor(x) and x.is_cuda and x.dtype == torch.float32 and bias is not None and act in (None, 'relu')
-             and x.shape[2] % 2 == 0 and x.shape[3] % 4 == 0
-             and not (torch.is_grad_enabled() and (x.requires_grad or weight.requires_grad or bias.requires_grad)))
-    if fused:
-        N, _, H, W = x.shape
-        L = _native.lib()
-        stream = torch.cuda.current_stream(x.device).cuda_stream
-        thin_in = Ci == 1 and kh == kw and kh in (3, 5) and padding == kh // 2 and Co >= 16
-        if not thin_in and _kxk_ok(N, Ci, Co, H, W, kh, kw, padding):
-            return _kxk_as_wino(x, weight, bias, act, True)
-        if thin_in or _wino_ok(N, Ci, Co, H, W, kh, kw, padding):
-            x = x.contiguous()
-            y = torch.empty((N, Co, H, W), dtype=x.dtype, device=x.device)
-            yp = torch.empty((N, Co, H // 2, W // 2), dtype=x.dtype, device=x.device)
-            with torch.cuda.device(x.device):
-                if thin_in:
-                    _native.check(L.tai_conv_cin1_forward_maxpool(x.data_ptr(), weight.contiguous().data_ptr(), bias.data_ptr(),
-                                                                  y.data_ptr(), yp.data_ptr(), N, Co, H, W, kh, _ACT[act], stream),
-                                  'tai_conv_cin1_forward_maxpool')
-                elif kh == kw == 3 and padding == 1 and _wino43_ok(N, Ci, Co, H, W, 1, weight):      # wide layer: F(4x4, 3x3): a tile is four pooling windows
-                    U = _wino43_weights(weight, False)
-                    xs = (ctypes.c_void_p * 1)(x.data_ptr())
-                    _wino43_launch(xs, 1, U, bias, y, N, Ci, Co, H, W, _ACT[act], stream, weight, ypool=yp)
-                else:
-                    U = _wino_weights(weight, False)
-                    _native.check(L.tai_conv3x3_wino_forward_maxpool(x.data_ptr(), U.data_ptr(), bias.data_ptr(), y.data_ptr(),
-                                                                     yp.data_ptr(), N, Ci, Co, H, W, _ACT[act], stream),
-                                  'tai_conv3x3_wino_forward_maxpool')
-            return y, yp
-    if (torch.is_tensor(x) and x.is_cuda and x.dtype == torch.float32 and act in (None, 'relu') and x.shape[2] % 2 == 0
-            and x.shape[3] % 4 == 0 and torch.is_grad_enabled()):
-        # training: the convolution without its activation, then activation + pool as one Function (one backward pass for
-        # the pool's scatter, the sum of the two gradient paths into y and the ReLU mask)
+    if route == 'kxk':
+        return _kxk_as_wino(x, weight, bias, act, True)
+    if route == 'act_pool':
         return _ActPool2x2.apply(conv_bias_act(x, weight, bias, padding, None), act == 'relu')
-    y = conv_bias_act(x, weight, bias, padding, act)
-    return y, F.max_pool2d(y, 2)
+    if route == 'unfused':
+        y = conv_bias_act(x, weight, bias, padding, act)
+        return y, F.max_pool2d(y, 2)
+    N, Ci, Co, H, W = l.N, l.Ci, l.Co, l.H, l.W
+    x = x.contiguous()
+    y = torch.empty((N, Co, H, W), dtype=x.dtype, device=x.device)
+    yp = torch.empty((N, Co, H // 2, W // 2), dtype=x.dtype, device=x.device)
+    if route == 'thin_in':
+        _native.launch('tai_conv_cin1_forward_maxpool', x.device, x, weight.contiguous(), bias, y, yp, N, Co, H, W, l.kh, _ACT[act])
+    elif route == 'wino43':
+        _wino43_launch(_part_pointers([x]), 1, _transformed_weights(weight, False, 4), bias, y, N, Ci, Co, H, W, _ACT[act], weight, ypool=yp)
+    else:
+        _native.launch('tai_conv3x3_wino_forward_maxpool', x.device, x, _transformed_weights(weight, False, 2), bias, y, yp,
+                       N, Ci, Co, H, W, _ACT[act])
+    return y, yp
 
 
 def conv_bias_act(x, weight, bias, padding, act, transposed=False, out=None):
@@ -1115,111 +1105,57 @@ def conv_bias_act(x, weight, bias, padding, act, transposed=False, out=None):
 
 
 def _conv_bias_act(x, weight, bias, padding, act, transposed, out):
-    if isinstance(x, (list, tuple)):
-        parts = list(x)
-        x0 = parts[0]
-        kh, kw = weight.shape[2], weight.shape[3]
-        Co, Ci = (weight.shape[1], weight.shape[0]) if transposed else (weight.shape[0], weight.shape[1])
-        N, Cp, H, W = x0.shape
-        if (len(parts) <= 4 and x0.is_cuda and x0.dtype == torch.float32 and bias is not None and Cp * len(parts) == Ci
-                and all(p.shape == x0.shape and p.dtype == x0.dtype for p in parts)
-                and _bf16_route(Ci, Co, kh, kw, padding, weight, bias, *parts)):
-            return _bf16_conv(parts, weight, bias, act, transposed, out)
-        direct = (len(parts) <= 4 and x0.is_cuda and x0.dtype == torch.float32 and bias is not None and Cp % 8 == 0
-                  and Cp * len(parts) == Ci and all(p.shape == x0.shape and p.is_contiguous() and p.dtype == x0.dtype for p in parts)
-                  and not (torch.is_grad_enabled() and (weight.requires_grad or bias.requires_grad or any(p.requires_grad for p in parts)))
-                  and _wino_ok(N, Ci, Co, H, W, kh, kw, padding, ragged=True))
-        if not direct:
-            if (len(parts) <= 4 and x0.is_cuda and x0.dtype == torch.float32 and bias is not None and Cp % 8 == 0 and Cp * len(parts) == Ci
-                    and kh == kw == 3 and all(p.shape == x0.shape and p.is_contiguous() and p.dtype == x0.dtype for p in parts)
-                    and torch.is_grad_enabled() and _wino_ok(N, Ci, Co, H, W, 3, 3, padding, ragged=True)
-                    and _wino_ok(N, Co, Cp, H, W, 3, 3, padding, ragged=True)
-                    and PARTS_UNDER_AUTOGRAD):
-                return _WinoConv3x3Parts.apply(weight, bias, act, transposed, *parts)     # training: the parts are read where they lie
-            return _conv_bias_act(torch.cat(parts, dim=1), weight, bias, padding, act, transposed, out)
-        L = _native.lib()
-        y = out if _usable_out(out, (N, Co, H, W), x0) else torch.empty((N, Co, H, W), dtype=x0.dtype, device=x0.device)
-        ptrs = (ctypes.c_void_p * len(parts))(*[p.data_ptr() for p in parts])
-        with torch.cuda.device(x0.device):
-            if _wino43_ok(N, Ci, Co, H, W, len(parts), weight):      # wide layer: F(4x4, 3x3) (set_winograd_tile)
-                U = _wino43_weights(weight, transposed)
-                _wino43_launch(ptrs, len(parts), U, bias, y, N, Ci, Co, H, W, _ACT[act], torch.cuda.current_stream(x0.device).cuda_stream,
-                               weight)
-                return y
-            U = _wino_weights(weight, transposed)
-            _native.check(L.tai_conv3x3_wino_forward_parts(ptrs, len(parts), U.data_ptr(), bias.data_ptr(), y.data_ptr(), N, Ci,
-                                                           Co, H, W, _ACT[act], torch.cuda.current_stream(x0.device).cuda_stream),
-                          'tai_conv3x3_wino_forward_parts')
-        return y
-    fused = (x.is_cuda and x.dtype == torch.float32 and bias is not None
-             and not (torch.is_grad_enabled() and (x.requires_grad or weight.requires_grad or bias.requires_grad)))
-    if not fused:
-        if x.is_cuda and x.dtype == torch.float32 and bias is not None and weight.shape[2] == weight.shape[3] == 3:
-            Co, Ci = (weight.shape[1], weight.shape[0]) if transposed else (weight.shape[0], weight.shape[1])
-            N, _, H, W = x.shape
-            # (min_ci 2: the 3-channel layers of c_dim 3 -- ContentEnc's first, DecCnn's last -- run in-tree too: their input / output
-            # gradient is a convolution with 3 output / input channels, padded to one 64-channel block; MIOpen's kernels sum with atomics)
-            mc = 2 if RAGGED_ROUTES[0] else 8
-            if _wino_ok(N, Ci, Co, H, W, 3, 3, padding, min_ci=mc, ragged=True) and _wino_ok(N, Co, Ci, H, W, 3, 3, padding, min_ci=mc, ragged=True):
-                return _WinoConv3x3.apply(x, weight, bias, act, transposed)      # training: autograd through the HIP kernel
-        if (x.is_cuda and x.dtype == torch.float32 and bias is not None and not transposed and weight.shape[2] == weight.shape[3]
-                and weight.shape[2] in (5, 7)):
-            Co, Ci, k = weight.shape[0], weight.shape[1], weight.shape[2]
-            N, _, H, W = x.shape
-            if _kxk_ok(N, Ci, Co, H, W, k, k, padding) and _kxk_ok(N, Co, Ci, H, W, k, k, padding):
-                return _WinoConvKxK.apply(x, weight, bias, act)
-        if x.is_cuda and x.dtype == torch.float32 and bias is not None and x.shape[3] % 4 == 0 and weight.shape[2] == weight.shape[3]:
-            Co, Ci = (weight.shape[1], weight.shape[0]) if transposed else (weight.shape[0], weight.shape[1])
-            k = weight.shape[2]
-            if Ci == 1 and not transposed and k in (3, 5) and padding == k // 2 and act in (None, 'relu') and Co >= 16:
-                return _ThinInConv.apply(x, weight, bias, act)
-            if Co == 1 and k == 3 and padding == 1 and Ci >= 16:
-                return _ThinOutConv.apply(x, weight, bias, act, transposed)
+    l = _Layer(x, weight, bias, padding, act, transposed)
+    route = conv_route(l)
+    if route == 'bf16':
+        return _bf16_conv(l.parts, weight, bias, act, transposed, out)
+    if route == 'cat':
+        return _conv_bias_act(torch.cat(l.parts, dim=1), weight, bias, padding, act, transposed, out)
+    if route == 'aten':
         y = F.conv2d(x, _as_conv_weight(weight, transposed), bias, stride=1, padding=padding)
         return torch.relu(y) if act == 'relu' else (torch.tanh(y) if act == 'tanh' else y)
-    kh, kw = weight.shape[2], weight.shape[3]
-    Co, Ci = (weight.shape[1], weight.shape[0]) if transposed else (weight.shape[0], weight.shape[1])
-    N, _, H, W = x.shape
-    if x.shape[1] == Ci and _bf16_route(Ci, Co, kh, kw, padding):     # (the fused test above: no gradient needed)
-        return _bf16_conv([x], weight, bias, act, transposed, out)
-    L = _native.lib()
-    stream = torch.cuda.current_stream(x.device).cuda_stream
-    thin_in = Ci == 1 and kh == kw and kh in (3, 5) and padding == kh // 2 and W % 4 == 0 and act in (None, 'relu') and Co >= 16
-    thin_out = Co == 1 and kh == kw == 3 and padding == 1 and W % 4 == 0 and Ci >= 16
-    if thin_in or thin_out:
+    if route == 'autograd_parts':
+        return _WinoConv3x3Parts.apply(weight, bias, act, transposed, *l.parts)
+    if route == 'autograd_3x3':
+        return _WinoConv3x3.apply(x, weight, bias, act, transposed)      # training: autograd through the HIP kernel
+    if route == 'autograd_kxk':
+        return _WinoConvKxK.apply(x, weight, bias, act)
+    if route == 'autograd_thin_in':
+        return _ThinInConv.apply(x, weight, bias, act)
+    if route == 'autograd_thin_out':
+        return _ThinOutConv.apply(x, weight, bias, act, transposed)
+    if route == 'kxk':
+        return _kxk_as_wino(x, weight, bias, act, False)
+    N, Ci, Co, H, W = l.N, l.Ci, l.Co, l.H, l.W
+    if route in ('thin_in', 'thin_out'):
         # one input or one output channel: no GEMM in it, a stream of the wide tensor (csrc/thin_conv.hip.inc)
         x = x.contiguous()
         w = _cached(weight, ('direct', transposed), lambda: _as_conv_weight(weight.detach(), transposed).contiguous())
         y = torch.empty((N, Co, H, W), dtype=x.dtype, device=x.device)
-        with torch.cuda.device(x.device):
-            if thin_in:
-                _native.check(L.tai_conv_cin1_forward(x.data_ptr(), w.data_ptr(), bias.data_ptr(), y.data_ptr(), N, Co,
-                                                      H, W, kh, _ACT[act], stream), 'tai_conv_cin1_forward')
-            else:
-                _native.check(L.tai_conv_cout1_3x3_forward(x.data_ptr(), w.data_ptr(), bias.data_ptr(), y.data_ptr(), N,
-                                                           Ci, H, W, _ACT[act], stream), 'tai_conv_cout1_3x3_forward')
+        if route == 'thin_in':
+            _native.launch('tai_conv_cin1_forward', x.device, x, w, bias, y, N, Co, H, W, l.kh, _ACT[act])
+        else:
+            _native.launch('tai_conv_cout1_3x3_forward', x.device, x, w, bias, y, N, Ci, H, W, _ACT[act])
         return y
-    if not transposed and _kxk_ok(N, Ci, Co, H, W, kh, kw, padding):
-        return _kxk_as_wino(x, weight, bias, act, False)
-    if _wino_ok(N, Ci, Co, H, W, kh, kw, padding, min_ci=2, ragged=True):
-        # Winograd F(2x2,3x3) on the fp32 MFMA pipe (csrc/wino_conv.hip.inc)
-        x = x.contiguous()
-        y = out if _usable_out(out, (N, Co, H, W), x) else torch.empty((N, Co, H, W), dtype=x.dtype, device=x.device)
-        with torch.cuda.device(x.device):
-            if _wino43_ok(N, Ci, Co, H, W, 1, weight):       # wide layer: F(4x4, 3x3) (set_winograd_tile)
-                U = _wino43_weights(weight, transposed)
-                _wino43_launch((ctypes.c_void_p * 1)(x.data_ptr()), 1, U, bias, y, N, Ci, Co, H, W, _ACT[act], stream, weight)
-                return y
-            U = _wino_weights(weight, transposed)
-            _wino_forward(L, x, U, bias, y, N, Ci, Co, H, W, act, stream)
+    if route == 'miopen':
+        w = _cached(weight, ('direct', transposed), lambda: _as_conv_weight(weight.detach(), transposed).contiguous()) \
+            if transposed else weight
+        y = F.conv2d(x, w, None, stride=1, padding=padding)
+        if not y.is_contiguous():
+            y = y.contiguous()
+        N, C, H, W = y.shape
+        _native.launch('tai_bias_act_inplace', y.device, y, bias, N, C, H * W, _ACT[act])
         return y
-    w = _cached(weight, ('direct', transposed), lambda: _as_conv_weight(weight.detach(), transposed).contiguous()) \
-        if transposed else weight
-    y = F.conv2d(x, w, None, stride=1, padding=padding)
-    if not y.is_contiguous():
-        y = y.contiguous()
-    N, C, H, W = y.shape
-    with torch.cuda.device(y.device):
-        _native.check(L.tai_bias_act_inplace(y.data_ptr(), bias.data_ptr(), N, C, H * W, _ACT[act], stream),
-                      'tai_bias_act_inplace')
+    # the Winograd kernels on the fp32 MFMA pipe (csrc/wino43_conv.hip.inc, csrc/wino_conv.hip.inc); they write ``out`` directly
+    parts = [p.contiguous() for p in l.parts]
+    x0 = parts[0]
+    y = out if _usable_out(out, (N, Co, H, W), x0) else torch.empty((N, Co, H, W), dtype=x0.dtype, device=x0.device)
+    if route == 'wino43':            # wide layer: F(4x4, 3x3) (set_winograd_tile)
+        _wino43_launch(_part_pointers(parts), len(parts), _transformed_weights(weight, transposed, 4), bias, y, N, Ci, Co, H, W,
+                       _ACT[act], weight)
+    elif route == 'wino_parts':
+        _native.launch('tai_conv3x3_wino_forward_parts', y.device, _part_pointers(parts), len(parts),
+                       _transformed_weights(weight, transposed, 2), bias, y, N, Ci, Co, H, W, _ACT[act])
+    else:
+        _wino_forward(x0, _transformed_weights(weight, transposed, 2), bias, y, N, Ci, Co, H, W, act)
     return y

@@ -252,7 +252,6 @@ class FusedStep(object):
                     s.fill_(float(t))
         else:
             from . import _native
-            lib = _native.lib()
             rows, n_segments = step_rows(params, grads, ms, vs, steps, emas)
             n = rows.shape[0]
             stats_rows = np.ascontiguousarray(rows[:, [1, 6, 6, 7]])
@@ -262,18 +261,17 @@ class FusedStep(object):
             tb = o.tables
             with torch.cuda.device(self.device):
                 tb.upload(stats_rows, rows)
-                stream = torch.cuda.current_stream(self.device).cuda_stream
                 sumsq_ptr = bad_ptr = None
                 if guard is not None:
                     base = tb.result.data_ptr()
                     sumsq_ptr, bad_ptr = base, base + 8 * (n + 1)
-                    _native.check(lib.tai_grad_stats(tb.stats.data_ptr(), stats_rows.ctypes.data, n, n_segments, 0, tb.workspace.data_ptr(),
-                                                     base, base + 16 * (n + 1), bad_ptr, stream), 'tai_grad_stats')
-                _native.check(lib.tai_step_verdict(sumsq_ptr, bad_ptr, n, float(max_norm), w, int(bool(last)), patience, self.table_len,
-                                                   self.rec.data_ptr(), stream), 'tai_step_verdict')
-                _native.check(lib.tai_fused_step(tb.rows.data_ptr(), rows.ctypes.data, n, n_segments, o.scalars.data_ptr(), self.table_len,
-                                                 float(o.k.w1), float(o.k.b2), float(o.k.w2), float(o.k.eps), float(o.k.wE),
-                                                 self.rec.data_ptr(), w, int(NT_LOADS), int(self.blocks), None, stream), 'tai_fused_step')
+                    _native.launch('tai_grad_stats', self.device, tb.stats, stats_rows.ctypes.data, n, n_segments, 0, tb.workspace,
+                                   base, base + 16 * (n + 1), bad_ptr)
+                _native.launch('tai_step_verdict', self.device, sumsq_ptr, bad_ptr, n, float(max_norm), w, int(bool(last)), patience,
+                               self.table_len, self.rec)
+                _native.launch('tai_fused_step', self.device, tb.rows, rows.ctypes.data, n, n_segments, o.scalars, self.table_len,
+                               float(o.k.w1), float(o.k.b2), float(o.k.w2), float(o.k.eps), float(o.k.wE), self.rec, w, int(NT_LOADS),
+                               int(self.blocks), None)
         if last:
             self._end_update()
 

@@ -128,11 +128,9 @@ def grad_stats(tensors, blocks=0):
         from . import _native
         bufs, rows, device, n_segments = _device_table(tensors)
         with torch.cuda.device(device):
-            stream = torch.cuda.current_stream(device)
             base = bufs.result.data_ptr()
-            _native.check(_native.lib().tai_grad_stats(bufs.table.data_ptr(), rows.ctypes.data, n, n_segments, int(blocks),
-                                                       bufs.workspace.data_ptr(), base, base + 16 * (n + 1), base + 8 * (n + 1),
-                                                       stream.cuda_stream), 'tai_grad_stats')
+            _native.launch('tai_grad_stats', device, bufs.table, rows.ctypes.data, n, n_segments, int(blocks), bufs.workspace,
+                           base, base + 16 * (n + 1), base + 8 * (n + 1))
             raw = bufs.result.cpu().numpy()                              # synchronises
         sumsq = raw[:2 * (n + 1)].view(np.float64)
         nonfinite = raw[2 * (n + 1):4 * (n + 1)].view(np.int64)
@@ -156,9 +154,7 @@ def scale_(tensors, c, blocks=0):
         return
     from . import _native
     bufs, rows, device, n_segments = _device_table(tensors)
-    with torch.cuda.device(device):
-        _native.check(_native.lib().tai_grad_scale(bufs.table.data_ptr(), rows.ctypes.data, len(tensors), n_segments, float(c), int(blocks),
-                                                   None, torch.cuda.current_stream(device).cuda_stream), 'tai_grad_scale')
+    _native.launch('tai_grad_scale', device, bufs.table, rows.ctypes.data, len(tensors), n_segments, float(c), int(blocks), None)
 
 
 def clip_coefficient(total_sumsq, nonfinite, max_norm):

@@ -58,11 +58,7 @@ class _SSIMLossFunction(torch.autograd.Function):
         workspace = torch.empty(nbytes // 8, dtype=torch.float64, device=dev)
         out = torch.empty(N * C + 2, dtype=torch.float64, device=dev)          # plane_ssim, then mean_ssim and loss
         grad = torch.empty(pred.shape, dtype=torch.float32, device=dev) if ctx.needs_input_grad[0] else None
-        with torch.cuda.device(dev):
-            stream = torch.cuda.current_stream(dev).cuda_stream
-            _native.check(L.tai_ssim_loss(p.data_ptr(), g.data_ptr(), out.data_ptr(), out[N * C:].data_ptr(),
-                                          grad.data_ptr() if grad is not None else None, workspace.data_ptr(), N, C, H, W, stream),
-                          'tai_ssim_loss')
+        _native.launch('tai_ssim_loss', dev, p, g, out, out[N * C:], grad, workspace, N, C, H, W)
         ctx.map = grad
         plane_ssim = out[:N * C]
         ctx.mark_non_differentiable(plane_ssim)
@@ -155,10 +151,7 @@ class _ImageLossFunction(torch.autograd.Function):
         pred_ptrs = (ctypes.c_void_p * n)(*[p.data_ptr() for p in ps])
         map_ptrs = (ctypes.c_void_p * n)(*[m.data_ptr() if m is not None else None for m in maps])
         totals = out[n * planes * 2:]
-        with torch.cuda.device(dev):
-            stream = torch.cuda.current_stream(dev).cuda_stream
-            _native.check(L.tai_image_loss(pred_ptrs, n, g.data_ptr(), kind, eps, out.data_ptr(), totals.data_ptr(), map_ptrs,
-                                           workspace.data_ptr(), planes, H, W, stream), 'tai_image_loss')
+        _native.launch('tai_image_loss', dev, pred_ptrs, n, g, kind, eps, out, totals, map_ptrs, workspace, planes, H, W)
         ctx.maps = maps
         t32 = totals.view(n, 3).to(torch.float32)
         losses, terms, plane_terms = t32[:, 2].contiguous(), t32[:, :2], out[:n * planes * 2].view(n, planes, 2)
@@ -325,11 +318,7 @@ class _LapLossFunction(torch.autograd.Function):
         out = torch.empty(planes * levels + levels + 1, dtype=torch.float64, device=dev)        # plane_terms, then totals
         grad = torch.empty(pred.shape, dtype=torch.float32, device=dev) if want_map and ctx.needs_input_grad[0] else None
         totals = out[planes * levels:]
-        with torch.cuda.device(dev):
-            stream = torch.cuda.current_stream(dev).cuda_stream
-            _native.check(L.tai_lap_loss(p.data_ptr(), g.data_ptr(), levels, out.data_ptr(), totals.data_ptr(),
-                                         grad.data_ptr() if grad is not None else None, workspace.data_ptr(), planes, H, W, stream),
-                          'tai_lap_loss')
+        _native.launch('tai_lap_loss', dev, p, g, levels, out, totals, grad, workspace, planes, H, W)
         ctx.map = grad
         t32 = totals.to(torch.float32)
         loss, terms, plane_terms = t32[levels].clone(), t32[:levels], out[:planes * levels].view(planes, levels)

@@ -68,10 +68,7 @@ def unpool2x_add(x, res):
         from . import _native
         x, res = x.contiguous(), res.contiguous()
         out = torch.empty_like(res)
-        with torch.cuda.device(x.device):
-            _native.check(_native.lib().tai_unpool2x_add(x.data_ptr(), res.data_ptr(), out.data_ptr(), x.shape[0] * x.shape[1],
-                                                         x.shape[2], x.shape[3], torch.cuda.current_stream(x.device).cuda_stream),
-                          'tai_unpool2x_add')
+        _native.launch('tai_unpool2x_add', x.device, x, res, out, x.shape[0] * x.shape[1], x.shape[2], x.shape[3])
         return out
     if (x.is_cuda and x.dtype == torch.float32 and res.dtype == torch.float32 and x.shape[3] % 2 == 0
             and tuple(res.shape) == (x.shape[0], x.shape[1], 2 * x.shape[2], 2 * x.shape[3])):
@@ -91,10 +88,7 @@ class _Unpool2xAdd(torch.autograd.Function):
         from . import _native
         x, res = x.contiguous(), res.contiguous()
         out = torch.empty_like(res)
-        with torch.cuda.device(x.device):
-            _native.check(_native.lib().tai_unpool2x_add(x.data_ptr(), res.data_ptr(), out.data_ptr(), x.shape[0] * x.shape[1],
-                                                         x.shape[2], x.shape[3], torch.cuda.current_stream(x.device).cuda_stream),
-                          'tai_unpool2x_add')
+        _native.launch('tai_unpool2x_add', x.device, x, res, out, x.shape[0] * x.shape[1], x.shape[2], x.shape[3])
         return out
 
     @staticmethod
@@ -215,10 +209,7 @@ class _LstmGates(torch.autograd.Function):
         gates, c = gates.contiguous(), c.contiguous()
         N, F4, H, W = gates.shape
         new_c, new_h = torch.empty_like(c), torch.empty_like(c)
-        with torch.cuda.device(gates.device):
-            _native.check(_native.lib().tai_convlstm_gates_forward(
-                gates.data_ptr(), c.data_ptr(), new_c.data_ptr(), new_h.data_ptr(), N, F4 // 4, H * W, float(forget_bias),
-                torch.cuda.current_stream(gates.device).cuda_stream), 'tai_convlstm_gates_forward')
+        _native.launch('tai_convlstm_gates_forward', gates.device, gates, c, new_c, new_h, N, F4 // 4, H * W, float(forget_bias))
         ctx.forget_bias = float(forget_bias)
         ctx.save_for_backward(gates, c, new_c)
         return new_c, new_h
@@ -233,11 +224,7 @@ class _LstmGates(torch.autograd.Function):
         g_c = g_c.contiguous() if g_c is not None else None
         g_h = g_h.contiguous() if g_h is not None else None
         d_gates, d_c = torch.empty_like(gates), torch.empty_like(c)
-        with torch.cuda.device(gates.device):
-            _native.check(_native.lib().tai_convlstm_gates_backward(
-                gates.data_ptr(), c.data_ptr(), new_c.data_ptr(), g_c.data_ptr() if g_c is not None else None,
-                g_h.data_ptr() if g_h is not None else None, d_gates.data_ptr(), d_c.data_ptr(), N, F4 // 4, H * W, ctx.forget_bias,
-                torch.cuda.current_stream(gates.device).cuda_stream), 'tai_convlstm_gates_backward')
+        _native.launch('tai_convlstm_gates_backward', gates.device, gates, c, new_c, g_c, g_h, d_gates, d_c, N, F4 // 4, H * W, ctx.forget_bias)
         return d_gates, d_c, None
 
 
@@ -277,10 +264,7 @@ class ConvLstmCell(nn.Module):
             from . import _native
             gates, c = gates.contiguous(), c.contiguous()
             new_c, new_h = torch.empty_like(c), torch.empty_like(c)
-            with torch.cuda.device(gates.device):
-                _native.check(_native.lib().tai_convlstm_gates_forward(
-                    gates.data_ptr(), c.data_ptr(), new_c.data_ptr(), new_h.data_ptr(), N, F4 // 4, H * W,
-                    float(self.forget_bias), torch.cuda.current_stream(gates.device).cuda_stream), 'tai_convlstm_gates_forward')
+            _native.launch('tai_convlstm_gates_forward', gates.device, gates, c, new_c, new_h, N, F4 // 4, H * W, float(self.forget_bias))
         elif gates.is_cuda and gates.dtype == torch.float32 and (H * W) % 4 == 0 and c.dtype == torch.float32:
             new_c, new_h = _LstmGates.apply(gates, c, self.forget_bias)           # training: the same kernel, and its gradient
         else:

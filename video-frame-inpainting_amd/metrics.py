@@ -110,10 +110,7 @@ def frame_metrics_device(pred, gt, out=None, workspace=None):
         out = torch.empty(3, N, dtype=torch.float64, device=dev)
     if out.dtype != torch.float64 or tuple(out.shape) != (3, N) or not out.is_contiguous():
         raise ValueError('frame_metrics_device: out must be a contiguous float64 [3, %d] tensor' % N)
-    with torch.cuda.device(dev):
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        _native.check(L.tai_frame_metrics(p.data_ptr(), g.data_ptr(), out[0].data_ptr(), out[1].data_ptr(), out[2].data_ptr(),
-                                          workspace.data_ptr(), N, C, H, W, stream), 'tai_frame_metrics')
+    _native.launch('tai_frame_metrics', dev, p, g, out[0], out[1], out[2], workspace, N, C, H, W)
     return out
 
 

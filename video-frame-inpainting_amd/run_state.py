@@ -148,11 +148,9 @@ def digest_tensors(entries, seg_words=SEG_WORDS):
         _tables[key] = _DeviceTable(host.shape[0], n_segments, device)
     bufs = _tables[key]
     with torch.cuda.device(device):
-        stream = torch.cuda.current_stream(device)
         bufs.table.copy_(torch.from_numpy(host))          # pageable memory: the copy has left `host` when it returns
-        _native.check(_native.lib().tai_state_digest(bufs.table.data_ptr(), host.ctypes.data, host.shape[0], n_segments, int(seg_words),
-                                                     bufs.workspace.data_ptr(), bufs.result.data_ptr(), stream.cuda_stream),
-                      'tai_state_digest')
+        _native.launch('tai_state_digest', device, bufs.table, host.ctypes.data, host.shape[0], n_segments, int(seg_words),
+                       bufs.workspace, bufs.result)
         value = int(bufs.result.item())                    # synchronises
     return value & _MASK
 

@@ -14,10 +14,6 @@ import torch
 from . import _native
 
 
-def _stream_ptr(t):
-    return torch.cuda.current_stream(t.device).cuda_stream
-
-
 class SeparableConvolution(torch.autograd.Function):
     @staticmethod
     def forward(ctx, input, vertical, horizontal, ks=51):
@@ -38,11 +34,7 @@ class SeparableConvolution(torch.autograd.Function):
         assert vertical.shape == horizontal.shape == (B, ks, Hout, Wout)
         assert input.dtype == vertical.dtype == horizontal.dtype == torch.float32
         output = torch.empty((B, C, Hout, Wout), dtype=input.dtype, device=input.device)
-        L = _native.lib()
-        with torch.cuda.device(input.device):
-            _native.check(L.tai_sepconv_forward(input.data_ptr(), vertical.data_ptr(), horizontal.data_ptr(),
-                                                output.data_ptr(), B, C, Hout, Wout, ks, _stream_ptr(input)),
-                          'tai_sepconv_forward')
+        _native.launch('tai_sepconv_forward', input.device, input, vertical, horizontal, output, B, C, Hout, Wout, ks)
         return output
 
     @staticmethod
@@ -58,13 +50,8 @@ class SeparableConvolution(torch.autograd.Function):
         grad_input = torch.empty_like(input) if need_i else None
         grad_vertical = torch.empty_like(vertical) if need_v else None
         grad_horizontal = torch.empty_like(horizontal) if need_h else None
-        ptr = lambda t: t.data_ptr() if t is not None else None
-        L = _native.lib()
-        with torch.cuda.device(input.device):
-            _native.check(L.tai_sepconv_backward(grad_output.data_ptr(), input.data_ptr(), vertical.data_ptr(),
-                                                 horizontal.data_ptr(), ptr(grad_input), ptr(grad_vertical),
-                                                 ptr(grad_horizontal), B, C, Hout, Wout, ks,
-                                                 _stream_ptr(input)), 'tai_sepconv_backward')
+        _native.launch('tai_sepconv_backward', input.device, grad_output, input, vertical, horizontal, grad_input, grad_vertical,
+                       grad_horizontal, B, C, Hout, Wout, ks)
         return grad_input, grad_vertical, grad_horizontal, None
 
 

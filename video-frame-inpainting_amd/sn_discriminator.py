@@ -79,10 +79,7 @@ class _SpectralNormalised(object):
         if scratch is None or scratch.device != weight.device or scratch.numel() != in_cols + out_rows + 1:
             scratch = self._sn_scratch = torch.empty(in_cols + out_rows + 1, device=weight.device, dtype=torch.float32)
         sigma = scratch[-1:] if sigma_out is None else sigma_out
-        with torch.cuda.device(weight.device):
-            _native.check(_native.lib().tai_sn_power_iteration(
-                weight.data_ptr(), u.data_ptr(), scratch.data_ptr(), sigma.data_ptr(), out_rows, in_cols, int(self.Ip),
-                torch.cuda.current_stream(weight.device).cuda_stream), 'tai_sn_power_iteration')
+        _native.launch('tai_sn_power_iteration', weight.device, weight, u, scratch, sigma, out_rows, in_cols, int(self.Ip))
 
     @property
     def last_sigma(self):
@@ -184,10 +181,7 @@ class _WindowScaledConvLReLU(torch.autograd.Function):
         N, Co, H, W = y.shape
         # (HW % 4 != 0: the one-element-per-thread form, e.g. the last layer's 10 x 13 output at 160 x 208 frames)
         tail = 'tai_window_scale_bias_lrelu' if (H * W) % 4 == 0 else 'tai_window_scale_bias_lrelu_scalar'
-        with torch.cuda.device(y.device):
-            _native.check(getattr(_native.lib(), tail)(
-                y.data_ptr(), bias.data_ptr(), inv_scale.data_ptr(), nw, N // nw, Co, H * W, float(slope),
-                torch.cuda.current_stream(y.device).cuda_stream), tail)
+        _native.launch(tail, y.device, y, bias, inv_scale, nw, N // nw, Co, H * W, float(slope))
         ctx.s2d = xs is not None
         if ctx.s2d:
             ctx.save_for_backward(x, w0, inv_scale, y, xs, w3)
@@ -206,10 +200,7 @@ class _WindowScaledConvLReLU(torch.autograd.Function):
         N, Co, H, W = g.shape
         gz, gs = torch.empty_like(g), torch.empty_like(g)
         tail = 'tai_window_scale_lrelu_backward' if (H * W) % 4 == 0 else 'tai_window_scale_lrelu_backward_scalar'
-        with torch.cuda.device(g.device):
-            _native.check(getattr(_native.lib(), tail)(
-                g.data_ptr(), y.data_ptr(), inv_scale.data_ptr(), gz.data_ptr(), gs.data_ptr(), nw, N // nw, Co, H * W, slope,
-                torch.cuda.current_stream(g.device).cuda_stream), tail)
+        _native.launch(tail, g.device, g, y, inv_scale, gz, gs, nw, N // nw, Co, H * W, slope)
         gx = gw = gb = None
         conv_bwd = torch.ops.aten.convolution_backward
         if ctx.needs_input_grad[1]:

@@ -16,10 +16,7 @@ class _Upsample2xAlignCorners(torch.autograd.Function):
         ctx.in_shape = (B, C, H, W)
         x = x.contiguous()
         out = torch.empty((B, C, 2 * H, 2 * W), dtype=x.dtype, device=x.device)
-        with torch.cuda.device(x.device):
-            _native.check(_native.lib().tai_upsample_bilinear2x_forward(
-                x.data_ptr(), out.data_ptr(), B * C, H, W, torch.cuda.current_stream(x.device).cuda_stream),
-                'tai_upsample_bilinear2x_forward')
+        _native.launch('tai_upsample_bilinear2x_forward', x.device, x, out, B * C, H, W)
         return out
 
     @staticmethod
@@ -27,10 +24,7 @@ class _Upsample2xAlignCorners(torch.autograd.Function):
         B, C, H, W = ctx.in_shape
         g = grad_out.contiguous()
         gin = torch.empty((B, C, H, W), dtype=g.dtype, device=g.device)
-        with torch.cuda.device(g.device):
-            _native.check(_native.lib().tai_upsample_bilinear2x_backward(
-                g.data_ptr(), gin.data_ptr(), B * C, H, W, torch.cuda.current_stream(g.device).cuda_stream),
-                'tai_upsample_bilinear2x_backward')
+        _native.launch('tai_upsample_bilinear2x_backward', g.device, g, gin, B * C, H, W)
         return gin
 
 
