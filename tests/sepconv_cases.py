@@ -10,7 +10,7 @@ Two kinds of data:
   * ``float_case``: tests/test_gpu_sepconv.py's generator (tanh-range image, taps N(0, 0.1)), compared within its BWD_TOL.
 
 The tiling constants restate csrc/sepconv_fwd.hip.inc / sepconv_bwd.hip.inc, the forward route predicates restate
-csrc/sepconv_capi.hip's persistent_policy; the CPU test reads them back from the sources.
+csrc/capi_sepconv.inc's persistent_policy; the CPU test reads them back from the sources.
 """
 import torch
 
@@ -172,7 +172,7 @@ def fwd_tiles(B, H, W):
 
 
 def fwd_persistent_runs(B, H, W, cus, forced=False):
-    """csrc/sepconv_capi.hip's persistent_policy at C = 1: a multiple of 8 tiles, more tiles than workgroups unless the variant
+    """csrc/capi_sepconv.inc's persistent_policy at C = 1: a multiple of 8 tiles, more tiles than workgroups unless the variant
     was asked for by number, tap offsets that fit 32 bits, a device of at least 8 CUs."""
     ntiles, grid = fwd_tiles(B, H, W), cus // 8 * 8
     return grid >= 8 and ntiles % 8 == 0 and (forced or ntiles > grid) and B * 51 * H * W * 4 <= 0xffffffff

@@ -1,0 +1,390 @@
+"""What the C ABI refuses, and with which words, is pinned: argument checks run before any runtime call, so they work without a device.
+
+tests/golden/capi_refusals.json holds, for every call of CASES below, what the library answered at the commit named in the file:
+(return code, tai_sepconv_last_error()).  It is recorded by this file itself --
+
+    python tests/test_capi_refusals_cpu.py --record path/to/libtai_sepconv.so <commit>
+
+-- on the commit BEFORE a change to the launchers, and the test replays the table on the tree and requires equality.  A call that is not
+refused may never be recorded (without a device it would reach a launch): the recorder stops at a return code other than
+TAI_SEPCONV_EINVAL.
+
+Pointer arguments are None or the dummy address P, which a refused call never dereferences; the host arrays an entry reads before it
+refuses (xs[i], preds[i], table_host) are real ctypes arrays: ('ptrs', [...]) and ('i64', [...]).  ('f', 'inf') is a float that JSON
+has no literal for."""
+import ctypes
+import json
+import os
+import re
+import subprocess
+import sys
+
+import pytest
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import importlib
+_native = importlib.import_module('video-frame-inpainting_amd._native')
+
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden', 'capi_refusals.json')
+EINVAL = -1
+NO_DEVICE = {'HIP_VISIBLE_DEVICES': '-1', 'ROCR_VISIBLE_DEVICES': '-1'}      # the replay's and the recorder's environment
+P = 16                      # a pointer that is never followed
+X1, X2, X5 = ('ptrs', [P]), ('ptrs', [P, P]), ('ptrs', [P, P, P, P, P])
+XNULL = ('ptrs', [P, None])
+ZROW4, ZROW8 = ('i64', [0, 0, 0, 0]), ('i64', [0] * 8)
+
+
+def case(entry, *args, before=(), after=()):
+    """One refused call; `before` / `after` are calls of selector entries around it (they are not refusals and not recorded)."""
+    return {'entry': entry, 'args': list(args), 'before': [list(b) for b in before], 'after': [list(a) for a in after]}
+
+
+def _wino_ex(xs=X1, nparts=1, shift_k=0, ypool=None, pool=(0, 0, 0, 0), addx=None, y2=None, dims=(1, 8, 8, 8, 8), win=(0, 0, 0, 0), act=0):
+    return case('tai_conv3x3_wino_forward_ex', xs, nparts, shift_k, P, P, P, ypool, *pool, addx, y2, *dims, *win, act, None)
+
+
+def _bf16(xs=X1, nparts=1, Wp=P, ypool=None, addx=None, y2=None, dims=(1, 16, 16, 8, 8), k=3, act=0):
+    return case('tai_conv_bf16_forward', xs, nparts, Wp, P, P, ypool, addx, y2, *dims, k, act, None)
+
+
+def _blocks(shift_k=5, ypool=None, pool=(0, 0, 0, 0), dims=(1, 16, 64, 8, 8), win=(16, 16, 1, 1), act=0):
+    return case('tai_conv3x3_wino43_forward_blocks', P, shift_k, P, P, P, ypool, *pool, *dims, *win, act, None)
+
+
+VARIANT = lambda v: dict(before=[('tai_sepconv_set_forward_variant', v)], after=[('tai_sepconv_set_forward_variant', 0)])
+
+CASES = [
+    # ---- separable convolution
+    case('tai_sepconv_forward', None, P, P, P, 1, 1, 8, 8, 51, None),
+    case('tai_sepconv_forward', P, P, P, P, 0, 1, 8, 8, 51, None),
+    case('tai_sepconv_forward', P, P, P, P, 1, 1, 8, 8, 7, None, **VARIANT(2)),
+    case('tai_sepconv_forward', P, P, P, P, 1, 1, 8, 8, 51, None, **VARIANT(99)),
+    case('tai_sepconv_forward', P, P, P, P, 1, 1, 8, 8, 51, None, **VARIANT(101)),
+    case('tai_sepconv_forward_route', 0, 1, 8, 8, 51, 0),
+    case('tai_sepconv_forward_route', 1, 1, 8, 6, 51, 2),
+    case('tai_sepconv_forward_route', 1, 1, 8, 8, 51, 99),
+    case('tai_sepconv_backward', P, None, P, P, P, P, P, 1, 1, 8, 8, 51, None),
+    case('tai_sepconv_backward', P, P, P, P, P, P, P, 1, 1, 8, 8, 0, None),
+    case('tai_sepconv_backward', P, P, P, P, P, P, P, 1 << 16, 1, 1 << 10, 1 << 10, 51, None),
+    # ---- pointwise and thin layers
+    case('tai_hbm_read_probe', P, 1024, 0, P, None),
+    case('tai_hbm_read_probe', P, 1 << 20, 0, None, None),
+    case('tai_bias_act_inplace', P, None, 1, 1, 4, 0, None),
+    case('tai_bias_act_inplace', P, P, 1, 1, 4, 3, None),
+    case('tai_conv_cin1_forward', P, P, None, P, 1, 16, 8, 8, 3, 0, None),
+    case('tai_conv_cin1_forward', P, P, P, P, 1, 16, 8, 6, 3, 0, None),
+    case('tai_conv_cin1_forward', P, P, P, P, 1, 16, 8, 8, 4, 0, None),
+    case('tai_conv_cin1_forward_maxpool', P, P, P, P, None, 1, 16, 8, 8, 3, 0, None),
+    case('tai_conv_cin1_forward_maxpool', P, P, P, P, P, 1, 16, 7, 8, 3, 0, None),
+    case('tai_conv_cin1_forward_maxpool_window', P, P, P, P, None, 1, 16, 8, 8, 3, 0, 4, 4, 0, 0, None),
+    case('tai_conv_cin1_forward_maxpool_window', P, P, P, P, P, 1, 16, 8, 8, 3, 2, 4, 4, 0, 0, None),
+    case('tai_conv_cin1_forward_maxpool_window', P, P, P, P, P, 1, 16, 8, 8, 3, 0, 4, 4, 1, 0, None),
+    case('tai_unpool2x_add', P, None, P, 1, 4, 4, None),
+    case('tai_unpool2x_add', P, P, P, 1, 4, 3, None),
+    case('tai_convlstm_gates_forward', P, P, P, None, 1, 4, 8, 1.0, None),
+    case('tai_convlstm_gates_forward', P, P, P, P, 1, 4, 6, 1.0, None),
+    case('tai_convlstm_gates_backward', P, P, P, None, None, P, P, 1, 4, 8, 1.0, None),
+    case('tai_convlstm_gates_backward', P, P, P, P, None, P, P, 1, 4, 6, 1.0, None),
+    case('tai_sn_power_iteration', P, None, P, None, 4, 4, 1, None),
+    case('tai_sn_power_iteration', P, P, P, None, 4, 4, 65, None),
+    case('tai_window_scale_bias_lrelu', P, P, None, 1, 1, 1, 4, 0.1, None),
+    case('tai_window_scale_bias_lrelu', P, P, P, 1, 1, 1, 6, 0.1, None),
+    case('tai_window_scale_lrelu_backward', P, P, P, P, None, 1, 1, 1, 4, 0.1, None),
+    case('tai_window_scale_lrelu_backward', P, P, P, P, P, 1, 1, 1, 6, 0.1, None),
+    case('tai_window_scale_bias_lrelu_scalar', None, P, P, 1, 1, 1, 3, 0.1, None),
+    case('tai_window_scale_bias_lrelu_scalar', P, P, P, 0, 1, 1, 3, 0.1, None),
+    case('tai_window_scale_bias_lrelu_scalar', P, P, P, 1 << 11, 1 << 10, 1 << 10, 3, 0.1, None),
+    case('tai_window_scale_lrelu_backward_scalar', P, None, P, P, P, 1, 1, 1, 3, 0.1, None),
+    case('tai_window_scale_lrelu_backward_scalar', P, P, P, P, P, 1, 1, 1, 0, 0.1, None),
+    case('tai_thin_conv_wrw', P, P, None, None, P, 1, 4, 8, 8, 3, None),
+    case('tai_thin_conv_wrw', P, P, P, P, P, 1, 4, 8, 8, 4, None),
+    case('tai_act_maxpool2x2_forward', P, P, None, 1, 4, 4, 1, None),
+    case('tai_act_maxpool2x2_forward', P, P, P, 1, 3, 4, 1, None),
+    case('tai_act_maxpool2x2_backward', P, P, None, P, 1, 4, 4, 1, None),
+    case('tai_act_maxpool2x2_backward', P, P, P, P, 1, 4, 6, 1, None),
+    case('tai_conv_shift_stack', P, None, 1, 4, 8, 8, 5, None),
+    case('tai_conv_shift_stack', P, P, 1, 4, 8, 8, 3, None),
+    case('tai_conv_cout1_3x3_forward', P, P, P, None, 1, 4, 8, 8, 0, None),
+    case('tai_conv_cout1_3x3_forward', P, P, P, P, 1, 4, 8, 8, 3, None),
+    case('tai_conv_cout1_5x5_forward', None, P, None, P, 1, 4, 8, 8, None),
+    case('tai_conv_cout1_5x5_forward', P, P, None, P, 1, 4, 8, 6, None),
+    case('tai_upsample_bilinear2x_forward', P, None, 1, 4, 4, None),
+    case('tai_upsample_bilinear2x_forward', P, P, 1, 0, 4, None),
+    case('tai_upsample_bilinear2x_backward', None, P, 1, 4, 4, None),
+    case('tai_upsample_bilinear2x_backward', P, P, 0, 4, 4, None),
+    # ---- Winograd F(4x4, 3x3)
+    case('tai_conv3x3_wino43_transform_weights', P, None, 8, 8, None),
+    case('tai_conv3x3_wino43_transform_weights', P, P, 8, 0, None),
+    case('tai_conv3x3_wino43_forward', None, P, P, P, 1, 8, 8, 8, 8, 0, None),
+    case('tai_conv3x3_wino43_forward', P, P, P, P, 1, 8, 8, 6, 8, 0, None),
+    case('tai_conv3x3_wino43_forward', P, P, P, P, 1, 8, 8, 8, 8, 3, None),
+    case('tai_conv3x3_wino43_forward', P, P, P, P, 128, 4, 64, 256, 256, 0, None),
+    case('tai_conv3x3_wino43_forward_parts', X5, 5, P, P, P, 1, 8, 8, 8, 8, 0, None),
+    case('tai_conv3x3_wino43_forward_parts', X2, 2, P, P, P, 1, 12, 8, 8, 8, 0, None),
+    case('tai_conv3x3_wino43_forward_parts', XNULL, 2, P, P, P, 1, 8, 8, 8, 8, 0, None),
+    case('tai_conv3x3_wino43_forward_ex', X1, 1, P, P, P, None, None, P, 1, 8, 8, 8, 8, 0, None),
+    case('tai_conv3x3_wino43_forward_ex', X1, 1, P, P, P, None, P, None, 1, 8, 8, 8, 8, 1, None),
+    case('tai_conv3x3_wino43_forward_ex', X1, 1, P, P, P, P, None, None, 1, 8, 8, 8, 8, 2, None),
+    case('tai_conv3x3_wino43_forward_ws', X1, 1, P, P, P, None, None, None, None, -1, 1, 8, 8, 8, 8, 0, None),
+    case('tai_conv3x3_wino43_forward_ws', X1, 1, P, P, P, None, None, None, None, 0, 1, 512, 64, 16, 16, 0, None),
+    case('tai_conv3x3_wino43_forward_ws', X1, 1, P, P, P, None, None, None, P, 16, 1, 512, 64, 16, 16, 0, None),
+    _blocks(shift_k=3),
+    _blocks(dims=(1, 12, 64, 8, 8)),
+    _blocks(act=2),
+    _blocks(win=(16, 16, 0, 1)),
+    _blocks(win=(12, 16, 1, 1)),
+    _blocks(dims=(128, 16, 64, 256, 256), win=(264, 264, 1, 1)),
+    _blocks(ypool=P, pool=(4, 3, 0, 0)),
+    _blocks(ypool=P, pool=(3, 4, 0, 0)),
+    # ---- Winograd F(2x2, 3x3)
+    case('tai_conv3x3_wino_set_arithmetic', 2),
+    case('tai_conv3x3_wino_timeline_skip', 1),
+    case('tai_conv3x3_wino_transform_weights', None, P, 8, 8, None),
+    case('tai_conv3x3_wino_transform_weights', P, P, 0, 8, None),
+    case('tai_conv3x3_wino_forward', P, P, P, P, 1, 8, 8, 7, 8, 0, None),
+    case('tai_conv3x3_wino_forward', None, P, P, P, 1, 8, 8, 8, 8, 0, None),
+    case('tai_conv3x3_wino_forward', P, P, P, P, 1, 8, 8, 8, 8, 3, None),
+    case('tai_conv3x3_wino_forward', P, P, P, P, 0, 8, 8, 8, 8, 0, None),
+    case('tai_conv3x3_wino_forward', P, P, P, P, 128, 8, 64, 256, 256, 0, None),
+    case('tai_conv3x3_wino_forward_maxpool', P, P, P, P, None, 1, 8, 8, 8, 8, 0, None),
+    case('tai_conv3x3_wino_forward_maxpool', P, P, P, P, P, 1, 8, 8, 7, 8, 0, None),
+    case('tai_conv3x3_wino_forward_window', P, P, P, P, None, 1, 8, 8, 8, 8, 4, 8, 0, 0, 0, None),
+    case('tai_conv3x3_wino_forward_window', P, P, P, P, None, 1, 8, 8, 8, 8, 10, 10, 1, 1, 0, None),
+    case('tai_conv3x3_wino_forward_window', P, P, P, P, None, 1, 8, 8, 7, 8, 9, 8, 0, 0, 0, None),
+    case('tai_conv3x3_wino_forward_parts', X5, 5, P, P, P, 1, 8, 8, 8, 8, 0, None),
+    case('tai_conv3x3_wino_forward_parts', None, 1, P, P, P, 1, 8, 8, 8, 8, 0, None),
+    case('tai_conv3x3_wino_forward_parts', X2, 2, P, P, P, 1, 24, 8, 8, 8, 0, None),
+    case('tai_conv3x3_wino_forward_parts', XNULL, 2, P, P, P, 1, 16, 8, 8, 8, 0, None),
+    case('tai_conv3x3_wino_forward_timeline', P, P, P, P, 1, 8, 8, 8, 8, None, None),
+    _wino_ex(xs=X2, nparts=2, shift_k=5),
+    _wino_ex(xs=X5, nparts=5),
+    _wino_ex(shift_k=3),
+    _wino_ex(shift_k=10),
+    _wino_ex(xs=X2, nparts=2, dims=(1, 24, 8, 8, 8)),
+    _wino_ex(shift_k=5, dims=(1, 12, 8, 8, 8)),
+    _wino_ex(y2=P),
+    _wino_ex(xs=XNULL, nparts=2, dims=(1, 16, 8, 8, 8)),
+    _wino_ex(shift_k=5, dims=(1, 32, 8, 8, 8), win=(16, 16, 0, 2), act=1),
+    _wino_ex(shift_k=5, dims=(1, 32, 8, 8, 8), win=(12, 16, 1, 2), act=1),
+    _wino_ex(shift_k=5, dims=(1, 32, 8, 8, 8), win=(16, 16, 1, 2), act=0),
+    _wino_ex(addx=P, act=1),
+    _wino_ex(ypool=P, pool=(1, 1, 0, 0)),
+    _wino_ex(ypool=P, pool=(4, 4, -1, 0)),
+    _wino_ex(ypool=P, pool=(1 << 15, 1 << 15, 0, 0)),
+    _wino_ex(addx=P, dims=(1, 8, 8, 7, 8)),
+    _wino_ex(dims=(1, 8, 8, 8, 8), win=(8, 9, 0, 0)),
+    case('tai_conv3x3_wino_wrw', P, None, P, P, P, 1, 8, 8, 8, 16, None),
+    case('tai_conv3x3_wino_wrw', P, P, P, P, P, 0, 8, 8, 8, 16, None),
+    case('tai_conv3x3_wino_wrw', P, P, P, P, P, 1 << 10, 64, 64, 128, 128, None),
+    case('tai_conv3x3_wino_wrw_window', P, P, P, P, P, 1, 8, 8, 8, 16, 0, 16, 0, 0, None),
+    case('tai_conv3x3_wino_wrw_window', P, P, P, P, P, 1, 8, 8, 8, 16, 8, 16, 1, 0, None),
+    case('tai_conv3x3_wino_wrw_window', P, P, P, P, P, 1, 8, 8, 8, 16, 10, 18, -1, 0, None),
+    # ---- bf16 inference convolution
+    case('tai_conv_bf16_weight_elems', 8, 16, 3),
+    case('tai_conv_bf16_weight_elems', 16, 16, 4),
+    case('tai_conv_bf16_pack_weights', P, None, 16, 16, 3, 0, None),
+    case('tai_conv_bf16_pack_weights', P, P, 16, 8, 3, 0, None),
+    case('tai_conv_bf16_pack_weights', P, P, 1 << 15, 1 << 15, 3, 0, None),
+    case('tai_conv_bf16_pack_weights', P, 8, 16, 16, 3, 0, None),
+    _bf16(xs=X5, nparts=5),
+    _bf16(xs=None),
+    _bf16(xs=XNULL, nparts=2),
+    _bf16(k=4),
+    _bf16(act=3),
+    _bf16(xs=X2, nparts=2, dims=(1, 17, 16, 8, 8)),
+    _bf16(dims=(1 << 15, 16, 16, 64, 64)),
+    _bf16(ypool=P, dims=(1, 16, 16, 7, 8)),
+    _bf16(addx=P, dims=(1, 16, 16, 8, 7)),
+    _bf16(y2=P),
+    _bf16(Wp=8),
+    # ---- image metrics, losses, clip pipeline
+    case('tai_frame_metrics', P, P, P, P, P, None, 1, 1, 8, 8, None),
+    case('tai_frame_metrics', P, P, P, P, P, P, 1, 1, 6, 8, None),
+    case('tai_frame_metrics', P, P, P, P, P, P, 1, 1, 1 << 16, 1 << 16, None),
+    case('tai_frame_metrics', P, P, P, P, P, 4, 1, 1, 8, 8, None),
+    case('tai_ssim_loss', P, None, P, P, None, P, 1, 1, 8, 8, None),
+    case('tai_ssim_loss', P, P, P, P, None, P, 1, 0, 8, 8, None),
+    case('tai_ssim_loss', P, P, P, P, None, P, 1 << 12, 1 << 12, 1 << 8, 1 << 8, None),
+    case('tai_ssim_loss', P, P, P, 4, None, P, 1, 1, 8, 8, None),
+    case('tai_image_loss', None, 1, P, 0, 0.0, P, P, None, P, 1, 8, 8, None),
+    case('tai_image_loss', X1, 4, P, 0, 0.0, P, P, None, P, 1, 8, 8, None),
+    case('tai_image_loss', X1, 1, P, 0, 0.0, P, P, None, P, 1, 1, 8, None),
+    case('tai_image_loss', X1, 1, P, 3, 0.0, P, P, None, P, 1, 8, 8, None),
+    case('tai_image_loss', X1, 1, P, 2, 0.0, P, P, None, P, 1, 8, 8, None),
+    case('tai_image_loss', X1, 1, P, 2, ('f', 'inf'), P, P, None, P, 1, 8, 8, None),
+    case('tai_image_loss', XNULL, 2, P, 0, 0.0, P, P, None, P, 1, 8, 8, None),
+    case('tai_image_loss', X1, 1, P, 0, 0.0, 12, P, None, P, 1, 8, 8, None),
+    case('tai_lap_loss', P, P, 3, None, P, None, P, 1, 8, 8, None),
+    case('tai_lap_loss', P, P, 7, P, P, None, P, 1, 8, 8, None),
+    case('tai_lap_loss', P, P, 3, P, P, None, P, 1, 2, 8, None),
+    case('tai_lap_loss', P, P, 3, P, 4, None, P, 1, 8, 8, None),
+    case('tai_clip_from_frames', P, 100, P, None, P, P, 1, 1, 4, 4, 0, 0, None),
+    case('tai_clip_from_frames', P, 100, P, ZROW4, P, P, 1, 2, 4, 4, 0, 0, None),
+    case('tai_clip_from_frames', P, 0, P, ZROW4, P, P, 1, 1, 4, 4, 0, 0, None),
+    case('tai_clip_from_frames', P, 100, P, ZROW4, P, P, 1, 1, 1 << 24, 4, 0, 0, None),
+    case('tai_clip_from_frames', P, 100, P, ZROW4, P, P, 1, 1, 4, 4, 0, 0, None),
+    case('tai_clip_from_frames', P, 100, P, ('i64', [60, 4, 4, 0]), P, P, 1, 1, 4, 4, 0, 0, None),
+    case('tai_clip_from_frames', P, 100, P, ('i64', [101, 1, 1, 0]), P, P, 1, 1, 4, 4, 0, 0, None),
+    case('tai_frames_to_uint8', P, None, 1, 1, 8, 8, 8, 8, 0, None),
+    case('tai_frames_to_uint8', P, P, 1, 2, 8, 8, 8, 8, 0, None),
+    case('tai_frames_to_uint8', P, P, 1, 1, 8, 8, 9, 8, 0, None),
+    case('tai_frames_to_uint8', P, P, 1 << 16, 1, 256, 128, 1, 1, 0, None),
+    # ---- tables of tensors
+    case('tai_state_digest', P, None, 1, 0, 4, P, P, None),
+    case('tai_state_digest', P, ZROW4, 1, 0, 3, P, P, None),
+    case('tai_state_digest', P, ZROW4, 0, 0, 4, P, P, None),
+    case('tai_state_digest', P, ('i64', [18, 4, 0, 0]), 1, 1, 4, P, P, None),
+    case('tai_state_digest', P, ('i64', [16, 4, 0, 0, 32, 4, 0, 2]), 2, 2, 4, P, P, None),
+    case('tai_state_digest', P, ('i64', [16, -1, 0, 0]), 1, 0, 4, P, P, None),
+    case('tai_state_digest', P, ('i64', [16, 9, 0, 0, 0, 9, 0, 3]), 2, 5, 4, P, P, None),
+    case('tai_grad_stats', P, ZROW4, 1, 0, 0, None, P, P, P, None),
+    case('tai_grad_stats', P, ZROW4, 0, 0, 0, P, P, P, P, None),
+    case('tai_grad_stats', P, ZROW4, 1, 0, 65537, P, P, P, P, None),
+    case('tai_grad_stats', P, ZROW4, 1, 0, 0, 8, P, P, P, None),
+    case('tai_grad_stats', P, ZROW4, 1, 0, 0, P, P, 18, P, None),
+    case('tai_grad_stats', P, ('i64', [16, 0, 0, 0]), 1, 0, 0, P, P, P, P, None),
+    case('tai_grad_stats', P, ('i64', [16, 5, 0, 1]), 1, 1, 0, P, P, P, P, None),
+    case('tai_grad_stats', P, ZROW4, 1, 5, 0, P, P, P, P, None),
+    case('tai_grad_scale', None, ZROW4, 1, 0, 1.0, 0, None, None),
+    case('tai_grad_scale', P, ZROW4, 1, 0, 1.0, -1, None, None),
+    case('tai_grad_scale', P, ZROW4, 1, 0, ('f', 'inf'), 0, None, None),
+    case('tai_grad_scale', P, ZROW4, 1, 0, ('f', 'nan'), 0, None, None),
+    case('tai_grad_scale', P, ('i64', [0, 5, 0, 0]), 1, 1, 1.0, 0, None, None),
+    case('tai_grad_scale', P, ('i64', [16, 1 << 40, 0, 0]), 1, 1, 1.0, 0, None, None),
+    case('tai_grad_scale', P, ('i64', [16, 16385, 0, 0]), 1, 1, 1.0, 0, None, None),
+    case('tai_step_verdict', None, None, 0, 0.0, 0, 0, 1, 1, None, None),
+    case('tai_step_verdict', None, None, 0, 0.0, 0, 0, 1, 1, 12, None),
+    case('tai_step_verdict', P, None, 1, 0.0, 0, 0, 1, 1, P, None),
+    case('tai_step_verdict', 12, P, 1, 0.0, 0, 0, 1, 1, P, None),
+    case('tai_step_verdict', P, P, 0, 0.0, 0, 0, 1, 1, P, None),
+    case('tai_step_verdict', None, None, 0, 0.0, 2, 0, 1, 1, P, None),
+    case('tai_step_verdict', None, None, 0, 0.0, 0, 0, 0, 1, P, None),
+    case('tai_step_verdict', None, None, 0, -1.0, 0, 0, 1, 1, P, None),
+    case('tai_step_verdict', None, None, 0, ('f', 'nan'), 0, 0, 1, 1, P, None),
+    case('tai_fused_step', P, ZROW8, 1, 0, None, 1, 0.1, 0.9, 0.1, 1e-8, 0.0, P, 0, 0, 0, None, None),
+    case('tai_fused_step', P, ZROW8, 0, 0, P, 1, 0.1, 0.9, 0.1, 1e-8, 0.0, P, 0, 0, 0, None, None),
+    case('tai_fused_step', P, ZROW8, 1, 0, P, 1, 0.1, 0.9, 0.1, 1e-8, 0.0, 12, 0, 0, 0, None, None),
+    case('tai_fused_step', P, ZROW8, 1, 0, P, 0, 0.1, 0.9, 0.1, 1e-8, 0.0, P, 0, 0, 0, None, None),
+    case('tai_fused_step', P, ('i64', [16, 16, 16, 0, 16, 0, 4, 0]), 1, 1, P, 1, 0.1, 0.9, 0.1, 1e-8, 0.0, P, 0, 0, 0, None, None),
+    case('tai_fused_step', P, ('i64', [16, 16, 16, 16, 16, 18, 4, 0]), 1, 1, P, 1, 0.1, 0.9, 0.1, 1e-8, 0.0, P, 0, 0, 0, None, None),
+    case('tai_fused_step', P, ('i64', [0, 0, 0, 0, 16, 16, 0, 0]), 1, 0, P, 1, 0.1, 0.9, 0.1, 1e-8, 0.0, P, 0, 0, 0, None, None),
+    case('tai_fused_step', P, ('i64', [16, 16, 16, 16, 16, 0, 4, 0, 16, 16, 16, 16, 16, 0, 4, 2]), 2, 2, P, 1, 0.1, 0.9, 0.1, 1e-8, 0.0, P, 0,
+         0, 0, None, None),
+    case('tai_fused_step', P, ('i64', [16, 16, 16, 16, 16, 0, 4, 0]), 1, 2, P, 1, 0.1, 0.9, 0.1, 1e-8, 0.0, P, 0, 0, 0, None, None),
+]
+
+# The refusal messages of the shipped build that no case reaches, each with why (the table may leave out 16 at the most):
+NOT_REACHED = {
+    'conv3x3_wino: the split-bf16 arithmetic needs even H and W':
+        'needs a weight buffer that tai_conv3x3_wino_transform_weights registered, and that call launches',
+    'conv3x3_wino_wrw: timeline stamps need even H and W % 16 == 0': 'stamps reach the launcher only through the tools build\'s timeline entry',
+    'conv_bf16_forward: no tile fits': 'cbf16::plan finds a tile for every shape the earlier checks admit',
+    'frame_metrics: too many tiles (2^31 or more)': 'no shape below the 2^40-element limit has 2^31 tiles',
+    'ssim_loss: too many tiles (2^31 or more)': 'no shape below the 2^40-element limit has 2^31 tiles',
+}
+
+
+def _load(path):
+    L = ctypes.CDLL(path)
+    for name, (restype, argtypes) in _native.signatures().items():
+        entry = getattr(L, name)
+        entry.restype, entry.argtypes = restype, argtypes
+    return L
+
+
+def _arg(a, keep):
+    if isinstance(a, (list, tuple)):
+        kind, values = a
+        if kind == 'f':
+            return float(values)
+        array = ((ctypes.c_void_p if kind == 'ptrs' else ctypes.c_longlong) * len(values))(*values)
+        keep.append(array)
+        return ctypes.cast(array, ctypes.c_void_p)
+    return a
+
+
+def answer(L, c):
+    """(return code, message) of one case on the library L."""
+    keep = []
+    for name, *args in c['before']:
+        getattr(L, name)(*args)
+    try:
+        rc = getattr(L, c['entry'])(*[_arg(a, keep) for a in c['args']])
+        return [rc, L.tai_sepconv_last_error().decode()]
+    finally:
+        for name, *args in c['after']:
+            getattr(L, name)(*args)
+
+
+def _jsonable(c):
+    return json.loads(json.dumps(c))
+
+
+def source_literals():
+    """The distinct fail(TAI_SEPCONV_EINVAL, "%s", "...") messages of the shipped build's launchers (-DTAI_TIMING_VARIANTS blocks left out)."""
+    text = ''.join(open(p).read() for p in _native.sources() if os.path.basename(p) == 'sepconv_capi.hip' or os.path.basename(p).startswith('capi_'))
+    kept, skipping = [], False
+    for line in text.split('\n'):
+        if line.startswith('#ifdef TAI_TIMING_VARIANTS'):
+            skipping = True
+        elif skipping and line.startswith(('#else', '#endif')):
+            skipping = False
+        elif not skipping:
+            kept.append(line)
+    found = re.findall(r'fail\(TAI_SEPCONV_EINVAL, "%s",\s*((?:"(?:[^"\\]|\\.)*"\s*)+)\)', '\n'.join(kept))
+    return {''.join(re.findall(r'"((?:[^"\\]|\\.)*)"', f)) for f in found}
+
+
+@pytest.fixture(scope='module')
+def golden():
+    return json.load(open(GOLDEN))
+
+
+def test_the_table_is_the_one_the_cases_describe(golden):
+    assert [{k: r[k] for k in ('entry', 'args', 'before', 'after')} for r in golden['refusals']] == [_jsonable(c) for c in CASES]
+    assert re.fullmatch(r'[0-9a-f]{7,40}', golden['recorded_on'])
+    assert all(r['answer'][0] == EINVAL and r['answer'][1] for r in golden['refusals'])
+
+
+def test_every_entry_with_a_stream_and_all_but_a_few_messages_are_covered(golden):
+    header = _native._header_text()
+    with_stream = set(re.findall(r'\b(tai_\w+)\s*\([^)]*\bhip_stream\)', header))
+    assert len(with_stream) > 50 and with_stream <= {r['entry'] for r in golden['refusals']}
+    literals, said = source_literals(), {r['answer'][1] for r in golden['refusals']}
+    assert len(literals) >= 111
+    assert literals - said == set(NOT_REACHED) and len(NOT_REACHED) <= 16
+
+
+def test_refusals_are_what_they_were(golden):
+    # replayed in a child process that sees no device: should a change ever stop refusing one of these calls, the call fails at
+    # its launch there instead of running a kernel on the dummy pointers
+    _native.verify(_native.LIB_PATH)
+    out = subprocess.run([sys.executable, os.path.abspath(__file__), '--answers', _native.LIB_PATH], env=dict(os.environ, **NO_DEVICE),
+                         capture_output=True, text=True, timeout=120)
+    assert out.returncode == 0, out.stderr[-2000:]
+    got = json.loads(out.stdout)
+    wrong = [(r['entry'], r['args'], r['answer'], g) for r, g in zip(golden['refusals'], got) if g != r['answer']]
+    assert len(got) == len(golden['refusals']) and not wrong, wrong[:5]
+
+
+if __name__ == '__main__':
+    if sys.argv[1:2] == ['--answers'] and len(sys.argv) == 3:
+        assert all(os.environ.get(k) == v for k, v in NO_DEVICE.items())
+        L = _load(sys.argv[2])
+        print(json.dumps([answer(L, r) for r in json.load(open(GOLDEN))['refusals']]))
+        sys.exit(0)
+    if len(sys.argv) != 4 or sys.argv[1] != '--record':
+        sys.exit(__doc__)
+    os.environ.update(NO_DEVICE)
+    L = _load(sys.argv[2])
+    rows = []
+    for c in CASES:
+        rc, msg = answer(L, c)
+        if rc != EINVAL:
+            sys.exit('NOT a refusal (%d, %r): %s%r -- remove the case, it may not be recorded' % (rc, msg, c['entry'], c['args']))
+        rows.append(dict(_jsonable(c), answer=[rc, msg]))
+    with open(GOLDEN, 'w') as f:
+        f.write('{"recorded_on": "%s",\n "refusals": [\n' % sys.argv[3])
+        f.write(',\n'.join('  ' + json.dumps(r) for r in rows))
+        f.write('\n]}\n')
+    print('%d refusals, %d distinct messages' % (len(rows), len({r['answer'][1] for r in rows})))

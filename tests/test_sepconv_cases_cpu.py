@@ -81,7 +81,7 @@ def test_tiling_constants_match_the_kernels():
     assert (sc.GI_R + 51 - 1) * const('SPITCH') == sc.GI_SLAB == 10800
     assert 'constexpr int KS = 51, THREADS = 512, TILE_H = %d;' % sc.GV_TILE_H in bwd       # sepconv_grad_vh_ab
     assert 'ROWS_PER_WAVE = 2 / SPLIT;' in fwd and 'WAVES = SPLIT == 1 ? 4 : 8;' in fwd      # Cfg<KS, 1>::TILE_H = 2 * 4
-    capi = open(os.path.join(CSRC, 'sepconv_capi.hip')).read()
+    capi = open(os.path.join(CSRC, 'capi_sepconv.inc')).read()
     assert 'const bool tileable = (ks == 51) && (W % 4 == 0) && (C == 1 || C == 3);' in capi
 
 
@@ -205,7 +205,9 @@ def test_forward_shapes_reach_the_route_they_are_listed_for():
 
 def test_forward_constants_and_route_conditions_match_the_sources():
     fwd = open(os.path.join(CSRC, 'sepconv_fwd.hip.inc')).read()
-    capi = open(os.path.join(CSRC, 'sepconv_capi.hip')).read()
+    # the launchers: every host file of the translation unit, so that "no second copy" means none anywhere
+    capi = ''.join(open(os.path.join(CSRC, f)).read() for f in ['sepconv_capi.hip'] + sorted(f for f in os.listdir(CSRC) if f.startswith('capi_')))
+    assert 'int persistent_policy(' in open(os.path.join(CSRC, 'capi_sepconv.inc')).read()
     # the persistent kernel and the kernels it shares its row loops with
     pers = fwd[fwd.index('void sepconv_forward_persistent('):fwd.index('// ---- multi-channel frames (RGB)')]
     m = re.search(r'constexpr int KS = (\d+), WAVES = (\d+), TILE_H = (\d+);\s+constexpr int PR = TILE_H \+ KS - 1, PITCH = (\d+);', pers)

@@ -239,7 +239,8 @@ def test_plain_references_agree_with_aten_on_the_cpu():
 
 
 def test_launch_constants_match_the_sources():
-    capi = open(os.path.join(CSRC, 'sepconv_capi.hip')).read()
+    capi = open(os.path.join(CSRC, 'capi_pointwise.inc')).read()          # the launchers of these kernels
+    helpers = open(os.path.join(CSRC, 'sepconv_capi.hip')).read()
     thin = open(os.path.join(CSRC, 'thin_conv.hip.inc')).read()
     bact = open(os.path.join(CSRC, 'bias_act.hip.inc')).read()
     snorm = open(os.path.join(CSRC, 'spectral_norm.hip.inc')).read()
@@ -249,11 +250,15 @@ def test_launch_constants_match_the_sources():
         start = capi.index('\nint %s(' % name)
         return capi[start:capi.index('\n}\n', start)]
 
+    # grid_for(work, cap): workgroups of 256 threads over the work items, at most cap
+    assert re.search(r'int grid_for\(long long work, int cap\) \{\s+const long long blocks = \(work \+ 255\) / 256;\s+'
+                     r'return \(int\)\(blocks < cap \? blocks : cap\);\s+\}', helpers)
+
     def cap_of(name, count='work'):
-        m = re.search(r'\(%s \+ 255\) / 256 < (\d+) \? \(%s \+ 255\) / 256 : (\d+)\)' % (count, count), body(name))
-        assert m and m.group(1) == m.group(2), name
+        m = re.findall(r'const int blocks = grid_for\(%s, (\d+)\);' % count, body(name))
+        assert len(m) == 1, name
         assert 'dim3(256)' in body(name)
-        return int(m.group(1))
+        return int(m[0])
 
     caps = tc.BLOCK_CAPS
     assert cap_of('tai_conv_cin1_forward') == caps['cin1'] and cap_of('tai_conv_cin1_forward_maxpool_window') == caps['cin1_pool']
@@ -267,7 +272,7 @@ def test_launch_constants_match_the_sources():
         assert 'const int blocks = planes < %d ? planes : %d;' % ((caps['window_scale_scalar'],) * 2) in body(name)
     up = body('tai_upsample_bilinear2x_forward')
     assert 'const int per_plane = H * (2 * W / 4);' in up
-    assert 'const int bx = (per_plane + 255) / 256 < %d ? (per_plane + 255) / 256 : %d;' % ((tc.UPS_XBLOCKS,) * 2) in up
+    assert 'const int bx = grid_for(per_plane, %d);' % tc.UPS_XBLOCKS in up
     assert 'if ((2 * W) % 4 == 0 && H >= 2 && W >= 2 &&' in up
     assert 'for (int t = blockIdx.x * blockDim.x + threadIdx.x; t < per_plane; t += gridDim.x * blockDim.x) {' in ups
     # the work counts

@@ -12,7 +12,7 @@ Data:
   * the pointwise kernels are one fp32 operation per element and take any finite floats; ``quantised`` makes the operands of
     the window_scale forward (a product and a sum, which a compiler may or may not contract) exact either way.
 
-The launch constants restate csrc/sepconv_capi.hip's launchers and the kernels' own arithmetic; the CPU test reads them back
+The launch constants restate csrc/capi_pointwise.inc's launchers and the kernels' own arithmetic; the CPU test reads them back
 from the sources, so that a changed cap fails there first.
 
 The upsample's gradient kernel caps its grid at 65,536 blocks: crossing that needs 16.8 M work items of four gradient
