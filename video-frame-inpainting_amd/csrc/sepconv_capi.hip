@@ -35,6 +35,7 @@
 #include "ssim_loss.hip.inc"
 #include "image_loss.hip.inc"
 #include "lap_loss.hip.inc"
+#include "temporal_loss.hip.inc"
 #include "clip_pipeline.hip.inc"
 #include "state_digest.hip.inc"
 #include "grad_stats.hip.inc"
@@ -140,7 +141,7 @@ void wino_div_magic(long long d, unsigned& m, unsigned& sh) {
 
 extern "C" {
 
-int tai_sepconv_version(void) { return 830; }
+int tai_sepconv_version(void) { return 840; }
 
 const char* tai_sepconv_last_error(void) { return g_err; }
 

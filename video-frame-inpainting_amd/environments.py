@@ -23,7 +23,7 @@ import torch
 from . import conv_ops, parallel, run_state
 from . import fused_step as fused_step_module
 from .graph import GraphedForward
-from .losses import GDL, IMAGE_LOSS_KINDS, ImageLoss, LapLoss, SSIMLoss
+from .losses import GDL, IMAGE_LOSS_KINDS, ImageLoss, LapLoss, SSIMLoss, TemporalLoss
 from .mcnet import MCNetFillInModel
 from .sn_discriminator import SNDiscriminator
 from .ablations import (BidirectionalSimpleAverageFillInModel, BidirectionalTimeWeightedAverageFillInModel,
@@ -46,7 +46,8 @@ def create_eval_environment(fill_in_model, checkpoints_dir, name, snapshot_file_
 def create_training_environment(fill_in_model, c_dim, checkpoints_dir, name, max_K, max_T, max_F, image_size, alpha,
                                 beta, lr, beta1, df_dim, Ip, disc_window_size, padding_size, device=None, graph_step=False,
                                 resumable=False, guard=None, fused_step=False, ema_decay=None, max_iter=100000, ssim_weight=0.0,
-                                image_loss='l2', charbonnier_eps=1e-3, lap_weight=0.0, lap_levels=5):
+                                image_loss='l2', charbonnier_eps=1e-3, lap_weight=0.0, lap_levels=5, temporal_weight=0.0,
+                                temporal_kind='charbonnier', temporal_eps=1e-3):
     if not ssim_weight >= 0.0:
         raise ValueError('ssim_weight must not be negative, found %r' % (ssim_weight,))
     if not lap_weight >= 0.0:
@@ -55,6 +56,12 @@ def create_training_environment(fill_in_model, c_dim, checkpoints_dir, name, max
         raise ValueError('image_loss must be one of %s, found %r' % (', '.join(IMAGE_LOSS_KINDS), image_loss))
     if not (charbonnier_eps > 0.0 and charbonnier_eps != float('inf')):
         raise ValueError('charbonnier_eps must be finite and > 0, found %r' % (charbonnier_eps,))
+    if not temporal_weight >= 0.0:
+        raise ValueError('temporal_weight must not be negative, found %r' % (temporal_weight,))
+    if temporal_kind not in IMAGE_LOSS_KINDS:
+        raise ValueError('temporal_kind must be one of %s, found %r' % (', '.join(IMAGE_LOSS_KINDS), temporal_kind))
+    if not (temporal_eps > 0.0 and temporal_eps != float('inf')):
+        raise ValueError('temporal_eps must be finite and > 0, found %r' % (temporal_eps,))
     if guard is not None and graph_step:
         raise ValueError('a guarded update cannot be a captured one: a replayed update cannot leave out an optimizer step')
     if fused_step and graph_step:
@@ -68,12 +75,14 @@ def create_training_environment(fill_in_model, c_dim, checkpoints_dir, name, max
             fill_in_model, checkpoints_dir, name, image_size, c_dim, alpha, beta, lr, beta1,
                                      df_dim, Ip, disc_window_size, max_K, max_T, max_F, padding_size, device=device,
                                      graph_step=graph_step, ssim_weight=ssim_weight, image_loss=image_loss,
-                                     charbonnier_eps=charbonnier_eps, lap_weight=lap_weight, lap_levels=lap_levels)
+                                     charbonnier_eps=charbonnier_eps, lap_weight=lap_weight, lap_levels=lap_levels,
+                                     temporal_weight=temporal_weight, temporal_kind=temporal_kind, temporal_eps=temporal_eps)
     elif isinstance(fill_in_model, MCNetFillInModel):
         env = MCNetTrainingEnvironment(fill_in_model, checkpoints_dir, name, image_size, c_dim, alpha, beta, lr, beta1,
                                        df_dim, Ip, disc_window_size, max_K, max_T, max_F, padding_size, device=device,
                                        graph_step=graph_step, ssim_weight=ssim_weight, image_loss=image_loss,
-                                     charbonnier_eps=charbonnier_eps, lap_weight=lap_weight, lap_levels=lap_levels)
+                                     charbonnier_eps=charbonnier_eps, lap_weight=lap_weight, lap_levels=lap_levels,
+                                     temporal_weight=temporal_weight, temporal_kind=temporal_kind, temporal_eps=temporal_eps)
     else:
         raise RuntimeError('Tried to create a training environment for object of unsupported type %s'
                            % type(fill_in_model).__name__)
@@ -271,9 +280,12 @@ class BaseTrainingEnvironment(BaseVideoFillInEnvironment):
     def forward_train(self):
         self.gen_output = self.generator(self.T, self.preceding_frames, self.following_frames)
 
-    # attributes an update produces (tensors of the captured graph's pool when the update is replayed)
+    # attributes an update produces (tensors of the captured graph's pool when the update is replayed).  Every tensor with autograd
+    # history that an update leaves on the environment belongs here -- a new loss term's values included: train_step detaches these
+    # before a capture ends, and one that is missing outlives the capture and faults the HIP runtime when it is closed
     _STEP_OUTPUTS = ('gen_output', 'loss_G', 'Lp', 'gdl', 'L_GAN', 'loss_d_fake', 'loss_d_real', 'loss_D', 'Lp_forward',
-                     'Lp_backward', 'gdl_forward', 'gdl_backward', 'ssim', 'ssim_forward', 'ssim_backward', 'lap', 'lap_forward', 'lap_backward')
+                     'Lp_backward', 'gdl_forward', 'gdl_backward', 'ssim', 'ssim_forward', 'ssim_backward', 'lap', 'lap_forward', 'lap_backward',
+                     'temporal', 'temporal_forward', 'temporal_backward')
 
     def train_step(self, preceding_frames, following_frames, gt_middle_frames):
         """One update on a batch: set_train_inputs + forward_train + optimize_parameters (src/train.py:147-169), with
@@ -484,7 +496,7 @@ class L2GDLDiscTrainingEnvironment(BaseTrainingEnvironment):
 
     def __init__(self, fill_in_model, checkpoints_dir, name, image_size, c_dim, alpha, beta, lr, beta1, df_dim, Ip,
                  disc_t, max_K, max_T, max_F, padding_size, device=None, graph_step=False, ssim_weight=0.0, image_loss='l2',
-                 charbonnier_eps=1e-3, lap_weight=0.0, lap_levels=5):
+                 charbonnier_eps=1e-3, lap_weight=0.0, lap_levels=5, temporal_weight=0.0, temporal_kind='charbonnier', temporal_eps=1e-3):
         super().__init__(fill_in_model, checkpoints_dir, name, lr, beta1, max_K, max_T, max_F, padding_size, device=device,
                          graph_step=graph_step)
         # ssim_weight (train.py --ssim_weight G) > 0: loss_G gains G (1 - mean SSIM) per prediction (losses.SSIMLoss, one HIP launch for
@@ -499,6 +511,11 @@ class L2GDLDiscTrainingEnvironment(BaseTrainingEnvironment):
         # with lap_levels levels, one HIP launch for the loss and its gradient); 0 = no module, no launch, no extra key
         self.lap_weight = float(lap_weight)
         self.loss_lap = LapLoss(lap_levels) if self.lap_weight > 0 else None
+        # temporal_weight (train.py --temporal_weight G) > 0: loss_G gains G times the temporal-difference term of every prediction
+        # (losses.TemporalLoss: one HIP launch for all predictions of an update, each read in its own layout -- gen_output['pred'] is a
+        # time-major view and is not copied); 0 = no module, no launch, no extra key
+        self.temporal_weight = float(temporal_weight)
+        self.loss_temporal = TemporalLoss(temporal_kind, temporal_eps) if self.temporal_weight > 0 else None
         self._fake_labels = {}
         self.loss_Lp = torch.nn.MSELoss()
         self.loss_gdl = GDL()
@@ -609,6 +626,14 @@ class L2GDLDiscTrainingEnvironment(BaseTrainingEnvironment):
         if self.loss_lap is not None:
             self.lap = self.loss_lap(self.gen_output['pred'], self.gt_middle_frames)
             self.loss_G = self.loss_G + self.lap_weight * self.lap
+        if self.loss_temporal is not None:
+            temporal = self.loss_temporal(tuple(self.gen_output[k] for k in self._IMAGE_LOSS_KEYS), self.gt_middle_frames)
+            self.temporal = temporal[0]
+            self.loss_G = self.loss_G + self.temporal_weight * self.temporal
+            self._add_further_temporal_losses(temporal[1:])
+
+    def _add_further_temporal_losses(self, losses):
+        """The temporal terms of ``_IMAGE_LOSS_KEYS[1:]`` (they came from the same launch as ``pred``'s): none here."""
 
     def _add_further_image_losses(self, losses):
         """The image losses of ``_IMAGE_LOSS_KEYS[1:]`` (they came from the same launch as ``pred``'s): none here."""
@@ -622,6 +647,8 @@ class L2GDLDiscTrainingEnvironment(BaseTrainingEnvironment):
             d['G_ssim'] = float(self.ssim.item())
         if self.loss_lap is not None:
             d['G_lap'] = float(self.lap.item())
+        if self.loss_temporal is not None:
+            d['G_temporal'] = float(self.temporal.item())
         return d
 
     def train(self):
@@ -674,6 +701,10 @@ class TAITrainingEnvironment(L2GDLDiscTrainingEnvironment):
         (self.Lp_forward, self.gdl_forward), (self.Lp_backward, self.gdl_backward) = self.loss_image.last_terms[1:]
         self.loss_G = self.loss_G + self.alpha * (losses[0] + losses[1])
 
+    def _add_further_temporal_losses(self, losses):
+        self.temporal_forward, self.temporal_backward = losses
+        self.loss_G = self.loss_G + self.temporal_weight * (self.temporal_forward + self.temporal_backward)
+
     def get_current_errors(self):
         d = super().get_current_errors()
         d.update({'G_Lp_forward': float(self.Lp_forward.item()), 'G_gdl_forward': float(self.gdl_forward.item()),
@@ -682,4 +713,6 @@ class TAITrainingEnvironment(L2GDLDiscTrainingEnvironment):
             d.update({'G_ssim_forward': float(self.ssim_forward.item()), 'G_ssim_backward': float(self.ssim_backward.item())})
         if self.loss_lap is not None:
             d.update({'G_lap_forward': float(self.lap_forward.item()), 'G_lap_backward': float(self.lap_backward.item())})
+        if self.loss_temporal is not None:
+            d.update({'G_temporal_forward': float(self.temporal_forward.item()), 'G_temporal_backward': float(self.temporal_backward.item())})
         return d

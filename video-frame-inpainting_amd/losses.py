@@ -1,6 +1,6 @@
 """Image gradient difference loss (reference src/losses/losses.py:4-44, Mathieu et al.), and this build's opt-in losses: SSIMLoss
-(train.py --ssim_weight), ImageLoss (train.py --image_loss l1 / charbonnier) and LapLoss (train.py --lap_weight), each a written
-definition with a HIP kernel behind it."""
+(train.py --ssim_weight), ImageLoss (train.py --image_loss l1 / charbonnier), LapLoss (train.py --lap_weight) and TemporalLoss
+(train.py --temporal_weight), each a written definition with a HIP kernel behind it."""
 import torch
 import torch.nn as nn
 
@@ -359,3 +359,144 @@ class LapLoss(nn.Module):
         loss, terms, planes = _lap_terms(input, target.to(device=input.device, dtype=input.dtype), self.levels)
         self.last_terms, self.plane_terms = terms.detach().to(input.dtype), planes.detach()
         return loss.to(input.dtype)
+
+
+def _temporal_terms(pred, gt, kind, eps):
+    """(loss, terms [T + 1], seq_terms [B * C, T + 1]) in float64 by torch ops, differentiable by autograd: the definition of
+    ``tai_temporal_loss`` (include/tai_sepconv.h) up to the order of the sums; the element-wise terms are formed in the tensors' own
+    precision."""
+    B, T, C, H, W = pred.shape
+    e = (pred + 1) / 2 - (gt + 1) / 2                             # util.inverse_transform, not clipped
+    known = torch.zeros_like(e[:, :1])                            # e_{-1} = e_T = 0: the known frames on both sides of the gap
+    e = torch.cat([known, e, known], dim=1)
+    d = e[:, 1:] - e[:, :-1]                                      # d_0 .. d_T
+    if kind == 0:
+        rho = d * d
+    elif kind == 1:
+        rho = d.abs()                                             # autograd's derivative is sign(d): 0 at 0
+    else:
+        import numpy as np
+        e2 = float(np.float32(eps) * np.float32(eps))             # the definition's constant: eps * eps in fp32, in either precision
+        # the square root is taken in float64 and rounded to the tensors' precision: correctly rounded, as the definition asks (53 bits
+        # are more than twice 24 plus 2, so the second rounding cannot move it), which torch's fp32 square root on the host is not
+        rho = torch.sqrt((d * d + e2).double()).to(pred.dtype)
+    seq_terms = rho.double().sum(dim=(3, 4)).permute(0, 2, 1).reshape(B * C, T + 1)
+    n_pos = float(B * C) * H * W
+    return seq_terms.sum() / (n_pos * (T + 1)), seq_terms.sum(dim=0) / n_pos, seq_terms
+
+
+def _block_strides(t):
+    """(batch stride, time stride) in elements if ``t`` [B, T, C, H, W] can be read where it lies by ``tai_temporal_loss``: every
+    [C, H, W] block dense, the (b, t) blocks apart from each other with one axis nested in the other; else None."""
+    B, T, C, H, W = t.shape
+    sb, st, sc, sh, sw = t.stride()
+    if (W > 1 and sw != 1) or (H > 1 and sh != W) or (C > 1 and sc != H * W):
+        return None
+    chw = C * H * W
+    if B == 1 and T == 1:
+        return chw, chw
+    if B == 1:
+        return (T * st, st) if st >= chw else None
+    if T == 1:
+        return (sb, B * sb) if sb >= chw else None
+    if (st >= chw and sb >= (T - 1) * st + chw) or (sb >= chw and st >= (B - 1) * sb + chw):
+        return sb, st
+    return None
+
+
+class _TemporalLossFunction(torch.autograd.Function):
+    """``tai_temporal_loss`` on the current stream for 1-3 predictions: (losses fp32 [n], terms fp32 [n, T + 1], seq_terms float64
+    [n, B * C, T + 1]).  Every tensor is passed where it lies with its own batch and time stride when its [C, H, W] blocks are dense
+    (``gen_output['pred']`` is a transposed view of a time-major buffer) and made contiguous otherwise; the gradient maps come from the
+    same launch, each in its prediction's layout, and are what ``backward`` scales; a prediction that needs no gradient, or ``want_maps``
+    false (the caller runs under no_grad), gets no map.  Every allocation is torch's, so under capture it comes from the graph's pool."""
+
+    @staticmethod
+    def forward(ctx, gt, kind, eps, want_maps, *preds):
+        import ctypes
+        from . import _native
+        B, T, C, H, W = gt.shape
+        n = len(preds)
+        L = _native.lib()
+        nbytes = L.tai_temporal_loss_workspace_bytes(n, B, T, C, H, W)
+        if nbytes < 0:
+            raise ValueError('TemporalLoss: %d predictions of %s are outside what tai_temporal_loss takes' % (n, tuple(gt.shape)))
+        dev = gt.device
+        tensors, strides = [], []
+        for t in preds + (gt,):
+            t = t.detach()
+            if _block_strides(t) is None:
+                t = t.contiguous()
+            tensors.append(t)
+            strides.extend(_block_strides(t))
+        S = B * C
+        workspace = torch.empty(nbytes // 8, dtype=torch.float64, device=dev)
+        out = torch.empty(n * S * (T + 1) + n * (T + 2), dtype=torch.float64, device=dev)          # seq_terms, then totals
+        maps = [torch.empty_strided(p.shape, p.stride(), dtype=torch.float32, device=dev) if want_maps and ctx.needs_input_grad[4 + i] else None
+                for i, p in enumerate(tensors[:n])]
+        pred_ptrs = (ctypes.c_void_p * n)(*[p.data_ptr() for p in tensors[:n]])
+        map_ptrs = (ctypes.c_void_p * n)(*[m.data_ptr() if m is not None else None for m in maps])
+        stride_table = (ctypes.c_longlong * (2 * n + 2))(*strides)
+        totals = out[n * S * (T + 1):]
+        _native.launch('tai_temporal_loss', dev, pred_ptrs, n, tensors[n], stride_table, kind, eps, out, totals, map_ptrs, workspace,
+                       B, T, C, H, W)
+        ctx.maps = maps
+        t32 = totals.view(n, T + 2).to(torch.float32)
+        losses, terms, seq_terms = t32[:, T + 1].contiguous(), t32[:, :T + 1], out[:n * S * (T + 1)].view(n, S, T + 1)
+        ctx.mark_non_differentiable(terms, seq_terms)
+        return losses, terms, seq_terms
+
+    @staticmethod
+    def backward(ctx, grad_losses, _grad_terms, _grad_seqs):
+        return (None, None, None, None) + tuple(grad_losses[i] * m if m is not None else None for i, m in enumerate(ctx.maps))
+
+
+class TemporalLoss(nn.Module):
+    """Temporal-difference loss of 1-3 predictions ``[B, T, C, H, W]`` against one target, the definition of ``tai_temporal_loss``
+    (include/tai_sepconv.h): frames mapped to [0, 1] as ``inverse_transform`` does and NOT clipped, e_t the error of frame t and zero on
+    the known frames on both sides of the gap, d_j = e_j - e_{j-1} for j = 0..T, and the loss the mean over the T + 1 positions and every
+    pixel of d^2 (``l2``), |d| (``l1``) or sqrt(d^2 + eps^2) (``charbonnier``): an error that stays constant through the gap is counted
+    at the two seams only, one that changes from frame to frame at every position.  ``forward(preds, target)`` takes one tensor or a tuple
+    of 1-3 and returns one scalar per prediction (a tuple for a tuple).  CUDA fp32 tensors go through ONE launch of the HIP kernel for all
+    predictions, which reads every tensor in its own layout and writes the losses and their gradient maps; anything else (CPU, float64)
+    evaluates the same definition with torch ops and is differentiated by autograd.  ``last_terms`` keeps the last call's per-position
+    means [n, T + 1] and ``seq_terms`` its per-sequence sums [n, B * C, T + 1] (float64), detached.  No parameters, no buffers."""
+
+    def __init__(self, kind='charbonnier', eps=1e-3):
+        super().__init__()
+        if kind not in IMAGE_LOSS_KINDS:
+            raise ValueError('TemporalLoss: kind must be one of %s, found %r' % (', '.join(IMAGE_LOSS_KINDS), kind))
+        eps = float(eps)
+        if not (eps > 0.0 and eps != float('inf')):
+            raise ValueError('TemporalLoss: eps must be finite and > 0, found %r' % (eps,))
+        self.kind, self.eps = kind, eps
+        self.last_terms = None
+        self.seq_terms = None
+
+    def forward(self, preds, target):
+        single = torch.is_tensor(preds)
+        preds = (preds,) if single else tuple(preds)
+        if not 1 <= len(preds) <= 3:
+            raise ValueError('TemporalLoss: takes 1 to 3 predictions, got %d' % len(preds))
+        for p in preds:
+            if p.shape != target.shape or p.dim() != 5:
+                raise ValueError('TemporalLoss: prediction %s and target %s must have one shape [B, T, C, H, W]'
+                                 % (tuple(p.shape), tuple(target.shape)))
+        if target.numel() == 0:
+            raise ValueError('TemporalLoss: needs at least one pixel, got %s' % (tuple(target.shape),))
+        kind = IMAGE_LOSS_KINDS.index(self.kind)
+        if all(t.is_cuda and t.dtype == torch.float32 for t in preds + (target,)):
+            # (inside Function.forward grad mode is always off and needs_input_grad ignores no_grad: the caller's mode is passed in)
+            losses, terms, seqs = _TemporalLossFunction.apply(target, kind, self.eps, torch.is_grad_enabled(), *preds)
+            self.last_terms, self.seq_terms = terms.detach(), seqs.detach()
+            out = tuple(losses[i] for i in range(len(preds)))
+        else:
+            out, terms, seqs = [], [], []
+            for p in preds:
+                loss, tm, sq = _temporal_terms(p, target.to(device=p.device, dtype=p.dtype), kind, self.eps)
+                out.append(loss.to(p.dtype))
+                terms.append(tm.detach().to(p.dtype))
+                seqs.append(sq.detach())
+            self.last_terms, self.seq_terms = torch.stack(terms), torch.stack(seqs)
+            out = tuple(out)
+        return out[0] if single else out

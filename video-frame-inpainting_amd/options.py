@@ -150,6 +150,18 @@ class TrainOptions(BaseOptions):
                             'of an update on the model\'s own layout; the printed keys G_Lp= G_gdl= (_forward, _backward) carry the chosen terms')
         g.add_argument('--charbonnier_eps', type=float, default=1e-3, metavar='E',
                        help='(this build, with --image_loss charbonnier) the eps of sqrt(d^2 + eps^2); finite and > 0')
+        g.add_argument('--temporal_weight', type=float, default=0.0, metavar='G',
+                       help="(this build) add G times the temporal-difference term of every prediction to the generator's loss "
+                            '(losses.TemporalLoss: the frame-to-frame difference of the error over the gap, the error taken as zero on the '
+                            'known frames on both sides, so flicker and the two seams are penalised and a constant error is not counted '
+                            'again; float frames in [0, 1], unclipped; losses and gradients of all predictions from one HIP launch, '
+                            'tai_temporal_loss, on the model\'s own layouts); printed lines gain G_temporal= (TAI: G_temporal_forward= '
+                            'G_temporal_backward= as well).  0 (default) = the loss as before: nothing is launched, no key is added')
+        g.add_argument('--temporal_kind', type=str, default='charbonnier', choices=['l2', 'l1', 'charbonnier'],
+                       help='(this build, with --temporal_weight) the distance on the temporal difference d: l2 = d^2, l1 = |d|, '
+                            'charbonnier (default) = sqrt(d^2 + eps^2) (--temporal_eps)')
+        g.add_argument('--temporal_eps', type=float, default=1e-3, metavar='E',
+                       help='(this build, with --temporal_kind charbonnier) the eps of sqrt(d^2 + eps^2); finite and > 0')
         g.add_argument('--max_wall_minutes', type=float, default=None, metavar='M',
                        help='(this build, with --resumable) stop as after SIGTERM once the run has lasted M minutes')
         g.add_argument('--miopen_find_mode', type=str, default=None, choices=['NORMAL', 'FAST', 'HYBRID', 'DYNAMIC_HYBRID'],
