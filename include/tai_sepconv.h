@@ -411,6 +411,13 @@ int tai_conv_bf16_pack_weights(const float* w, void* Wp, int K, int C, int k, in
  * TAI_SEPCONV_EINVAL with a message outside the rule above or the index space (N C H W and N K H W below 2^31). */
 int tai_conv_bf16_forward(const float* const* xs, int nparts, const void* Wp, const float* bias, float* y, float* ypool,
                           const float* addx, float* y2, int N, int C, int K, int H, int W, int k, int act, void* hip_stream);
+/* The plan tai_conv_bf16_forward launches N x K x H x W, k with (the launcher's own decision, not a restatement: the same host
+ * function).  out[0..10] = MW (4: the 256-pixel tile and the conv_bf16<k, 4, act> instances, 2: 128 pixels), TH, TW (tile rows and
+ * columns, even), IMG (images per tile), PH, PW (patch rows and columns: the tile plus its halo), pitch (patch row pitch in
+ * pixels, PW or raised to 4 mod 8), tiles_x, tiles_y, groups (ceil(N / IMG)), lds_bytes (dynamic LDS of the launch).  Returns the
+ * number of workgroups, tiles_x tiles_y groups ceil(K / 64); TAI_SEPCONV_EINVAL (out untouched) where tai_conv_bf16_forward refuses
+ * these dimensions whatever C >= 16 it is given.  Launches nothing and takes no stream. */
+int tai_conv_bf16_plan(int N, int K, int H, int W, int k, int* out);
 
 /* Per-frame image-quality metrics (csrc/frame_metrics.hip.inc): the reference's compute_errors (train.py:237-287) as
  * video_frame_inpainting_amd/metrics.py restates it.  pred and gt are contiguous fp32 [N, C, H, W] in [-1, 1] (N = B T frames),

@@ -34,6 +34,23 @@ int tai_conv_bf16_pack_weights(const float* w, void* Wp, int K, int C, int k, in
     return check_launch("conv_bf16_pack_weights");
 }
 
+// The plan of a launch as a query: the same cbf16::plan call and the same refusals (with the forward's words) as tai_conv_bf16_forward
+// makes for N, K, H, W and k.  No stream, no launch.
+int tai_conv_bf16_plan(int N, int K, int H, int W, int k, int* out) {
+    g_err[0] = 0;
+    if (!out) return fail(TAI_SEPCONV_EINVAL, "%s", "null pointer");
+    if (!bf16_shape_ok(K, 16, k)) return fail(TAI_SEPCONV_EINVAL, "%s", "conv_bf16_forward: needs C >= 16, K >= 16 and k in {3, 5, 7}");
+    if (N <= 0 || H <= 0 || W <= 0)
+        return fail(TAI_SEPCONV_EINVAL, "%s", "conv_bf16_forward: needs N, H, W >= 1, C a multiple of the part count, act in {0, 1, 2}");
+    if ((long long)N * K * H * W >= (1LL << 31))
+        return fail(TAI_SEPCONV_EINVAL, "%s", "conv_bf16_forward: tensor too large (2^31 elements or more)");
+    const cbf16::Plan pl = cbf16::plan(N, K, H, W, k);
+    if (pl.blocks <= 0 || pl.blocks >= (1LL << 31)) return fail(TAI_SEPCONV_EINVAL, "%s", "conv_bf16_forward: no tile fits");
+    const int v[11] = {pl.MW, pl.TH, pl.TW, pl.IMG, pl.PH, pl.PW, pl.pitch, pl.tiles_x, pl.tiles_y, pl.groups, pl.lds_bytes};
+    for (int i = 0; i < 11; ++i) out[i] = v[i];
+    return (int)pl.blocks;
+}
+
 int tai_conv_bf16_forward(const float* const* xs, int nparts, const void* Wp, const float* bias, float* y, float* ypool, const float* addx,
                           float* y2, int N, int C, int K, int H, int W, int k, int act, void* hip_stream) {
     g_err[0] = 0;
