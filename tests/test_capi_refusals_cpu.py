@@ -321,7 +321,8 @@ def _jsonable(c):
 
 
 def source_literals():
-    """The distinct fail(TAI_SEPCONV_EINVAL, "%s", "...") messages of the shipped build's launchers (-DTAI_TIMING_VARIANTS blocks left out)."""
+    """The distinct fail(TAI_SEPCONV_EINVAL, "%s", "...") messages of the shipped build's launchers (-DTAI_TIMING_VARIANTS blocks left out),
+    with the four that tai_ssim_loss takes from ssimloss::refusal."""
     text = ''.join(open(p).read() for p in _native.sources() if os.path.basename(p) == 'sepconv_capi.hip' or os.path.basename(p).startswith('capi_'))
     kept, skipping = [], False
     for line in text.split('\n'):
@@ -332,7 +333,9 @@ def source_literals():
         elif not skipping:
             kept.append(line)
     found = re.findall(r'fail\(TAI_SEPCONV_EINVAL, "%s",\s*((?:"(?:[^"\\]|\\.)*"\s*)+)\)', '\n'.join(kept))
-    return {''.join(re.findall(r'"((?:[^"\\]|\\.)*)"', f)) for f in found}
+    # tai_ssim_loss's words are in ssimloss::refusal (csrc/ssim_loss.hip.inc), which its launcher shares with the workspace query
+    shared = re.findall(r'return "(ssim_loss: [^"]*)";', open(os.path.join(_native.CSRC, 'ssim_loss.hip.inc')).read())
+    return {''.join(re.findall(r'"((?:[^"\\]|\\.)*)"', f)) for f in found} | set(shared)
 
 
 @pytest.fixture(scope='module')

@@ -3,9 +3,7 @@ definition (ssim_loss_ref.py): gradient bit for bit, plane values and loss to 1e
 reproducible, batch-independent, isolated from a non-finite plane, capturable; and train.py --ssim_weight with the other run options.
 The tile is 16 x 16 pixels: sizes below run from a single window over one below / at / one above the tile to three tiles each way."""
 import functools
-import gc
 import os
-import re
 import sys
 
 import numpy as np
@@ -14,6 +12,8 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import ssim_loss_ref as ref  # noqa: E402
+import loss_kit as kit  # noqa: E402
+from loss_kit import _bits, _generator, _rel, _states, _train  # noqa: E402
 
 from video_frame_inpainting_amd import _native  # noqa: E402
 from video_frame_inpainting_amd.losses import SSIMLoss  # noqa: E402
@@ -55,14 +55,6 @@ def _launch(pred, gt, with_grad=True):
     assert rc == 0, L.tai_sepconv_last_error()
     torch.cuda.synchronize()
     return planes.cpu().numpy(), totals.cpu().numpy(), grad.cpu().numpy() if with_grad else None
-
-
-def _bits(a):
-    return np.ascontiguousarray(a).view(np.int32 if a.dtype == np.float32 else np.int64)
-
-
-def _rel(a, b):
-    return float(np.max(np.abs(a - b) / np.maximum(np.abs(b), 1e-300)))
 
 
 @pytest.mark.parametrize('shape', CASES, ids=lambda s: 'x'.join(map(str, s)))
@@ -176,66 +168,14 @@ def test_forward_and_backward_replay_inside_one_graph():
     p2, g2, want2 = _case('uniform', shape, seed=2)
     sp = torch.from_numpy(np.array(p1)).to(DEV).requires_grad_()
     sg = torch.from_numpy(np.array(g1)).to(DEV)
-    module = SSIMLoss()
-    side = torch.cuda.Stream()
-    side.wait_stream(torch.cuda.current_stream())
-    with torch.cuda.stream(side):                                                     # warm-up outside the capture
-        module(sp, sg).backward()
-    torch.cuda.current_stream().wait_stream(side)
-    sp.grad = None
-    torch.cuda.synchronize()
-    gc.collect()
-    graph = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(graph):
-        loss = module(sp, sg)
-        loss.backward()
-        loss = loss.detach()                                                          # nothing with history outlives the capture
-    with torch.no_grad():
-        sp.copy_(torch.from_numpy(np.array(p2)))
-        sg.copy_(torch.from_numpy(np.array(g2)))
-    graph.replay()
-    torch.cuda.synchronize()
-    eager_p = torch.from_numpy(np.array(p2)).to(DEV).requires_grad_()
-    eager_loss = SSIMLoss()(eager_p, torch.from_numpy(np.array(g2)).to(DEV))
-    eager_loss.backward()
-    assert float(loss) == float(eager_loss.detach())
-    assert torch.equal(sp.grad.view(torch.int32), eager_p.grad.view(torch.int32))
-    assert np.array_equal(_bits(sp.grad.cpu().numpy()), _bits(want2['grad']))
+    kit.check_graph_replay(SSIMLoss, [sp], sg, [p2], g2, [want2['grad']], single=True)
 
 
 # ---------------------------------------------------------------------------------------------------------------- drivers
 
-SPEC = '{"class": "TAIFillInModel", "args": [4, 1, 3, 51], "kwargs": {"num_block": 5, "kf_dim": 2}}'
-K, T, F, SIZE = 3, 2, 3, 32
-
-
-def _train(tmp_path, capsys, name, max_iter, extra):
-    import train
-    capsys.readouterr()
-    train.main(['--name', name, '--K', str(K), '--T', str(T), '--F', str(F), '--c_dim', '1', '--image_size', str(SIZE), '--model_key', SPEC,
-                '--checkpoints_dir', str(tmp_path / 'ckpt'), '--batch_size', '2', '--max_iter', str(max_iter), '--print_freq', '1',
-                '--df_dim', '8', '--synthetic', '4'] + list(extra))
-    return capsys.readouterr().out
-
-
-def _states(out):
-    return dict((int(i), s) for i, s in re.findall(r'^iter (\d+) .* state=([0-9a-f]{16})$', out, re.M))
-
-
 def _terms(out, n):
     """{key: [value per printed update]} of the three SSIM terms; asserts each is printed on every line, finite, inside (0, 2)."""
-    found = {}
-    for key in ('G_ssim', 'G_ssim_forward', 'G_ssim_backward'):
-        values = [float(v) for v in re.findall(r' %s=(\S+)' % key, out)]
-        assert len(values) == n, (key, out)
-        assert all(np.isfinite(v) and 0.0 < v < 2.0 for v in values), (key, values)
-        found[key] = values
-    return found
-
-
-def _generator(tmp_path, name):
-    snap = torch.load(str(tmp_path / 'ckpt' / name / 'model_latest.ckpt'), map_location='cpu', weights_only=False)
-    return snap['generator']
+    return kit._terms(out, n, ('G_ssim', 'G_ssim_forward', 'G_ssim_backward'), 0.0, 2.0)
 
 
 def test_the_flag_adds_its_terms_and_weight_zero_is_the_run_without_it(tmp_path, capsys, monkeypatch):
@@ -256,22 +196,10 @@ def test_the_flag_adds_its_terms_and_weight_zero_is_the_run_without_it(tmp_path,
                          ids=['resumable', 'guard_fused_ema'])
 def test_straight_against_split_with_the_term(tmp_path, capsys, monkeypatch, extra):
     monkeypatch.chdir(tmp_path)
-    extra = ['--resumable', '--ssim_weight', '0.2'] + extra
-    straight = _train(tmp_path, capsys, 'A', 4, extra)
-    first = _train(tmp_path, capsys, 'B', 2, extra)
-    second = _train(tmp_path, capsys, 'B', 4, extra)
-    assert 'carries no run_state' not in second and 'falling back' not in second
-    sa, sb1, sb2 = _states(straight), _states(first), _states(second)
-    print('straight', sa, 'split', sb1, sb2)
-    assert sorted(sa) == [1, 2, 3, 4] and sorted(sb1) == [1, 2] and sorted(sb2) == [3, 4]
-    assert sa == {**sb1, **sb2} and len(set(sa.values())) == 4
-    _terms(straight, 4)
+    kit.check_straight_against_split(tmp_path, capsys, ['--resumable', '--ssim_weight', '0.2'] + extra, _terms)
 
 
 def test_graph_step_with_the_term(tmp_path, capsys, monkeypatch):
     """Updates 1-2 eager, 3 captured and replayed, 4 replayed: the launch is part of the captured update."""
     monkeypatch.chdir(tmp_path)
-    out = _train(tmp_path, capsys, 'g', 4, ['--graph_step', '--ssim_weight', '0.2'])
-    terms = _terms(out, 4)
-    print(terms)
-    assert len(set(terms['G_ssim'])) > 1
+    kit.check_graph_step(tmp_path, capsys, ['--ssim_weight', '0.2'], _terms, changing=('G_ssim',))

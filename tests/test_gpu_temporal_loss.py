@@ -7,9 +7,7 @@ sequence: the shapes below run from one pixel over odd planes (no 16-byte alignm
 per sequence to a plane whose base is one element off alignment."""
 import ctypes
 import functools
-import gc
 import os
-import re
 import sys
 
 import numpy as np
@@ -18,6 +16,8 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import temporal_loss_ref as ref  # noqa: E402
+import loss_kit as kit  # noqa: E402
+from loss_kit import MCNET, _bits, _generator, _rel, _states, _train  # noqa: E402
 
 from video_frame_inpainting_amd import _native  # noqa: E402
 from video_frame_inpainting_amd.losses import TemporalLoss  # noqa: E402
@@ -92,15 +92,6 @@ def _launch(preds, gt, kind, eps=EPS, grads=True, layouts=None, gt_layout='bt'):
     assert rc == 0, L.tai_sepconv_last_error()
     torch.cuda.synchronize()
     return seqs.cpu().numpy(), totals.cpu().numpy(), [m.cpu().contiguous().numpy() if m is not None else None for m in maps]
-
-
-def _bits(a):
-    return np.ascontiguousarray(a).view(np.int32 if a.dtype == np.float32 else np.int64)
-
-
-def _rel(a, b):
-    a, b = np.asarray(a, np.float64), np.asarray(b, np.float64)
-    return float(np.max(np.where(a == b, 0.0, np.abs(a - b) / np.maximum(np.abs(b), 1e-300))))
 
 
 def _want_totals(want):
@@ -293,72 +284,19 @@ def test_forward_and_backward_replay_inside_one_graph():
     second = [_case(inputs, shape, 2, 5 + i) for i, inputs in enumerate(('uniform', 'grid', 'smooth'))]
     sp = [_store(first[0][0], 'tb')[0].requires_grad_()] + [torch.from_numpy(np.array(c[0])).to(DEV).requires_grad_() for c in first[1:]]
     sg = torch.from_numpy(np.array(first[0][1])).to(DEV)
-    module = TemporalLoss('charbonnier', EPS)
-    side = torch.cuda.Stream()
-    side.wait_stream(torch.cuda.current_stream())
-    with torch.cuda.stream(side):                                                     # warm-up outside the capture
-        sum(module(tuple(sp), sg)).backward()
-    torch.cuda.current_stream().wait_stream(side)
-    for p in sp:
-        p.grad = None
-    torch.cuda.synchronize()
-    gc.collect()
-    graph = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(graph):
-        losses = module(tuple(sp), sg)
-        sum(losses).backward()
-        losses = [x.detach() for x in losses]                                         # nothing with history outlives the capture
     gt2 = second[0][1]
-    with torch.no_grad():
-        for p, c in zip(sp, second):
-            p.copy_(torch.from_numpy(np.array(c[0])))
-        sg.copy_(torch.from_numpy(np.array(gt2)))
-    graph.replay()
-    torch.cuda.synchronize()
-    eager_p = [torch.from_numpy(np.array(c[0])).to(DEV).requires_grad_() for c in second]
-    eager = TemporalLoss('charbonnier', EPS)(tuple(eager_p), torch.from_numpy(np.array(gt2)).to(DEV))
-    sum(eager).backward()
-    for i in range(3):
-        assert float(losses[i]) == float(eager[i].detach())
-        assert torch.equal(sp[i].grad.view(torch.int32), eager_p[i].grad.view(torch.int32))
-        assert np.array_equal(_bits(sp[i].grad.cpu().numpy()), _bits(ref.temporal_loss_ref(second[i][0], gt2, 2, EPS)['grad']))
+    kit.check_graph_replay(lambda: TemporalLoss('charbonnier', EPS), sp, sg, [c[0] for c in second], gt2,
+                           [ref.temporal_loss_ref(c[0], gt2, 2, EPS)['grad'] for c in second])
 
 
 # ---------------------------------------------------------------------------------------------------------------- drivers
 
-SPEC = '{"class": "TAIFillInModel", "args": [4, 1, 3, 51], "kwargs": {"num_block": 5, "kf_dim": 2}}'
-MCNET = '{"class": "MCNetFillInModel", "args": [4, 1, 3], "kwargs": {}}'          # MCNet_gray at reduced width
-K, T, F, SIZE = 3, 2, 3, 32
 TAI_KEYS = ('G_temporal', 'G_temporal_forward', 'G_temporal_backward')
-
-
-def _train(tmp_path, capsys, name, max_iter, extra, model=SPEC):
-    import train
-    capsys.readouterr()
-    train.main(['--name', name, '--K', str(K), '--T', str(T), '--F', str(F), '--c_dim', '1', '--image_size', str(SIZE), '--model_key', model,
-                '--checkpoints_dir', str(tmp_path / 'ckpt'), '--batch_size', '2', '--max_iter', str(max_iter), '--print_freq', '1',
-                '--df_dim', '8', '--synthetic', '4'] + list(extra))
-    return capsys.readouterr().out
-
-
-def _states(out):
-    return dict((int(i), s) for i, s in re.findall(r'^iter (\d+) .* state=([0-9a-f]{16})$', out, re.M))
 
 
 def _terms(out, n, keys=TAI_KEYS):
     """{key: [value per printed update]}; asserts each key is printed on every line, finite and positive."""
-    found = {}
-    for key in keys:
-        values = [float(v) for v in re.findall(r' %s=(\S+)' % key, out)]
-        assert len(values) == n, (key, out)
-        assert all(np.isfinite(v) and v > 0.0 for v in values), (key, values)
-        found[key] = values
-    return found
-
-
-def _generator(tmp_path, name):
-    snap = torch.load(str(tmp_path / 'ckpt' / name / 'model_latest.ckpt'), map_location='cpu', weights_only=False)
-    return snap['generator']
+    return kit._terms(out, n, keys, 0.0, float('inf'))
 
 
 def test_the_keys_come_with_the_weight_and_weight_zero_is_the_run_without_the_flag(tmp_path, capsys, monkeypatch):
@@ -383,26 +321,13 @@ def test_the_keys_come_with_the_weight_and_weight_zero_is_the_run_without_the_fl
                                         '--image_loss', 'charbonnier', '--lap_weight', '0.5']], ids=['resumable', 'guard_fused_ema_all_terms'])
 def test_straight_against_split_with_the_temporal_term(tmp_path, capsys, monkeypatch, extra):
     monkeypatch.chdir(tmp_path)
-    extra = ['--resumable', '--temporal_weight', '0.5'] + extra
-    straight = _train(tmp_path, capsys, 'A', 4, extra)
-    first = _train(tmp_path, capsys, 'B', 2, extra)
-    second = _train(tmp_path, capsys, 'B', 4, extra)
-    assert 'carries no run_state' not in second and 'falling back' not in second
-    sa, sb1, sb2 = _states(straight), _states(first), _states(second)
-    print('straight', sa, 'split', sb1, sb2)
-    assert sorted(sa) == [1, 2, 3, 4] and sorted(sb1) == [1, 2] and sorted(sb2) == [3, 4]
-    assert sa == {**sb1, **sb2} and len(set(sa.values())) == 4
-    print(_terms(straight, 4))
+    kit.check_straight_against_split(tmp_path, capsys, ['--resumable', '--temporal_weight', '0.5'] + extra, _terms)
 
 
 def test_graph_step_with_the_temporal_term(tmp_path, capsys, monkeypatch):
     """Updates 1-2 eager, 3 captured and replayed, 4 replayed: the launch is part of the captured update."""
     monkeypatch.chdir(tmp_path)
-    out = _train(tmp_path, capsys, 'g', 4, ['--graph_step', '--temporal_weight', '0.5', '--temporal_kind', 'l1'])
-    terms = _terms(out, 4)
-    print(terms)
-    assert all(len(set(v)) > 1 for v in terms.values())
-    assert any(v[2] != v[3] for v in terms.values())                                  # the second replay read new inputs and new weights
+    kit.check_graph_step(tmp_path, capsys, ['--temporal_weight', '0.5', '--temporal_kind', 'l1'], _terms, replays_differ=True)
 
 
 def test_mcnet_runs_with_one_prediction(tmp_path, capsys, monkeypatch):

@@ -6,7 +6,9 @@ For a change that may not touch device code (host-side refactors of the launcher
 -save-temps gives any other).  A kernel is its function body ('; -- Begin function' ... '; -- End function') plus its
 '.amdhsa_kernel ... .end_amdhsa_kernel' descriptor.  Function-local labels carry the ordinal at which the compiler emitted the
 function (.LBB<n>_<m>, .Lfunc_end<n>, inline assembly's %=), which moves when the host code names the kernels in another order, so
-labels are compared by their order of definition inside the kernel.  Exit status 0 when both files hold the same kernel symbols with identical text, 1 otherwise."""
+labels are compared by their order of definition inside the kernel.  Comment-only lines (first non-blank character ';': 'implicit-def'
+notes, loop nests, the resource summary that the descriptor repeats) and the comment behind a label (the IR block's name, numbered
+by the compiler's value counter) are dropped before comparing: they move with inlining while the instructions stay put.  Exit status 0 when both files hold the same kernel symbols with identical text, 1 otherwise."""
 import re
 import sys
 
@@ -22,6 +24,8 @@ def kernels(path):
         if name not in bodies:
             sys.exit('%s: kernel descriptor without a function body: %s' % (path, name))
         code = bodies[name] + '\n.amdhsa_kernel\n' + m.group(2)
+        code = re.sub(r'^[ \t]*;.*\n', '', code, flags=re.M)
+        code = re.sub(r'^([A-Za-z_.$][\w.$]*:)[ \t]*;.*$', r'\1', code, flags=re.M)
         # labels are renamed by their order of definition inside the kernel: the compiler's (.LBB<n>_<m>, .Lfunc_end<n>) and inline
         # assembly's (NAME_%=) carry an ordinal that moves when the host code names the kernels in another order
         order = {}

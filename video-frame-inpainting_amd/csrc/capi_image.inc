@@ -1,5 +1,18 @@
 // Image metrics, losses and the clip pipeline (included by sepconv_capi.hip).
 
+// one workgroup per tile or chunk up to the kernel's GRID_CAP; past it a workgroup strides
+static dim3 capped_grid(long long work, long long cap) { return dim3((unsigned)(work < cap ? work : cap)); }
+
+// the pred[] / grad[] tables of imgloss::Args and temploss::Args: the caller's npred entries, null behind them and for every map
+// when the caller passes no table
+template <typename A>
+static void fill_tables(A& a, const float* const* preds, float* const* grads, int npred) {
+    for (int i = 0; i < (int)(sizeof(a.pred) / sizeof(a.pred[0])); ++i) {
+        a.pred[i] = i < npred ? preds[i] : nullptr;
+        a.grad[i] = (grads && i < npred) ? grads[i] : nullptr;
+    }
+}
+
 extern "C" {
 
 long long tai_frame_metrics_workspace_bytes(int N, int C, int H, int W) {
@@ -33,25 +46,17 @@ int tai_frame_metrics(const float* pred, const float* gt, long long* sse, double
 }
 
 long long tai_ssim_loss_workspace_bytes(int N, int C, int H, int W) {
-    if (N <= 0 || C <= 0 || H < 7 || W < 7) return TAI_SEPCONV_EINVAL;
-    if ((long long)N * C * H * W >= (1LL << 40) || (long long)H * W >= (1LL << 31)) return TAI_SEPCONV_EINVAL;
-    const ssimloss::Plan pl = ssimloss::plan(N, C, H, W);
-    if (pl.tiles_total >= (1LL << 31)) return TAI_SEPCONV_EINVAL;
-    return pl.tiles_total * (long long)sizeof(double);
+    if (ssimloss::refusal(N, C, H, W)) return TAI_SEPCONV_EINVAL;
+    return ssimloss::plan(N, C, H, W).tiles_total * (long long)sizeof(double);
 }
 
 int tai_ssim_loss(const float* pred, const float* gt, double* plane_ssim, double* totals, float* grad, void* workspace, int N, int C,
                   int H, int W, void* hip_stream) {
     g_err[0] = 0;
     if (!pred || !gt || !plane_ssim || !totals || !workspace) return fail(TAI_SEPCONV_EINVAL, "%s", "ssim_loss: null pointer");
-    if (N <= 0 || C <= 0 || H < 7 || W < 7)
-        return fail(TAI_SEPCONV_EINVAL, "%s", "ssim_loss: needs N, C >= 1 and H, W >= 7 (the 7x7 SSIM window)");
-    if ((long long)N * C * H * W >= (1LL << 40) || (long long)H * W >= (1LL << 31))
-        return fail(TAI_SEPCONV_EINVAL, "%s", "ssim_loss: tensor too large");
-    if (!aligned(workspace, 8) || !aligned(plane_ssim, 8) || !aligned(totals, 8))
-        return fail(TAI_SEPCONV_EINVAL, "%s", "ssim_loss: workspace, plane_ssim and totals must be 8-byte aligned");
+    if (const char* why = ssimloss::refusal(N, C, H, W, aligned(workspace, 8) && aligned(plane_ssim, 8) && aligned(totals, 8)))
+        return fail(TAI_SEPCONV_EINVAL, "%s", why);
     const ssimloss::Plan pl = ssimloss::plan(N, C, H, W);
-    if (pl.tiles_total >= (1LL << 31)) return fail(TAI_SEPCONV_EINVAL, "%s", "ssim_loss: too many tiles (2^31 or more)");
     const int planes = N * C;       // below 2^31: every plane has at least one tile
     double* part = static_cast<double*>(workspace);
     const double divisor = ((double)N * (double)C) * ((double)(H - 6) * (double)(W - 6));
@@ -85,10 +90,7 @@ int tai_image_loss(const float* const* preds, int npred, const float* gt, int ki
         return fail(TAI_SEPCONV_EINVAL, "%s", "image_loss: workspace, plane_terms and totals must be 8-byte aligned");
     const imgloss::Plan pl = imgloss::plan(planes, H, W);
     imgloss::Args a;
-    for (int i = 0; i < imgloss::MAXP; ++i) {
-        a.pred[i] = i < npred ? preds[i] : nullptr;
-        a.grad[i] = (grads && i < npred) ? grads[i] : nullptr;
-    }
+    fill_tables(a, preds, grads, npred);
     a.gt = gt;
     a.part = static_cast<double*>(workspace);
     a.npred = npred; a.kind = kind; a.H = H; a.W = W; a.nby = pl.nby; a.nbx = pl.nbx;
@@ -98,8 +100,7 @@ int tai_image_loss(const float* const* preds, int npred, const float* gt, int ki
     a.cg = 0.5 / (((double)planes * (double)(H - 1)) * (double)(W - 1));
     const long long rows = npred * planes;
     hipStream_t s = static_cast<hipStream_t>(hip_stream);
-    const unsigned grid = (unsigned)(pl.tiles_total < imgloss::GRID_CAP ? pl.tiles_total : imgloss::GRID_CAP);
-    hipLaunchKernelGGL(imgloss::tile_loss_grad, dim3(grid), dim3(imgloss::THREADS), 0, s, a);
+    hipLaunchKernelGGL(imgloss::tile_loss_grad, capped_grid(pl.tiles_total, imgloss::GRID_CAP), dim3(imgloss::THREADS), 0, s, a);
     if (int rc = check_launch("image_loss tile_loss_grad")) return rc;
     hipLaunchKernelGGL(imgloss::finish_planes, dim3((unsigned)((rows + imgloss::THREADS - 1) / imgloss::THREADS)), dim3(imgloss::THREADS), 0, s,
                        a.part, plane_terms, rows, pl.nby * pl.nbx);
@@ -148,9 +149,8 @@ int tai_temporal_loss(const float* const* preds, int npred, const float* gt, con
     const long long S = (long long)B * C;
     const temploss::Plan pl = temploss::plan(S, H, W);
     temploss::Args a;
+    fill_tables(a, preds, grads, npred);
     for (int i = 0; i < temploss::MAXP; ++i) {
-        a.pred[i] = i < npred ? preds[i] : nullptr;
-        a.grad[i] = (grads && i < npred) ? grads[i] : nullptr;
         a.sb[i] = i < npred ? strides[2 * i] : 0;
         a.st[i] = i < npred ? strides[2 * i + 1] : 0;
     }
@@ -166,8 +166,7 @@ int tai_temporal_loss(const float* const* preds, int npred, const float* gt, con
     a.ct = 0.5 / count;
     const long long rows = npred * S * (T + 1);
     hipStream_t s = static_cast<hipStream_t>(stream);
-    const unsigned grid = (unsigned)(pl.chunks_total < temploss::GRID_CAP ? pl.chunks_total : temploss::GRID_CAP);
-    hipLaunchKernelGGL(temploss::walk_loss_grad, dim3(grid), dim3(temploss::THREADS), 0, s, a);
+    hipLaunchKernelGGL(temploss::walk_loss_grad, capped_grid(pl.chunks_total, temploss::GRID_CAP), dim3(temploss::THREADS), 0, s, a);
     if (int rc = check_launch("temporal_loss walk_loss_grad")) return rc;
     hipLaunchKernelGGL(temploss::finish_sequences, dim3((unsigned)((rows + temploss::THREADS - 1) / temploss::THREADS)), dim3(temploss::THREADS),
                        0, s, a.part, seq_terms, rows, S, T + 1, pl.cps);

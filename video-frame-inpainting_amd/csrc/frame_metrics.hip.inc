@@ -17,6 +17,8 @@
 // every pixel is counted once.  The tile's three partials go to the workspace; `finish` sums them per frame in a fixed order.  No
 // atomics, no dependence on the batch: a frame's bits depend only on its own pixels and on (C, H, W).
 
+#include "loss_common.hip.inc"
+
 namespace fmetrics {
 
 constexpr int BH = 16, TW = 64;            // SSIM outputs per tile: rows x columns
@@ -33,12 +35,7 @@ __device__ __forceinline__ int to_u8(float x, float& unit) {
     return (int)(unit * 255.f);
 }
 
-template <typename V>
-__device__ __forceinline__ V wave_sum(V x) {
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) x += __shfl_xor(x, m, 64);
-    return x;
-}
+using losscommon::wave_sum;
 
 __global__ __launch_bounds__(THREADS)
 void tile_partials(const float* __restrict__ pred, const float* __restrict__ gt, double* __restrict__ part_ssim,

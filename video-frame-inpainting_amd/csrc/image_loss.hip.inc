@@ -19,6 +19,8 @@
 // (r, c) it is written for above, so every term is summed once.  LDS: 4 x 18 x 72 x 4 + 192 = 20,928 bytes.  The grid is capped at
 // GRID_CAP workgroups; past it a workgroup strides over the tiles.
 
+#include "loss_common.hip.inc"
+
 namespace imgloss {
 
 constexpr int TH = 16, TW = 64;            // pixels per tile
@@ -39,21 +41,7 @@ struct Args {
     double cp, cg;
 };
 
-__device__ __forceinline__ float range_map(float v) {
-#pragma clang fp contract(off)
-    return (v + 1.f) / 2.f;
-}
-
-// sgn(0) = 0, NaN kept
-__device__ __forceinline__ float sgn(float v) {
-    return v != v ? v : (float)((v > 0.f) - (v < 0.f));
-}
-
-__device__ __forceinline__ double wave_sum(double x) {
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) x += __shfl_xor(x, m, 64);
-    return x;
-}
+using namespace losscommon;
 
 // the lane's four pixels of one array: registers and LDS; zero outside the plane (no term that exists reads those)
 __device__ __forceinline__ void stage_row(const float* __restrict__ plane, float* __restrict__ s, int r, int c, int H, int W, int ty, int tx,
@@ -142,18 +130,7 @@ void tile_loss_grad(const Args a) {
                 const float xc = xx[j + 1], yc = yy[j + 1];
                 const float d = xc - yc;
                 float rho, drho;
-                if (a.kind == 0) {
-                    rho = d * d;
-                    drho = 2.f * d;
-                } else if (a.kind == 1) {
-                    rho = __builtin_fabsf(d);
-                    drho = sgn(d);
-                } else {
-                    const float dd = d * d;
-                    const float s = __builtin_sqrtf(dd + a.e2);
-                    rho = s;
-                    drho = d / s;
-                }
+                rho_drho(a.kind, d, a.e2, rho, drho);
                 point = point + (double)rho;
                 const bool left = cc >= 1, right = cc <= W - 2;
                 const float gw = (xc - xx[j + 2]) - (yc - yy[j + 2]);          // gw(r, c)

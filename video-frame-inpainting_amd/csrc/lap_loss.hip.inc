@@ -20,6 +20,8 @@
 // the fly per output pixel (25 and up to 9 reads), their adjoints as gathers over the 25 and 9 candidate pixels with the operators'
 // weights, which takes care of every clamped edge, 1 x 1 levels included.
 
+#include "loss_common.hip.inc"
+
 namespace laploss {
 
 constexpr int THREADS = 1024;
@@ -45,11 +47,7 @@ struct Args {
 
 __device__ __forceinline__ int clampi(int v, int hi) { return v < 0 ? 0 : (v > hi ? hi : v); }
 
-__device__ __forceinline__ double wave_sum(double x) {
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) x += __shfl_xor(x, m, 64);
-    return x;
-}
+using losscommon::wave_sum;
 
 // every lane gets the workgroup's sum: the waves in order
 __device__ __forceinline__ double block_sum(double v, double* red) {

@@ -11,15 +11,13 @@
 // The normalisation of a vector is applied by its consumer (the products are linear in it), so no kernel waits on a
 // grid-wide norm.  All sums have a fixed order: the results are reproducible from call to call.
 
+#include "loss_common.hip.inc"
+
 namespace snorm {
 
 constexpr float EPS = 1e-12f;      // _l2normalize's eps (SNDiscriminator.py:27-28)
 
-__device__ __forceinline__ float wave_sum(float x) {
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) x += __shfl_xor(x, m, 64);
-    return x;
-}
+using losscommon::wave_sum;
 
 // Sum over the whole workgroup (blockDim.x * blockDim.y threads, a multiple of 64, at most 1024); every thread gets it.
 __device__ __forceinline__ float block_sum(float x, float* red) {

@@ -19,6 +19,8 @@
 // sums, reused for the maps' vertical sums) + 3 x 22 x 22 x 8 (maps) + 32 = 42,560 bytes: three workgroups (12 waves) per CU of 160 KiB.
 // With grad == nullptr only the owned windows are evaluated and the second pass is skipped.
 
+#include "loss_common.hip.inc"
+
 namespace ssimloss {
 
 constexpr int TH = 16, TW = 16;            // pixels (and owned window corners) per tile
@@ -28,11 +30,7 @@ constexpr int THREADS = 256;
 
 constexpr double C1 = 0.01 * 0.01, C2 = 0.03 * 0.03, COV_NORM = 49.0 / 48.0, TWO_COV_NORM = 2.0 * (49.0 / 48.0);
 
-__device__ __forceinline__ double wave_sum(double x) {
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) x += __shfl_xor(x, m, 64);
-    return x;
-}
+using losscommon::wave_sum;
 
 __global__ __launch_bounds__(THREADS)
 void tile_loss_grad(const float* __restrict__ pred, const float* __restrict__ gt, double* __restrict__ part, float* __restrict__ grad,
@@ -178,6 +176,16 @@ inline Plan plan(int N, int C, int H, int W) {
     p.nbx = (W + TW - 1) / TW;
     p.tiles_total = (long long)N * C * p.nby * p.nbx;
     return p;
+}
+
+// what tai_ssim_loss and its workspace query refuse for the dimensions; null: they are taken.  (The launcher's alignment message sits
+// between the size checks and the tile count, where it always has; the query has no pointers and passes nothing.)
+inline const char* refusal(int N, int C, int H, int W, bool pointers_aligned = true) {
+    if (N <= 0 || C <= 0 || H < 7 || W < 7) return "ssim_loss: needs N, C >= 1 and H, W >= 7 (the 7x7 SSIM window)";
+    if ((long long)N * C * H * W >= (1LL << 40) || (long long)H * W >= (1LL << 31)) return "ssim_loss: tensor too large";
+    if (!pointers_aligned) return "ssim_loss: workspace, plane_ssim and totals must be 8-byte aligned";
+    if (plan(N, C, H, W).tiles_total >= (1LL << 31)) return "ssim_loss: too many tiles (2^31 or more)";
+    return nullptr;
 }
 
 }  // namespace ssimloss

@@ -17,6 +17,8 @@
 // and no barrier: each wave's sum of position j goes to the workspace, [npred][chunks][T + 1][4].  The grid is capped at GRID_CAP
 // workgroups; past it a workgroup strides over the chunks.
 
+#include "loss_common.hip.inc"
+
 namespace temploss {
 
 constexpr int THREADS = 256;               // runs per chunk
@@ -38,21 +40,7 @@ struct Args {
     double ct;                             // 0.5 / count
 };
 
-__device__ __forceinline__ float range_map(float v) {
-#pragma clang fp contract(off)
-    return (v + 1.f) / 2.f;
-}
-
-// sgn(0) = 0, NaN kept
-__device__ __forceinline__ float sgn(float v) {
-    return v != v ? v : (float)((v > 0.f) - (v < 0.f));
-}
-
-__device__ __forceinline__ double wave_sum(double x) {
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) x += __shfl_xor(x, m, 64);
-    return x;
-}
+using namespace losscommon;
 
 // the first nv (0..4) words of the run at q; the others read as zero
 __device__ __forceinline__ void load_run(const float* q, int nv, float (&v)[4]) {
@@ -141,18 +129,7 @@ void walk_loss_grad(const Args a) {
                     const float e = t < T ? range_map(xc[i][j]) - y[j] : 0.f;     // e_T = +0: the known frame after the gap
                     const float d = e - e_prev[i][j];                             // d_t; e_{-1} = +0
                     float rho, drho;
-                    if (a.kind == 0) {
-                        rho = d * d;
-                        drho = 2.f * d;
-                    } else if (a.kind == 1) {
-                        rho = __builtin_fabsf(d);
-                        drho = sgn(d);
-                    } else {
-                        const float dd = d * d;
-                        const float sq = __builtin_sqrtf(dd + a.e2);
-                        rho = sq;
-                        drho = d / sq;
-                    }
+                    rho_drho(a.kind, d, a.e2, rho, drho);
                     if (j < nv) sum = sum + (double)rho;
                     g[j] = (float)(((double)dr_prev[i][j] - (double)drho) * a.ct);          // frame t - 1's
                     e_prev[i][j] = e;

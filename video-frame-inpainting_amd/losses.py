@@ -1,6 +1,8 @@
 """Image gradient difference loss (reference src/losses/losses.py:4-44, Mathieu et al.), and this build's opt-in losses: SSIMLoss
 (train.py --ssim_weight), ImageLoss (train.py --image_loss l1 / charbonnier), LapLoss (train.py --lap_weight) and TemporalLoss
 (train.py --temporal_weight), each a written definition with a HIP kernel behind it."""
+import collections
+
 import torch
 import torch.nn as nn
 
@@ -40,33 +42,77 @@ def _ssim_planes(pred, gt):
     return ((2 * ux * uy + C1) * (2 * vxy + C2)) / ((ux * ux + uy * uy + C1) * (vx + vy + C2))
 
 
-class _SSIMLossFunction(torch.autograd.Function):
-    """``tai_ssim_loss`` on the current stream: (loss fp32 scalar, plane_ssim float64 [planes]); the gradient map comes from the same
-    launch and is what ``backward`` scales.  Every allocation is torch's, so under capture it comes from the graph's pool."""
+# What one fused loss hands to _FusedLoss: the entry's name; the arguments of its ``*_workspace_bytes`` query and (format, values) of the
+# ValueError when that refuses them; how many float64 detail values and totals the launch writes; ``args(pred, gt, detail, totals, map,
+# workspace, strides)`` -> the launch's argument list; ``views(detail, totals)`` -> what the call returns, the loss(es) first; ``table``:
+# 1-3 predictions passed as pointer tables (else one, passed itself); ``strided``: tensors are read where they lie (_block_strides).
+_Call = collections.namedtuple('_Call', 'entry query refused detail totals args views table strided', defaults=(False, False))
+
+
+class _FusedLoss(torch.autograd.Function):
+    """One launch of a fused loss+gradient entry on the current stream behind autograd.  ``call`` (a _Call) says what differs between the
+    losses; the rest is here: one float64 tensor for detail and totals, the float64 workspace, and an fp32 gradient map in its prediction's
+    layout for every prediction that needs a gradient when ``want_maps`` (inside Function.forward grad mode is always off and
+    needs_input_grad ignores no_grad, so the caller passes its mode in).  The maps come from the same launch and are what ``backward``
+    scales.  Every allocation is torch's, so under capture it comes from the graph's pool; nothing waits for the device."""
 
     @staticmethod
-    def forward(ctx, pred, gt):
+    def forward(ctx, call, want_maps, gt, *preds):
+        import ctypes
         from . import _native
-        C, H, W = pred.shape[-3:]
-        N = pred.numel() // (C * H * W)
-        L = _native.lib()
-        nbytes = L.tai_ssim_loss_workspace_bytes(N, C, H, W)
+        n = len(preds)
+        nbytes = getattr(_native.lib(), call.entry + '_workspace_bytes')(*call.query)
         if nbytes < 0:
-            raise ValueError('SSIMLoss: [%d, %d, %d, %d] is outside what tai_ssim_loss takes' % (N, C, H, W))
-        dev = pred.device
-        p, g = pred.detach().contiguous(), gt.detach().contiguous()
+            raise ValueError(call.refused[0] % call.refused[1])
+        dev = gt.device
+        tensors, strides = [], []
+        for t in preds + (gt,):
+            t = t.detach()
+            where = _block_strides(t) if call.strided else None
+            if where is None:
+                t = t.contiguous()
+                where = _block_strides(t) if call.strided else ()
+            tensors.append(t)
+            strides.extend(where)
         workspace = torch.empty(nbytes // 8, dtype=torch.float64, device=dev)
-        out = torch.empty(N * C + 2, dtype=torch.float64, device=dev)          # plane_ssim, then mean_ssim and loss
-        grad = torch.empty(pred.shape, dtype=torch.float32, device=dev) if ctx.needs_input_grad[0] else None
-        _native.launch('tai_ssim_loss', dev, p, g, out, out[N * C:], grad, workspace, N, C, H, W)
-        ctx.map = grad
-        plane_ssim = out[:N * C]
-        ctx.mark_non_differentiable(plane_ssim)
-        return out[N * C + 1].to(torch.float32), plane_ssim
+        out = torch.empty(call.detail + call.totals, dtype=torch.float64, device=dev)          # detail, then totals
+        maps = [torch.empty_strided(p.shape, p.stride(), dtype=torch.float32, device=dev) if want_maps and ctx.needs_input_grad[3 + i] else None
+                for i, p in enumerate(tensors[:n])]
+        pred_arg, map_arg = tensors[0], maps[0]
+        if call.table:
+            pred_arg = (ctypes.c_void_p * n)(*[p.data_ptr() for p in tensors[:n]])
+            map_arg = (ctypes.c_void_p * n)(*[m.data_ptr() if m is not None else None for m in maps])
+        detail, totals = out[:call.detail], out[call.detail:]
+        stride_table = (ctypes.c_longlong * len(strides))(*strides) if call.strided else None
+        _native.launch(call.entry, dev, *call.args(pred_arg, tensors[n], detail, totals, map_arg, workspace, stride_table))
+        ctx.maps = maps
+        results = call.views(detail, totals)
+        ctx.mark_non_differentiable(*results[1:])
+        return results
 
     @staticmethod
-    def backward(ctx, grad_loss, _grad_planes):
-        return (grad_loss * ctx.map if ctx.map is not None else None), None
+    def backward(ctx, grad_losses, *_):
+        one = grad_losses.dim() == 0
+        return (None, None, None) + tuple(None if m is None else (grad_losses if one else grad_losses[i]) * m for i, m in enumerate(ctx.maps))
+
+
+def _kind_and_eps(name, kind, eps):
+    """(kind, eps) of ImageLoss and TemporalLoss, checked."""
+    if kind not in IMAGE_LOSS_KINDS:
+        raise ValueError('%s: kind must be one of %s, found %r' % (name, ', '.join(IMAGE_LOSS_KINDS), kind))
+    eps = float(eps)
+    if not (eps > 0.0 and eps != float('inf')):
+        raise ValueError('%s: eps must be finite and > 0, found %r' % (name, eps))
+    return kind, eps
+
+
+def _predictions(name, preds):
+    """(single, tuple of 1-3 predictions) of what ImageLoss and TemporalLoss take: one tensor or a tuple."""
+    single = torch.is_tensor(preds)
+    preds = (preds,) if single else tuple(preds)
+    if not 1 <= len(preds) <= 3:
+        raise ValueError('%s: takes 1 to 3 predictions, got %d' % (name, len(preds)))
+    return single, preds
 
 
 class SSIMLoss(nn.Module):
@@ -88,7 +134,12 @@ class SSIMLoss(nn.Module):
         if H < 7 or W < 7 or input.numel() == 0:
             raise ValueError('SSIMLoss: needs at least one plane and H, W >= 7 (the 7x7 window), got %s' % (tuple(input.shape),))
         if input.is_cuda and input.dtype == torch.float32 and target.is_cuda and target.dtype == torch.float32:
-            loss, planes = _SSIMLossFunction.apply(input, target)
+            C = input.shape[-3]
+            N = input.numel() // (C * H * W)
+            call = _Call('tai_ssim_loss', (N, C, H, W), ('SSIMLoss: [%d, %d, %d, %d] is outside what tai_ssim_loss takes', (N, C, H, W)), N * C, 2,
+                         lambda p, g, planes, totals, m, ws, _: (p, g, planes, totals, m, ws, N, C, H, W),
+                         lambda planes, totals: (totals[1].to(torch.float32), planes))                     # totals: mean_ssim and loss
+            loss, planes = _FusedLoss.apply(call, True, target, input)                 # (a map whenever the input requires grad, whatever the mode)
             self.plane_ssim = planes.detach()
             return loss
         S = _ssim_planes(input, target.to(device=input.device, dtype=input.dtype))
@@ -124,45 +175,6 @@ def _image_loss_terms(pred, gt, kind, eps):
     return point, gdl, torch.stack([plane_point, plane_gdl], dim=1)
 
 
-class _ImageLossFunction(torch.autograd.Function):
-    """``tai_image_loss`` on the current stream for 1-3 predictions: (losses fp32 [n], terms fp32 [n, 2] (point, gdl), plane_terms float64
-    [n, P, 2]); the gradient maps come from the same launch and are what ``backward`` scales; a prediction that needs no gradient, or
-    ``want_maps`` false (the caller runs under no_grad), gets no map.  Every allocation is torch's, so under
-    capture it comes from the graph's pool."""
-
-    @staticmethod
-    def forward(ctx, gt, kind, eps, want_maps, *preds):
-        import ctypes
-        from . import _native
-        H, W = gt.shape[-2:]
-        planes = gt.numel() // (H * W)
-        n = len(preds)
-        L = _native.lib()
-        nbytes = L.tai_image_loss_workspace_bytes(n, planes, H, W)
-        if nbytes < 0:
-            raise ValueError('ImageLoss: %d predictions of %d planes of %d x %d are outside what tai_image_loss takes' % (n, planes, H, W))
-        dev = gt.device
-        g = gt.detach().contiguous()
-        ps = [p.detach().contiguous() for p in preds]
-        workspace = torch.empty(nbytes // 8, dtype=torch.float64, device=dev)
-        out = torch.empty(n * planes * 2 + n * 3, dtype=torch.float64, device=dev)         # plane_terms, then totals
-        maps = [torch.empty(p.shape, dtype=torch.float32, device=dev) if want_maps and ctx.needs_input_grad[4 + i] else None
-                for i, p in enumerate(preds)]
-        pred_ptrs = (ctypes.c_void_p * n)(*[p.data_ptr() for p in ps])
-        map_ptrs = (ctypes.c_void_p * n)(*[m.data_ptr() if m is not None else None for m in maps])
-        totals = out[n * planes * 2:]
-        _native.launch('tai_image_loss', dev, pred_ptrs, n, g, kind, eps, out, totals, map_ptrs, workspace, planes, H, W)
-        ctx.maps = maps
-        t32 = totals.view(n, 3).to(torch.float32)
-        losses, terms, plane_terms = t32[:, 2].contiguous(), t32[:, :2], out[:n * planes * 2].view(n, planes, 2)
-        ctx.mark_non_differentiable(terms, plane_terms)
-        return losses, terms, plane_terms
-
-    @staticmethod
-    def backward(ctx, grad_losses, _grad_terms, _grad_planes):
-        return (None, None, None, None) + tuple(grad_losses[i] * m if m is not None else None for i, m in enumerate(ctx.maps))
-
-
 class ImageLoss(nn.Module):
     """Pointwise term + gradient-difference term of 1-3 predictions against one target, the definition of ``tai_image_loss``
     (include/tai_sepconv.h): frames mapped to [0, 1] as ``inverse_transform`` does and NOT clipped; the point term is the mean of d^2
@@ -175,20 +187,12 @@ class ImageLoss(nn.Module):
 
     def __init__(self, kind='charbonnier', eps=1e-3):
         super().__init__()
-        if kind not in IMAGE_LOSS_KINDS:
-            raise ValueError('ImageLoss: kind must be one of %s, found %r' % (', '.join(IMAGE_LOSS_KINDS), kind))
-        eps = float(eps)
-        if not (eps > 0.0 and eps != float('inf')):
-            raise ValueError('ImageLoss: eps must be finite and > 0, found %r' % (eps,))
-        self.kind, self.eps = kind, eps
+        self.kind, self.eps = _kind_and_eps('ImageLoss', kind, eps)
         self.last_terms = None
         self.plane_terms = None
 
     def forward(self, preds, target):
-        single = torch.is_tensor(preds)
-        preds = (preds,) if single else tuple(preds)
-        if not 1 <= len(preds) <= 3:
-            raise ValueError('ImageLoss: takes 1 to 3 predictions, got %d' % len(preds))
+        single, preds = _predictions('ImageLoss', preds)
         for p in preds:
             if p.shape != target.shape or p.dim() < 2:
                 raise ValueError('ImageLoss: prediction %s and target %s must have one shape [..., H, W]' % (tuple(p.shape), tuple(target.shape)))
@@ -197,8 +201,15 @@ class ImageLoss(nn.Module):
             raise ValueError('ImageLoss: needs at least one plane and H, W >= 2 (the gradient-difference term), got %s' % (tuple(target.shape),))
         kind = IMAGE_LOSS_KINDS.index(self.kind)
         if all(t.is_cuda and t.dtype == torch.float32 for t in preds + (target,)):
-            # (inside Function.forward grad mode is always off and needs_input_grad ignores no_grad: the caller's mode is passed in)
-            losses, terms, planes = _ImageLossFunction.apply(target, kind, self.eps, torch.is_grad_enabled(), *preds)
+            n, P, eps = len(preds), target.numel() // (H * W), self.eps
+
+            def views(planes, totals):                                                  # totals: (point, gdl, loss) per prediction
+                t32 = totals.view(n, 3).to(torch.float32)
+                return t32[:, 2].contiguous(), t32[:, :2], planes.view(n, P, 2)
+            call = _Call('tai_image_loss', (n, P, H, W),
+                         ('ImageLoss: %d predictions of %d planes of %d x %d are outside what tai_image_loss takes', (n, P, H, W)), n * P * 2, n * 3,
+                         lambda ps, g, planes, totals, ms, ws, _: (ps, n, g, kind, eps, planes, totals, ms, ws, P, H, W), views, table=True)
+            losses, terms, planes = _FusedLoss.apply(call, torch.is_grad_enabled(), target, *preds)
             self.last_terms = [(terms[i, 0], terms[i, 1]) for i in range(len(preds))]
             self.plane_terms = planes
             out = tuple(losses[i] for i in range(len(preds)))
@@ -298,38 +309,6 @@ def _lap_terms(pred, gt, levels):
     return loss, terms, plane_terms
 
 
-class _LapLossFunction(torch.autograd.Function):
-    """``tai_lap_loss`` on the current stream: (loss fp32 scalar, terms fp32 [L], plane_terms float64 [P, L]); the gradient map comes
-    from the same launch and is what ``backward`` scales; ``want_map`` false (the caller runs under no_grad) or a prediction that needs
-    no gradient gets no map.  Every allocation is torch's, so under capture it comes from the graph's pool."""
-
-    @staticmethod
-    def forward(ctx, pred, gt, levels, want_map):
-        from . import _native
-        H, W = pred.shape[-2:]
-        planes = pred.numel() // (H * W)
-        L = _native.lib()
-        nbytes = L.tai_lap_loss_workspace_bytes(planes, H, W, levels)
-        if nbytes < 0:
-            raise ValueError('LapLoss: %d planes of %d x %d with %d levels are outside what tai_lap_loss takes' % (planes, H, W, levels))
-        dev = pred.device
-        p, g = pred.detach().contiguous(), gt.detach().contiguous()
-        workspace = torch.empty(nbytes // 8, dtype=torch.float64, device=dev)
-        out = torch.empty(planes * levels + levels + 1, dtype=torch.float64, device=dev)        # plane_terms, then totals
-        grad = torch.empty(pred.shape, dtype=torch.float32, device=dev) if want_map and ctx.needs_input_grad[0] else None
-        totals = out[planes * levels:]
-        _native.launch('tai_lap_loss', dev, p, g, levels, out, totals, grad, workspace, planes, H, W)
-        ctx.map = grad
-        t32 = totals.to(torch.float32)
-        loss, terms, plane_terms = t32[levels].clone(), t32[:levels], out[:planes * levels].view(planes, levels)
-        ctx.mark_non_differentiable(terms, plane_terms)
-        return loss, terms, plane_terms
-
-    @staticmethod
-    def backward(ctx, grad_loss, _grad_terms, _grad_planes):
-        return (grad_loss * ctx.map if ctx.map is not None else None), None, None, None
-
-
 class LapLoss(nn.Module):
     """L1 distance between the Laplacian pyramids of prediction and target, the definition of ``tai_lap_loss`` (include/tai_sepconv.h):
     frames mapped to [0, 1] as ``inverse_transform`` does and NOT clipped, ``levels`` levels (1..6) of the 5-tap binomial pyramid with
@@ -352,8 +331,16 @@ class LapLoss(nn.Module):
             raise ValueError('LapLoss: input %s and target %s must have one shape [..., H, W]' % (tuple(input.shape), tuple(target.shape)))
         _lap_check(input.shape, self.levels)
         if input.is_cuda and input.dtype == torch.float32 and target.is_cuda and target.dtype == torch.float32:
-            # (inside Function.forward grad mode is always off and needs_input_grad ignores no_grad: the caller's mode is passed in)
-            loss, terms, planes = _LapLossFunction.apply(input, target, self.levels, torch.is_grad_enabled())
+            (H, W), levels = input.shape[-2:], self.levels
+            P = input.numel() // (H * W)
+
+            def views(planes, totals):                                                  # totals: the terms, then the loss
+                t32 = totals.to(torch.float32)
+                return t32[levels].clone(), t32[:levels], planes.view(P, levels)
+            call = _Call('tai_lap_loss', (P, H, W, levels),
+                         ('LapLoss: %d planes of %d x %d with %d levels are outside what tai_lap_loss takes', (P, H, W, levels)), P * levels, levels + 1,
+                         lambda p, g, planes, totals, m, ws, _: (p, g, levels, planes, totals, m, ws, P, H, W), views)
+            loss, terms, planes = _FusedLoss.apply(call, torch.is_grad_enabled(), target, input)
             self.last_terms, self.plane_terms = terms.detach(), planes.detach()
             return loss
         loss, terms, planes = _lap_terms(input, target.to(device=input.device, dtype=input.dtype), self.levels)
@@ -404,53 +391,6 @@ def _block_strides(t):
     return None
 
 
-class _TemporalLossFunction(torch.autograd.Function):
-    """``tai_temporal_loss`` on the current stream for 1-3 predictions: (losses fp32 [n], terms fp32 [n, T + 1], seq_terms float64
-    [n, B * C, T + 1]).  Every tensor is passed where it lies with its own batch and time stride when its [C, H, W] blocks are dense
-    (``gen_output['pred']`` is a transposed view of a time-major buffer) and made contiguous otherwise; the gradient maps come from the
-    same launch, each in its prediction's layout, and are what ``backward`` scales; a prediction that needs no gradient, or ``want_maps``
-    false (the caller runs under no_grad), gets no map.  Every allocation is torch's, so under capture it comes from the graph's pool."""
-
-    @staticmethod
-    def forward(ctx, gt, kind, eps, want_maps, *preds):
-        import ctypes
-        from . import _native
-        B, T, C, H, W = gt.shape
-        n = len(preds)
-        L = _native.lib()
-        nbytes = L.tai_temporal_loss_workspace_bytes(n, B, T, C, H, W)
-        if nbytes < 0:
-            raise ValueError('TemporalLoss: %d predictions of %s are outside what tai_temporal_loss takes' % (n, tuple(gt.shape)))
-        dev = gt.device
-        tensors, strides = [], []
-        for t in preds + (gt,):
-            t = t.detach()
-            if _block_strides(t) is None:
-                t = t.contiguous()
-            tensors.append(t)
-            strides.extend(_block_strides(t))
-        S = B * C
-        workspace = torch.empty(nbytes // 8, dtype=torch.float64, device=dev)
-        out = torch.empty(n * S * (T + 1) + n * (T + 2), dtype=torch.float64, device=dev)          # seq_terms, then totals
-        maps = [torch.empty_strided(p.shape, p.stride(), dtype=torch.float32, device=dev) if want_maps and ctx.needs_input_grad[4 + i] else None
-                for i, p in enumerate(tensors[:n])]
-        pred_ptrs = (ctypes.c_void_p * n)(*[p.data_ptr() for p in tensors[:n]])
-        map_ptrs = (ctypes.c_void_p * n)(*[m.data_ptr() if m is not None else None for m in maps])
-        stride_table = (ctypes.c_longlong * (2 * n + 2))(*strides)
-        totals = out[n * S * (T + 1):]
-        _native.launch('tai_temporal_loss', dev, pred_ptrs, n, tensors[n], stride_table, kind, eps, out, totals, map_ptrs, workspace,
-                       B, T, C, H, W)
-        ctx.maps = maps
-        t32 = totals.view(n, T + 2).to(torch.float32)
-        losses, terms, seq_terms = t32[:, T + 1].contiguous(), t32[:, :T + 1], out[:n * S * (T + 1)].view(n, S, T + 1)
-        ctx.mark_non_differentiable(terms, seq_terms)
-        return losses, terms, seq_terms
-
-    @staticmethod
-    def backward(ctx, grad_losses, _grad_terms, _grad_seqs):
-        return (None, None, None, None) + tuple(grad_losses[i] * m if m is not None else None for i, m in enumerate(ctx.maps))
-
-
 class TemporalLoss(nn.Module):
     """Temporal-difference loss of 1-3 predictions ``[B, T, C, H, W]`` against one target, the definition of ``tai_temporal_loss``
     (include/tai_sepconv.h): frames mapped to [0, 1] as ``inverse_transform`` does and NOT clipped, e_t the error of frame t and zero on
@@ -464,20 +404,12 @@ class TemporalLoss(nn.Module):
 
     def __init__(self, kind='charbonnier', eps=1e-3):
         super().__init__()
-        if kind not in IMAGE_LOSS_KINDS:
-            raise ValueError('TemporalLoss: kind must be one of %s, found %r' % (', '.join(IMAGE_LOSS_KINDS), kind))
-        eps = float(eps)
-        if not (eps > 0.0 and eps != float('inf')):
-            raise ValueError('TemporalLoss: eps must be finite and > 0, found %r' % (eps,))
-        self.kind, self.eps = kind, eps
+        self.kind, self.eps = _kind_and_eps('TemporalLoss', kind, eps)
         self.last_terms = None
         self.seq_terms = None
 
     def forward(self, preds, target):
-        single = torch.is_tensor(preds)
-        preds = (preds,) if single else tuple(preds)
-        if not 1 <= len(preds) <= 3:
-            raise ValueError('TemporalLoss: takes 1 to 3 predictions, got %d' % len(preds))
+        single, preds = _predictions('TemporalLoss', preds)
         for p in preds:
             if p.shape != target.shape or p.dim() != 5:
                 raise ValueError('TemporalLoss: prediction %s and target %s must have one shape [B, T, C, H, W]'
@@ -486,8 +418,18 @@ class TemporalLoss(nn.Module):
             raise ValueError('TemporalLoss: needs at least one pixel, got %s' % (tuple(target.shape),))
         kind = IMAGE_LOSS_KINDS.index(self.kind)
         if all(t.is_cuda and t.dtype == torch.float32 for t in preds + (target,)):
-            # (inside Function.forward grad mode is always off and needs_input_grad ignores no_grad: the caller's mode is passed in)
-            losses, terms, seqs = _TemporalLossFunction.apply(target, kind, self.eps, torch.is_grad_enabled(), *preds)
+            n, eps, (B, T, C, H, W) = len(preds), self.eps, target.shape
+            S = B * C
+
+            def views(seqs, totals):                                                    # totals: the T + 1 position means, then the loss
+                t32 = totals.view(n, T + 2).to(torch.float32)
+                return t32[:, T + 1].contiguous(), t32[:, :T + 1], seqs.view(n, S, T + 1)
+            call = _Call('tai_temporal_loss', (n, B, T, C, H, W),
+                         ('TemporalLoss: %d predictions of %s are outside what tai_temporal_loss takes', (n, tuple(target.shape))),
+                         n * S * (T + 1), n * (T + 2),
+                         lambda ps, g, seqs, totals, ms, ws, strides: (ps, n, g, strides, kind, eps, seqs, totals, ms, ws, B, T, C, H, W),
+                         views, table=True, strided=True)
+            losses, terms, seqs = _FusedLoss.apply(call, torch.is_grad_enabled(), target, *preds)
             self.last_terms, self.seq_terms = terms.detach(), seqs.detach()
             out = tuple(losses[i] for i in range(len(preds)))
         else:
