@@ -179,6 +179,14 @@ int tai_conv3x3_wino_wrw_set_paired(int on);
  * (csrc/wino43_conv.hip.inc, conv3x3_wrw_gen); other shapes keep the F(2x2, 3x3) kernel.  Same interface, same workspace (the size query
  * covers both), reproducible either way.  Returns the previous value, -1 for anything else. */
 int tai_conv3x3_wino_wrw_set_tile(int tile);
+/* The route of tai_conv3x3_wino_wrw (in_h <= 0: no window) / tai_conv3x3_wino_wrw_window (in_h > 0) for these dimensions, as a query: the launcher
+ * calls the same function, so the answer is the launch's own decision and the refusals are the launcher's, with its words.  No stream, no
+ * launch.  Returns the grid (kblocks * cblocks * splits workgroups) or TAI_SEPCONV_EINVAL, and fills
+ * out[0..7] = tile (4: the F(4x4, 3x3)-domain kernel, 2: F(2x2, 3x3); follows tai_conv3x3_wino_wrw_set_tile), paired (tile 2: chunk pairs
+ * over 16 tiles; follows tai_conv3x3_wino_wrw_set_paired), ragged (tile 2: the zero-extended planes, odd H or W % 16 != 0), kblocks (blocks
+ * of 64 output channels), cblocks (blocks of 64 input channels; 32 at tile 4), nchunks (chunks of 8 tiles; at tile 4 of four 4 x 4 tiles),
+ * chunks_per_split (the last split may hold fewer), splits. */
+int tai_conv3x3_wino_wrw_plan(int N, int C, int K, int H, int W, int in_h, int in_w, int in_oy, int in_ox, int* out);
 
 /* Spectral normalisation of one discriminator layer, as the reference's SNConv2d / SNLinear do on every forward
  * (src/discriminators/SNDiscriminator.py:10-25 max_singular_value, :60-68 and :84-92 W.data <- W.data / sigma):
@@ -240,6 +248,17 @@ int tai_conv3x3_wino_forward_parts(const float* const* xs, int nparts, const flo
 int tai_conv3x3_wino_forward_ex(const float* const* xs, int nparts, int shift_k, const float* U, const float* bias, float* y,
                                 float* ypool, int pool_h, int pool_w, int pool_oy, int pool_ox, const float* addx, float* y2, int N,
                                 int C, int K, int H, int W, int in_h, int in_w, int in_oy, int in_ox, int act, void* hip_stream);
+/* The plan of a tai_conv3x3_wino_forward_ex launch with these arguments, as a query (has_pool, has_addx, has_y2: whether ypool, addx, y2
+ * are given; the pooled output is the plain [N, K, H/2, W/2] tensor; in_h = 0: the plane is H x W at (0, 0)): the launcher calls the same
+ * function, so the answer is the launch's own decision and the refusals are the launcher's, with its words.  U: the transformed-weight
+ * buffer the launch would read -- a buffer written in split-bf16 arithmetic takes the split kernel where that kernel has the shape -- or
+ * NULL for fp32 arithmetic.  No stream, no launch.  Returns the grid or TAI_SEPCONV_EINVAL, and fills
+ * out[0..8] = split (1: the split-bf16 kernel, 0: fp32), tall (the 128-channel x 32-tile workgroups; follows tai_conv3x3_wino_set_tall),
+ * parts (0 one tensor, 1 cat operands, 2 displaced reads), epilogue (0 none, 1 y2, 2 the sum into y, 3 odd H or W), edge (the split
+ * kernel's edge handling), kblocks (blocks of 64 output channels, 128 tall), tblocks (blocks of 64 tiles, 32 tall), nchunks (chunks of 8
+ * input channels), grid (kblocks * tblocks). */
+int tai_conv3x3_wino_forward_plan(int nparts, int shift_k, int has_pool, int has_addx, int has_y2, int N, int C, int K, int H, int W, int in_h,
+                                  int in_w, int in_oy, int in_ox, int act, const float* U, int* out);
 /* The same convolution as Winograd F(4x4, 3x3) on the fp32 MFMA pipe (csrc/wino43_conv.hip.inc): 36 multiplies per 4 x 4 output tile
  * instead of 16 per 2 x 2 -- 1.78x fewer MFMAs, ~7x the fp32 rounding error per layer; meant for the layers with C >= 128 and
  * K >= 128, where the bi-TAI forward's end-to-end error is unchanged (profiles/r04_wino_f43_study.txt, r04_wino43_default_parity.txt):

@@ -7,7 +7,8 @@ tests/golden/capi_refusals.json holds, for every call of CASES below, what the l
 
 -- on the commit BEFORE a change to the launchers, and the test replays the table on the tree and requires equality.  A call that is not
 refused may never be recorded (without a device it would reach a launch): the recorder stops at a return code other than
-TAI_SEPCONV_EINVAL.
+TAI_SEPCONV_EINVAL.  (The rows of an entry point that a change adds -- the plan queries -- can only come from that change's own tree;
+theirs are the words of the launchers they answer for, whose rows stand beside them.)
 
 Pointer arguments are None or the dummy address P, which a refused call never dereferences; the host arrays an entry reads before it
 refuses (xs[i], preds[i], table_host) are real ctypes arrays: ('ptrs', [...]) and ('i64', [...]).  ('f', 'inf') is a float that JSON
@@ -179,6 +180,15 @@ CASES = [
     case('tai_conv3x3_wino_wrw_window', P, P, P, P, P, 1, 8, 8, 8, 16, 0, 16, 0, 0, None),
     case('tai_conv3x3_wino_wrw_window', P, P, P, P, P, 1, 8, 8, 8, 16, 8, 16, 1, 0, None),
     case('tai_conv3x3_wino_wrw_window', P, P, P, P, P, 1, 8, 8, 8, 16, 10, 18, -1, 0, None),
+    case('tai_conv3x3_wino_wrw_window', P, P, P, P, P, 1, 8, 8, 8, 16, 8, 0, 0, 0, None),
+    # (the plan queries refuse with the launchers' words: the same functions decide)
+    case('tai_conv3x3_wino_forward_plan', 1, 0, 0, 0, 0, 1, 8, 8, 8, 8, 0, 0, 0, 0, 0, None, None),
+    case('tai_conv3x3_wino_forward_plan', 1, 10, 0, 0, 0, 1, 8, 8, 8, 8, 0, 0, 0, 0, 0, None, P),
+    case('tai_conv3x3_wino_forward_plan', 1, 0, 0, 1, 0, 1, 8, 8, 7, 8, 0, 0, 0, 0, 0, None, P),
+    case('tai_conv3x3_wino_wrw_plan', 1, 8, 8, 8, 16, 0, 0, 0, 0, None),
+    case('tai_conv3x3_wino_wrw_plan', 0, 8, 8, 8, 16, 0, 0, 0, 0, P),
+    case('tai_conv3x3_wino_wrw_plan', 1, 8, 8, 8, 16, 10, 18, -1, 0, P),
+    case('tai_conv3x3_wino_wrw_plan', 1, 8, 8, 8, 16, 8, 0, 0, 0, P),
     # ---- bf16 inference convolution
     case('tai_conv_bf16_weight_elems', 8, 16, 3),
     case('tai_conv_bf16_weight_elems', 16, 16, 4),

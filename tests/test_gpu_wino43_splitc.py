@@ -1,7 +1,9 @@
 """F(4x4, 3x3) forward with its reduction split over the input channels on small grids (tai_conv3x3_wino43_forward_ws; csrc/wino43_conv.hip.inc,
 conv3x3_gen<..., SPLITC> + splitc_reduce): against an fp64 convolution of the same operands, against the unsplit kernel, with every epilogue,
 bit for bit from run to run and from graph replay to replay, and bit-identical to the unsplit kernel where the split count is 1.
-Shapes: the small-grid layers of the configs[1] forward (N = 160 / 64 / 32)."""
+Shapes: the small-grid layers of the configs[1] forward (N = 160 / 64 / 32).
+(Nothing here runs between guard bands: the read behind the end of x with one ragged part, C % 4 != 0, is pinned by the `ws` cases of
+tests/test_gpu_wino_kernels.py.)"""
 import ctypes
 
 import pytest

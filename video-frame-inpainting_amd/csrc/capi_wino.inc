@@ -144,23 +144,58 @@ long long tai_conv3x3_wino_wrw_workspace_floats(int N, int C, int K, int H, int 
 static std::atomic<int> g_wrw_pair{1};              // 1: paired chunks (whole-line loads) when W % 32 == 0
 int tai_conv3x3_wino_wrw_set_paired(int on) { return g_wrw_pair.exchange(on ? 1 : 0, std::memory_order_relaxed); }
 
-static int wino_wrw_impl(const float* x, const float* dy, float* dw, float* dbias, float* workspace, int N, int C, int K, int H,
-                         int W, void* hip_stream, long long* stamps, int in_h = 0, int in_w = 0, int in_oy = 0, int in_ox = 0) {
-    g_err[0] = 0;
-    if (!x || !dy || !dw || !workspace) return fail(TAI_SEPCONV_EINVAL, "%s", "null pointer");
-    WrwPlan p;
+// THE decision of a weight-gradient launch (wino_wrw_impl below, and through it every entry point, and tai_conv3x3_wino_wrw_plan): the
+// refusals that depend on the dimensions alone, then the transform domain (tile 4: wino43::conv3x3_wrw_gen where its shape rules allow
+// and tai_conv3x3_wino_wrw_set_tile has not chosen 2) with that kernel's plan, and the load scheme of the F(2x2) kernel.  Returns 0, or
+// the refusal (fail).  in_h <= 0: no window (the plane is H x W at (0, 0)).
+struct WrwRoute { int tile, pair; WrwPlan p; };
+static int wrw_route(int N, int C, int K, int H, int W, int in_h, int in_w, int in_oy, int in_ox, bool stamps, WrwRoute& r) {
     if (in_h <= 0) { in_h = H; in_w = W; in_oy = in_ox = 0; }
+    else if (in_w <= 0) return fail(TAI_SEPCONV_EINVAL, "%s", "conv3x3_wino_wrw_window: bad plane");      // (the window launcher's own words)
     // the window of every tile must lie inside the plane or in its zero padding on all sides consistently: the origin may
     // not be negative and an input with a halo (origin > 0) must hold the whole 1-pixel frame
     if (in_oy < 0 || in_ox < 0 || in_oy + H > in_h || in_ox + W > in_w)
         return fail(TAI_SEPCONV_EINVAL, "%s", "conv3x3_wino_wrw: output window outside the input plane");
-    if (!wrw_plan(N, C, K, H, W, p, in_h, in_w))
+    if (!wrw_plan(N, C, K, H, W, r.p, in_h, in_w))
         return fail(TAI_SEPCONV_EINVAL, "%s", "conv3x3_wino_wrw: needs positive dimensions and tensors below 2 GiB");
-    if (p.ragged && stamps)
+    if (r.p.ragged && stamps)
         return fail(TAI_SEPCONV_EINVAL, "%s", "conv3x3_wino_wrw: timeline stamps need even H and W % 16 == 0");
-    hipStream_t stream = static_cast<hipStream_t>(hip_stream);
     WrwPlan q;
     if (g_wrw_tile.load(std::memory_order_relaxed) == 4 && !stamps && wrw43_plan(N, C, K, H, W, q, in_h, in_w, in_oy, in_ox)) {
+        r.tile = 4;
+        r.pair = 0;
+        r.p = q;
+        r.p.ragged = 0;
+        return 0;
+    }
+    r.tile = 2;
+    r.pair = r.p.pair && g_wrw_pair.load(std::memory_order_relaxed) ? 1 : 0;
+    return 0;
+}
+
+// The route of a launch as a query: the same wrw_route call, hence the same refusals with the same words, as tai_conv3x3_wino_wrw
+// (in_h <= 0) / tai_conv3x3_wino_wrw_window make for these dimensions.  No stream, no launch.
+int tai_conv3x3_wino_wrw_plan(int N, int C, int K, int H, int W, int in_h, int in_w, int in_oy, int in_ox, int* out) {
+    g_err[0] = 0;
+    if (!out) return fail(TAI_SEPCONV_EINVAL, "%s", "null pointer");
+    WrwRoute r;
+    if (int rc = wrw_route(N, C, K, H, W, in_h, in_w, in_oy, in_ox, false, r)) return rc;
+    const int v[8] = {r.tile, r.pair, r.p.ragged, r.p.kblocks, r.p.cblocks, r.p.nchunks, r.p.chunks_per_split, r.p.splits};
+    for (int i = 0; i < 8; ++i) out[i] = v[i];
+    return r.p.kblocks * r.p.cblocks * r.p.splits;
+}
+
+static int wino_wrw_impl(const float* x, const float* dy, float* dw, float* dbias, float* workspace, int N, int C, int K, int H,
+                         int W, void* hip_stream, long long* stamps, int in_h = 0, int in_w = 0, int in_oy = 0, int in_ox = 0) {
+    g_err[0] = 0;
+    if (!x || !dy || !dw || !workspace) return fail(TAI_SEPCONV_EINVAL, "%s", "null pointer");
+    if (in_h <= 0) { in_h = H; in_w = W; in_oy = in_ox = 0; }
+    WrwRoute r;
+    if (int rc = wrw_route(N, C, K, H, W, in_h, in_w, in_oy, in_ox, stamps != nullptr, r)) return rc;
+    const WrwPlan& p = r.p;
+    hipStream_t stream = static_cast<hipStream_t>(hip_stream);
+    if (r.tile == 4) {
+        const WrwPlan& q = r.p;
         const int Kpad = q.kblocks * 64, Cpad = (C + 63) / 64 * 64;
         float* wsb43 = dbias ? workspace + (long long)q.splits * 9 * Kpad * Cpad : nullptr;
         if (int rc = launch(wino43::conv3x3_wrw_gen, dim3((unsigned)(q.kblocks * q.cblocks * q.splits)), dim3(512), wino43::WRW_LDS_BYTES, stream, x, dy,
@@ -175,7 +210,7 @@ static int wino_wrw_impl(const float* x, const float* dy, float* dw, float* dbia
     }
     const int grid = p.kblocks * p.cblocks * p.splits;
     float* wsb = dbias ? workspace + (long long)p.splits * 9 * p.kblocks * 64 * p.cblocks * 64 : nullptr;
-    const bool pair = p.pair && g_wrw_pair.load(std::memory_order_relaxed);
+    const bool pair = r.pair != 0;
     auto kern = pair ? wino::wrw::conv3x3_wrw<0, true> : wino::wrw::conv3x3_wrw<0, false>;
     if (stamps) kern = pair ? wino::wrw::conv3x3_wrw<2, true> : wino::wrw::conv3x3_wrw<2, false>;
     else if (p.ragged) kern = wino::wrw::conv3x3_wrw<wino::wrw::WRW_RAGGED, false>;
@@ -272,14 +307,9 @@ int tai_conv3x3_wino_forward_timeline(const float* x, const float* U, const floa
     return wino_forward_impl(xs, 1, U, bias, y, N, C, K, H, W, 1, hip_stream, stamps);
 }
 
-#ifdef TAI_TIMING_VARIANTS
-static long long* g_wino_ex_stamps = nullptr;
-int tai_conv3x3_wino_ex_timeline_target(long long* stamps) { g_wino_ex_stamps = stamps; return 0; }
-#endif
-int tai_conv3x3_wino_forward_ex(const float* const* xs, int nparts, int shift_k, const float* U, const float* bias, float* y,
-                                float* ypool, int pool_h, int pool_w, int pool_oy, int pool_ox, const float* addx, float* y2, int N,
-                                int C, int K, int H, int W, int in_h, int in_w, int in_oy, int in_ox, int act, void* hip_stream) {
-    if (!xs || nparts < 1 || nparts > 4 || (shift_k != 0 && nparts != 1))
+// What tai_conv3x3_wino_forward_ex checks before it builds its WinoExtras, for the entry point and for tai_conv3x3_wino_forward_plan
+static int wino_ex_arguments(bool has_xs, int nparts, int shift_k, int C, bool has_addx, bool has_y2) {
+    if (!has_xs || nparts < 1 || nparts > 4 || (shift_k != 0 && nparts != 1))
         return fail(TAI_SEPCONV_EINVAL, "%s", "conv3x3_wino_ex: 1 to 4 input parts, or one tensor read S x S times (shift_k)");
     if (shift_k != 0 && (shift_k < 4 || shift_k > 9))
         return fail(TAI_SEPCONV_EINVAL, "%s", "conv3x3_wino_ex: shift_k is the size k of the k x k filter, 4 <= k <= 9");
@@ -288,7 +318,19 @@ int tai_conv3x3_wino_forward_ex(const float* const* xs, int nparts, int shift_k,
         return fail(TAI_SEPCONV_EINVAL, "%s", "conv3x3_wino: parts must have equal channel counts, a multiple of 8");
     if (shift_s != 0 && (C % (shift_s * shift_s) != 0 || (C / (shift_s * shift_s)) % 8 != 0))
         return fail(TAI_SEPCONV_EINVAL, "%s", "conv3x3_wino_ex: C = S^2 x (a multiple of 8), S = (shift_k + 2) / 3");
-    if (y2 && !addx) return fail(TAI_SEPCONV_EINVAL, "%s", "conv3x3_wino_ex: y2 needs addx");
+    if (has_y2 && !has_addx) return fail(TAI_SEPCONV_EINVAL, "%s", "conv3x3_wino_ex: y2 needs addx");
+    return 0;
+}
+
+#ifdef TAI_TIMING_VARIANTS
+static long long* g_wino_ex_stamps = nullptr;
+int tai_conv3x3_wino_ex_timeline_target(long long* stamps) { g_wino_ex_stamps = stamps; return 0; }
+#endif
+int tai_conv3x3_wino_forward_ex(const float* const* xs, int nparts, int shift_k, const float* U, const float* bias, float* y,
+                                float* ypool, int pool_h, int pool_w, int pool_oy, int pool_ox, const float* addx, float* y2, int N,
+                                int C, int K, int H, int W, int in_h, int in_w, int in_oy, int in_ox, int act, void* hip_stream) {
+    if (int rc = wino_ex_arguments(xs != nullptr, nparts, shift_k, C, addx != nullptr, y2 != nullptr)) return rc;
+    const int shift_s = shift_k ? (shift_k + 2) / 3 : 0;
     const float* p[4];
     for (int i = 0; i < 4; ++i) {
         p[i] = xs[i < nparts ? i : 0];
@@ -307,19 +349,27 @@ int tai_conv3x3_wino_forward_ex(const float* const* xs, int nparts, int shift_k,
     return wino_forward_impl(p, nparts, U, bias, y, N, C, K, H, W, act, hip_stream, nullptr, ypool, in_h, in_w, in_oy, in_ox, ex);
 }
 
-static int wino_forward_impl(const float* const* xs, int nparts, const float* U, const float* bias, float* y, int N, int C,
-                             int K, int H, int W, int act, void* hip_stream, long long* stamps, float* ypool, int in_h,
-                             int in_w, int in_oy, int in_ox, const WinoExtras& ex) {
+// THE decisions of one forward launch (wino_forward_impl below, and through it every entry point, and tai_conv3x3_wino_forward_plan): the
+// refusals that depend on the dimensions and on which optional arguments are present, then the arithmetic (a buffer made in split
+// arithmetic takes the split-bf16 kernel where that kernel has the shape), the workgroup shape, the parts mode, the epilogue and the grid.
+// Returns 0, or the refusal (fail).
+struct WinoFwdPlan {
+    int split, tall, pmode, epi, edge;        // split: 1 = wino::split::conv3x3<A, parts, E, edge>, 0 = wino::conv3x3<ACT, 0, 0, pmode, tall, epi>
+    int kblocks, nchunks;                     // blocks of WTM output channels (64; 128 tall), chunks of KC input channels
+    long long tblocks, grid;                  // blocks of WTN tiles (64; 32 tall), workgroups
+    int in_h, in_w, Kpad, Cpad, cpart, th, tw_all, pool_h, pool_w, pool_oy, pool_ox;
+};
+static int wino_forward_plan(int nparts, const WinoExtras& ex, bool has_pool, bool has_addx, bool has_y2, bool split_buf, bool stamps, int N, int C,
+                             int K, int H, int W, int in_h, int in_w, int in_oy, int in_ox, int act, WinoFwdPlan& p) {
     if (in_h == 0) { in_h = H; in_w = W; }
-    g_err[0] = 0;
-    if (!xs[0] || !U || !bias || !y) return fail(TAI_SEPCONV_EINVAL, "%s", "null pointer");
     const int S = ex.shift_s;
-    const int cpart = S ? C / (S * S) : C / nparts;
-    const int pool_h = ex.pool_h ? ex.pool_h : H / 2, pool_w = ex.pool_h ? ex.pool_w : W / 2;
-    const int pool_oy = ex.pool_h ? ex.pool_oy : 0, pool_ox = ex.pool_h ? ex.pool_ox : 0;
-    if (ypool && (pool_oy < 0 || pool_ox < 0 || pool_h < H / 2 + pool_oy || pool_w < W / 2 + pool_ox))
+    p.in_h = in_h; p.in_w = in_w;
+    p.cpart = S ? C / (S * S) : C / nparts;
+    const int pool_h = p.pool_h = ex.pool_h ? ex.pool_h : H / 2, pool_w = p.pool_w = ex.pool_h ? ex.pool_w : W / 2;
+    const int pool_oy = p.pool_oy = ex.pool_h ? ex.pool_oy : 0, pool_ox = p.pool_ox = ex.pool_h ? ex.pool_ox : 0;
+    if (has_pool && (pool_oy < 0 || pool_ox < 0 || pool_h < H / 2 + pool_oy || pool_w < W / 2 + pool_ox))
         return fail(TAI_SEPCONV_EINVAL, "%s", "conv3x3_wino: bad pooled-output window");
-    if (ypool && (long long)N * K * pool_h * pool_w >= (1LL << 29))
+    if (has_pool && (long long)N * K * pool_h * pool_w >= (1LL << 29))
         return fail(TAI_SEPCONV_EINVAL, "%s", "conv3x3_wino: pooled tensor too large (2^29 elements or more)");
     // displaced reads stay inside the plane: rows up to H + in_oy + 3 (S - 1), columns up to W + 1 + in_ox + 3 (S - 1)
     if (S && (in_oy < 1 || in_ox < 2 || in_h < H + in_oy + 1 + 3 * (S - 1) || in_w < W + in_ox + 2 + 3 * (S - 1)))
@@ -328,55 +378,104 @@ static int wino_forward_impl(const float* const* xs, int nparts, const float* U,
         return fail(TAI_SEPCONV_EINVAL, "%s", "conv3x3_wino: bad dimensions, act in {0, 1, 2}");
     // an odd side (the ragged-plane variant, EPI 3 of wino::conv3x3): plain input and output planes only
     const bool ragged = H % 2 != 0 || W % 2 != 0;
-    if (ragged && (ypool || S || ex.addx || stamps || in_h != H || in_w != W || in_oy != 0 || in_ox != 0))
+    if (ragged && (has_pool || S || has_addx || stamps || in_h != H || in_w != W || in_oy != 0 || in_ox != 0))
         return fail(TAI_SEPCONV_EINVAL, "%s", "conv3x3_wino: needs even H and W for a pooled output, the unpooling epilogue, an input "
                     "window or displaced reads (odd H or W: plain input and output only)");
     if (in_h < H + in_oy || in_w < W + in_ox || in_oy < 0 || in_ox < 0 || in_ox % 2 || (!ragged && in_w % 2))
         return fail(TAI_SEPCONV_EINVAL, "%s", "conv3x3_wino: bad input window");
     if ((long long)N * C * in_h * in_w >= (1LL << 29) || (long long)N * K * H * W >= (1LL << 29))   // byte offsets < 2^31
         return fail(TAI_SEPCONV_EINVAL, "%s", "conv3x3_wino: tensor too large (2^29 elements or more)");
-    const int Kpad = (K + wino::TM - 1) / wino::TM * wino::TM, Cpad = (C + wino::KC - 1) / wino::KC * wino::KC;
-    const int kblocks = Kpad / wino::TM, nchunks = Cpad / wino::KC;
-    const int th = (H + 1) / 2, tw_all = (W + 1) / 2;           // tiles per column / row (ceil: H / 2, W / 2 on even planes)
-    const long long tiles = (long long)N * th * tw_all;
-    const long long tblocks = (tiles + wino::TN - 1) / wino::TN;
+    p.Kpad = (K + wino::TM - 1) / wino::TM * wino::TM;
+    p.Cpad = (C + wino::KC - 1) / wino::KC * wino::KC;
+    p.nchunks = p.Cpad / wino::KC;
+    p.th = (H + 1) / 2; p.tw_all = (W + 1) / 2;                 // tiles per column / row (ceil: H / 2, W / 2 on even planes)
+    const long long tiles = (long long)N * p.th * p.tw_all;
+    const int epi = has_addx ? (has_y2 ? 1 : 2) : 0;
+    // A buffer made in split arithmetic (tai_conv3x3_wino_set_arithmetic(1)) takes the split-bf16 kernel where that kernel has the
+    // shape: no displaced reads, no timeline stamps, tile rows of 2^k or 16 m tiles (its 16-lane neighbour shifts).
+    if (split_buf && ragged)
+        return fail(TAI_SEPCONV_EINVAL, "%s", "conv3x3_wino: the split-bf16 arithmetic needs even H and W");
+    const int tw = W / 2;
+    const bool tw_ok = tw % 16 == 0 || (tw >= 2 && (tw & (tw - 1)) == 0);
+    if (split_buf && !S && !stamps && tw_ok && !(epi && act != 0)) {
+        p.split = 1; p.tall = 0; p.pmode = nparts > 1 ? 1 : 0; p.epi = epi;
+        p.edge = tw > 16 || in_ox > 0 || in_w > W + in_ox;
+        p.kblocks = p.Kpad / wino::TM;
+        p.tblocks = (tiles + wino::TN - 1) / wino::TN;
+        p.grid = p.tblocks * p.kblocks;
+        return 0;
+    }
+    // 128-channel x 32-tile workgroups (half the patch transform and LDS writes per MFMA) where K allows
+    p.split = 0; p.edge = 0;
+    p.tall = p.Kpad % wino::TTM == 0 && g_wino_tall.load(std::memory_order_relaxed) != 0;
+    p.pmode = S ? 2 : (nparts > 1 ? 1 : 0);
+    // the instantiations the path uses: the second-output / sum epilogues come without activation (Residual's last
+    // convolution) on one tensor or cat operands; the displaced reads come with ReLU (MotionEnc)
+    if (epi && (act != 0 || p.pmode == 2 || stamps)) return fail(TAI_SEPCONV_EINVAL, "%s", "conv3x3_wino_ex: addx needs act 0 and no displaced reads");
+    if (p.pmode == 2 && act != 1) return fail(TAI_SEPCONV_EINVAL, "%s", "conv3x3_wino_ex: displaced reads are built for act 1 (ReLU)");
+    p.epi = epi ? epi : (ragged ? 3 : 0);
+    p.kblocks = p.tall ? p.Kpad / wino::TTM : p.Kpad / wino::TM;
+    p.tblocks = p.tall ? (tiles + wino::TTN - 1) / wino::TTN : (tiles + wino::TN - 1) / wino::TN;
+    p.grid = p.tblocks * p.kblocks;
+    return 0;
+}
+
+// The plan of a launch as a query: the argument checks of tai_conv3x3_wino_forward_ex (wino_ex_arguments) and the same wino_forward_plan
+// call as the launcher makes, hence the same refusals with the same words.  The pooled output, where asked for, is the plain
+// [N, K, H/2, W/2] tensor.  U: the transformed-weight buffer the launch would read (its recorded arithmetic decides), or NULL for a
+// buffer in fp32 arithmetic.  No stream, no launch.
+int tai_conv3x3_wino_forward_plan(int nparts, int shift_k, int has_pool, int has_addx, int has_y2, int N, int C, int K, int H, int W, int in_h,
+                                  int in_w, int in_oy, int in_ox, int act, const float* U, int* out) {
+    g_err[0] = 0;
+    if (!out) return fail(TAI_SEPCONV_EINVAL, "%s", "null pointer");
+    if (int rc = wino_ex_arguments(true, nparts, shift_k, C, has_addx != 0, has_y2 != 0)) return rc;
+    WinoExtras ex;
+    ex.shift_s = shift_k ? (shift_k + 2) / 3 : 0;
+    ex.zero_tail = (shift_k && 3 * ex.shift_s > shift_k) ? 1 : 0;
+    bool split_buf = false;
+    if (U) { std::lock_guard<std::mutex> lk(g_split_mu); split_buf = g_split_bufs.count(U) != 0; }
+    WinoFwdPlan p;
+    if (int rc = wino_forward_plan(nparts, ex, has_pool != 0, has_addx != 0, has_y2 != 0, split_buf, false, N, C, K, H, W, in_h, in_w, in_oy, in_ox, act, p))
+        return rc;
+    const int v[9] = {p.split, p.tall, p.pmode, p.epi, p.edge, p.kblocks, (int)p.tblocks, p.nchunks, (int)p.grid};
+    for (int i = 0; i < 9; ++i) out[i] = v[i];
+    return (int)p.grid;
+}
+
+static int wino_forward_impl(const float* const* xs, int nparts, const float* U, const float* bias, float* y, int N, int C,
+                             int K, int H, int W, int act, void* hip_stream, long long* stamps, float* ypool, int in_h,
+                             int in_w, int in_oy, int in_ox, const WinoExtras& ex) {
+    g_err[0] = 0;
+    if (!xs[0] || !U || !bias || !y) return fail(TAI_SEPCONV_EINVAL, "%s", "null pointer");
+    bool split_buf;
+    { std::lock_guard<std::mutex> lk(g_split_mu); split_buf = g_split_bufs.count(U) != 0; }
+    WinoFwdPlan p;
+    if (int rc = wino_forward_plan(nparts, ex, ypool != nullptr, ex.addx != nullptr, ex.y2 != nullptr, split_buf, stamps != nullptr, N, C, K, H, W, in_h,
+                                   in_w, in_oy, in_ox, act, p))
+        return rc;
+    in_h = p.in_h; in_w = p.in_w;
+    const int S = ex.shift_s, cpart = p.cpart, Kpad = p.Kpad, nchunks = p.nchunks;
     hipStream_t s = static_cast<hipStream_t>(hip_stream);
     // the divisors of the kernels' index arithmetic: tiles per image, tiles per row, blocks of output channels
     wino::DivMagic dv;
-    wino_div_magic((long long)th * tw_all, dv.m_tpi, dv.s_tpi);
-    wino_div_magic(tw_all, dv.m_tw, dv.s_tw);
-    wino_div_magic(kblocks, dv.m_kb, dv.s_kb);
-    const int epi = ex.addx ? (ex.y2 ? 1 : 2) : 0;
-    // A buffer made in split arithmetic (tai_conv3x3_wino_set_arithmetic(1)) takes the split-bf16 kernel where that kernel has the
-    // shape: no displaced reads, no timeline stamps, tile rows of 2^k or 16 m tiles (its 16-lane neighbour shifts).
-    {
-        bool split_buf;
-        { std::lock_guard<std::mutex> lk(g_split_mu); split_buf = g_split_bufs.count(U) != 0; }
-        if (split_buf && ragged)
-            return fail(TAI_SEPCONV_EINVAL, "%s", "conv3x3_wino: the split-bf16 arithmetic needs even H and W");
-        const int tw = W / 2;
-        const bool tw_ok = tw % 16 == 0 || (tw >= 2 && (tw & (tw - 1)) == 0);
-        if (split_buf && !S && !stamps && tw_ok && !(epi && act != 0)) {
-            const unsigned short* U3 = reinterpret_cast<const unsigned short*>(U + 16LL * Kpad * Cpad);
-            const bool edge = tw > 16 || in_ox > 0 || in_w > W + in_ox, parts = nparts > 1;
-            auto kern = epi == 1 ? wino_split_kernel<0, 1>(parts, edge) : epi == 2 ? wino_split_kernel<0, 2>(parts, edge)
-                      : act == 0 ? wino_split_kernel<0, 0>(parts, edge) : act == 1 ? wino_split_kernel<1, 0>(parts, edge)
-                                                                                   : wino_split_kernel<2, 0>(parts, edge);
-            if (int rc = launch(kern, dim3((unsigned)(tblocks * kblocks)), dim3(512), wino::split::LDS_BYTES, s, xs[0], xs[1], xs[2], xs[3], cpart, U3,
-                                bias, y, ypool, N, C, K, H, W, in_h, in_w, in_oy, in_ox, nchunks, kblocks, pool_h, pool_w, pool_oy, pool_ox, ex.addx,
-                                ex.y2, dv, nullptr))
-                return rc;
-            return check_launch("conv3x3_wino_split");
-        }
+    wino_div_magic((long long)p.th * p.tw_all, dv.m_tpi, dv.s_tpi);
+    wino_div_magic(p.tw_all, dv.m_tw, dv.s_tw);
+    wino_div_magic(p.kblocks, dv.m_kb, dv.s_kb);
+    if (p.split) {
+        const unsigned short* U3 = reinterpret_cast<const unsigned short*>(U + 16LL * Kpad * p.Cpad);
+        const bool edge = p.edge != 0, parts = p.pmode == 1;
+        auto kern = p.epi == 1 ? wino_split_kernel<0, 1>(parts, edge) : p.epi == 2 ? wino_split_kernel<0, 2>(parts, edge)
+                  : act == 0 ? wino_split_kernel<0, 0>(parts, edge) : act == 1 ? wino_split_kernel<1, 0>(parts, edge)
+                                                                               : wino_split_kernel<2, 0>(parts, edge);
+        if (int rc = launch(kern, dim3((unsigned)p.grid), dim3(512), wino::split::LDS_BYTES, s, xs[0], xs[1], xs[2], xs[3], cpart, U3,
+                            bias, y, ypool, N, C, K, H, W, in_h, in_w, in_oy, in_ox, nchunks, p.kblocks, p.pool_h, p.pool_w, p.pool_oy, p.pool_ox, ex.addx,
+                            ex.y2, dv, nullptr))
+            return rc;
+        return check_launch("conv3x3_wino_split");
     }
-    // 128-channel x 32-tile workgroups (half the patch transform and LDS writes per MFMA) where K allows
-    const bool tall = Kpad % wino::TTM == 0 && g_wino_tall.load(std::memory_order_relaxed) != 0;
-    const int pmode = S ? 2 : (nparts > 1 ? 1 : 0);
+    const bool tall = p.tall != 0;
+    const int pmode = p.pmode;
     const int part_magic = S ? (1 << 20) / (cpart / 8) + 1 : 0;     // chunk -> channel block of the displaced reads
-    // the instantiations the path uses: the second-output / sum epilogues come without activation (Residual's last
-    // convolution) on one tensor or cat operands; the displaced reads come with ReLU (MotionEnc)
-    if (epi && (act != 0 || pmode == 2 || stamps)) return fail(TAI_SEPCONV_EINVAL, "%s", "conv3x3_wino_ex: addx needs act 0 and no displaced reads");
-    if (pmode == 2 && act != 1) return fail(TAI_SEPCONV_EINVAL, "%s", "conv3x3_wino_ex: displaced reads are built for act 1 (ReLU)");
     WinoKernel kern;        // <ACT, DBG, SKIP, PARTS, TALL, EPI>
     if (stamps) {           // timeline launches (tools/wino_timeline.py): ReLU, one tensor
         kern = wino_kernel<1, 1, 0, 0, 0>(tall);
@@ -390,21 +489,14 @@ static int wino_forward_impl(const float* const* xs, int nparts, const float* U,
         else if (pmode == 2) kern = wino_kernel<1, 1, 0, 2, 0>(tall);
 #endif
     }
-    else if (epi == 1) kern = pmode == 1 ? wino_kernel<0, 0, 0, 1, 1>(tall) : wino_kernel<0, 0, 0, 0, 1>(tall);
-    else if (epi == 2) kern = pmode == 1 ? wino_kernel<0, 0, 0, 1, 2>(tall) : wino_kernel<0, 0, 0, 0, 2>(tall);
+    else if (p.epi == 1) kern = pmode == 1 ? wino_kernel<0, 0, 0, 1, 1>(tall) : wino_kernel<0, 0, 0, 0, 1>(tall);
+    else if (p.epi == 2) kern = pmode == 1 ? wino_kernel<0, 0, 0, 1, 2>(tall) : wino_kernel<0, 0, 0, 0, 2>(tall);
     else if (pmode == 2) kern = wino_kernel<1, 0, 0, 2, 0>(tall);
-    else if (ragged) kern = pmode == 1 ? wino_kernel_act<1, 3>(act, tall) : wino_kernel_act<0, 3>(act, tall);       // odd H or W
+    else if (p.epi == 3) kern = pmode == 1 ? wino_kernel_act<1, 3>(act, tall) : wino_kernel_act<0, 3>(act, tall);       // odd H or W
     else kern = pmode == 1 ? wino_kernel_act<1, 0>(act, tall) : wino_kernel_act<0, 0>(act, tall);
-    long long grid = tblocks * kblocks;
-    int kb = kblocks;
-    if (tall) {
-        kb = Kpad / wino::TTM;
-        grid = (tiles + wino::TTN - 1) / wino::TTN * kb;
-        wino_div_magic(kb, dv.m_kb, dv.s_kb);
-    }
-    if (int rc = launch(kern, dim3((unsigned)grid), dim3(256), tall ? wino::TLDS_BYTES : wino::LDS_BYTES, s, xs[0], xs[1], xs[2], xs[3], cpart, U, bias, y,
-                        ypool, N, C, K, H, W, in_h, in_w, in_oy, in_ox, Kpad, nchunks, kb, stamps, pool_h, pool_w, pool_oy, pool_ox, ex.addx, ex.y2, S,
-                        part_magic, ex.zero_tail, dv))
+    if (int rc = launch(kern, dim3((unsigned)p.grid), dim3(256), tall ? wino::TLDS_BYTES : wino::LDS_BYTES, s, xs[0], xs[1], xs[2], xs[3], cpart, U, bias, y,
+                        ypool, N, C, K, H, W, in_h, in_w, in_oy, in_ox, Kpad, nchunks, p.kblocks, stamps, p.pool_h, p.pool_w, p.pool_oy, p.pool_ox, ex.addx,
+                        ex.y2, S, part_magic, ex.zero_tail, dv))
         return rc;
     return check_launch("conv3x3_wino");
 }

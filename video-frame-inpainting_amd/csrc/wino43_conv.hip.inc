@@ -234,12 +234,20 @@ void conv3x3_gen(const float* __restrict__ x, const float* __restrict__ x1, cons
         unsigned long long b[4] = {reinterpret_cast<unsigned long long>(x), reinterpret_cast<unsigned long long>(x1),
                                    reinterpret_cast<unsigned long long>(x2), reinterpret_cast<unsigned long long>(x3)};
         int c0 = 0, nch = nchunks;            // this workgroup's chunks
+        long long moved = 0;                  // bytes the (one, ragged) part's base has moved on
         if constexpr (SPLITC) {
             c0 = sp * win.chunks_per_split;
             nch = min(win.chunks_per_split, nchunks - c0);
             // first part p0 at chunk o: the parts from p0 on move into slots 0.. (past the last part: never read), part p0's base moves
-            // o chunks on -- the same addresses and the same range check (the soffset is not in it) as the unsplit loop's at chunk c0
+            // o chunks on -- the same addresses as the unsplit loop's at chunk c0.  The hardware's range check INCLUDES the scalar offset
+            // (a load is out of range when vector offset + scalar offset >= num_records; that is how the unsplit loop, whose chunk offset
+            // rides in the scalar offset, gets 0.0 for the last image's channels C .. Cpad - 1) and counts from the base.  So with ONE
+            // part of a ragged channel count num_records shrinks by what the base moved: those channels are then past the end exactly
+            // as in the unsplit loop (with num_records left whole they were read from behind the tensor's end, up to 3 planes of foreign
+            // memory times zero weights).  Only then (cpart == C): several parts are whole chunks each, nothing is read past a part,
+            // and their bases are other tensors'.
             const int cpp = (cpart + KC - 1) / KC, p0 = c0 / cpp, o = c0 - p0 * cpp;
+            if (cpart == C) moved = (long long)o * KC * plane * 4;
             const unsigned long long q[4] = {b[0], b[1], b[2], b[3]};
 #pragma unroll
             for (int i = 0; i < 4; ++i) b[i] = p0 + i == 1 ? q[1] : p0 + i == 2 ? q[2] : p0 + i == 3 ? q[3] : q[0];
@@ -252,7 +260,7 @@ void conv3x3_gen(const float* __restrict__ x, const float* __restrict__ x1, cons
         }
         const unsigned long long ub = reinterpret_cast<unsigned long long>(U) +
             (((unsigned long long)kb * nchunks + c0) * (U_STAGE * 4) + (unsigned long long)(wave & 3) * 1024ull);
-        sin[8] = __builtin_amdgcn_readfirstlane((int)((long long)N * cpart * plane * 4));      // bytes of a part (num_records)
+        sin[8] = __builtin_amdgcn_readfirstlane((int)((long long)N * cpart * plane * 4 - moved));      // bytes of a part (num_records)
         sin[9] = __builtin_amdgcn_readfirstlane((cpart + KC - 1) / KC);                         // chunks per part (one part: all of them)
         sin[10] = __builtin_amdgcn_readfirstlane(nch);
         sin[11] = __builtin_amdgcn_readfirstlane((int)(KC * plane * 4));                        // bytes from one chunk's channels to the next

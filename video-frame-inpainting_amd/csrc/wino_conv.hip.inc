@@ -299,13 +299,14 @@ void conv3x3(const float* __restrict__ x, const float* __restrict__ x1, const fl
     const unsigned long long xd1 = reinterpret_cast<unsigned long long>(x1) - xb0, xd2 = reinterpret_cast<unsigned long long>(x2) - xb0,
                              xd3 = reinterpret_cast<unsigned long long>(x3) - xb0;
     // Left / right outer values: the neighbouring lane's middle pair when that lane is the neighbouring tile of the same
-    // tile row (mask 1), else an own load (first / last tile of a row, lanes 0 / 63) -- or nothing, where the column is
+    // tile row, else an own load (first / last tile of a row, lanes 0 / 63) -- or nothing, where the column is
     // outside the input plane (the zero padding).
     const bool left_in = pvalid && 2 * ptx - 1 + in_ox >= 0, right_in = pvalid && 2 * ptx + 2 + in_ox < in_w;
     // (128 x 32 shape: lanes 31 | 32 are not neighbours -- different channels -- so both ends of each half-wave load their own)
     const bool first_lane = TALL ? l5 == 0 : lane == 0, last_lane = TALL ? l5 == 31 : lane == 63;
-    const float mask_left = (pvalid && ptx > 0 && !(TALL && first_lane)) ? 1.f : 0.f,
-                mask_right = (pvalid && ptx < TW - 1 && !(TALL && last_lane)) ? 1.f : 0.f;
+    // (as lane masks: the lanes that KEEP their own outer value)
+    const unsigned long long keep_left = __builtin_amdgcn_ballot_w64(!(pvalid && ptx > 0 && !(TALL && first_lane))),
+                             keep_right = __builtin_amdgcn_ballot_w64(!(pvalid && ptx < TW - 1 && !(TALL && last_lane)));
     const bool left_own = left_in && (ptx == 0 || first_lane), right_own = right_in && (ptx == TW - 1 || last_lane);
     unsigned off_mid[4], off_left[4], off_right[4];     // byte offsets from the channel plane of image 0
     unsigned off_mid1[4];                               // RAGGED: the middle pair's second value (out of range at column W)
@@ -394,18 +395,22 @@ void conv3x3(const float* __restrict__ x, const float* __restrict__ x1, const fl
             xrsrc = xrsrc0;
             soff = (int)((long long)cc * plane_in * 4);
         }
+        // 128 x 32 shape, odd C: channel C - 1's partner in lanes 32-63 would be channel 0 of the NEXT image (times zero weights,
+        // but 0 x NaN / Inf there would reach this image): those lanes go out of range and read 0.0
+        unsigned past = 0;
+        if constexpr (TALL && PARTS == 0) past = (c + 1 >= C && pkk) ? OUT_OF_RANGE : 0u;
         if (what != 2) {
             if constexpr (RAGGED) {
-                dm[buf][p][i].x = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(xrsrc, off_mid[i], soff, 0));
-                dm[buf][p][i].y = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(xrsrc, off_mid1[i], soff, 0));
+                dm[buf][p][i].x = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(xrsrc, off_mid[i] | past, soff, 0));
+                dm[buf][p][i].y = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(xrsrc, off_mid1[i] | past, soff, 0));
             } else {
-                dm[buf][p][i] = __builtin_bit_cast(float2, __builtin_amdgcn_raw_buffer_load_b64(xrsrc, off_mid[i], soff, 0));
+                dm[buf][p][i] = __builtin_bit_cast(float2, __builtin_amdgcn_raw_buffer_load_b64(xrsrc, off_mid[i] | past, soff, 0));
             }
         }
         // own outer values (first / last tile of a tile row, lanes 0 / 63); every other lane is out of range: no memory access
         if (what != 1) {
-            dlr[buf][p][i].x = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(xrsrc, off_left[i], soff, 0));
-            dlr[buf][p][i].y = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(xrsrc, off_right[i], soff, 0));
+            dlr[buf][p][i].x = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(xrsrc, off_left[i] | past, soff, 0));
+            dlr[buf][p][i].y = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(xrsrc, off_right[i] | past, soff, 0));
         }
     };
 
@@ -447,13 +452,17 @@ void conv3x3(const float* __restrict__ x, const float* __restrict__ x1, const fl
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             const float2 m = dm[buf][p][i];
-            // lane l takes lane l-1's m.y as its left value and lane l+1's m.x as its right value, times the column
-            // mask (0 where that lane is not the neighbouring tile: first / last tile of a tile row), added to the lane's
-            // own outer load (0.0 unless it is such a tile).  Lane 0 has no lane to its left: the instruction leaves its
-            // register alone, i.e. its own load; likewise lane 63 on the right.  (0 x finite: inputs are assumed finite.)
+            // lane l takes lane l-1's m.y as its left value and lane l+1's m.x as its right value, unless that lane is
+            // not the neighbouring tile (first / last tile of a tile row): then it KEEPS its own outer load (0.0 where the
+            // column is padding).  A select on the lane mask, not a multiply by 0.0: the neighbouring lane may hold another
+            // image, and 0 x NaN / Inf there would reach this one.  Lane 0 has no lane to its left: the instruction leaves
+            // its register alone, i.e. its own load; likewise lane 63 on the right.  (The VOP2 select takes its mask from
+            // vcc only; the scalar move in front of it is free next to the vector work.)
             float left = dlr[buf][p][i].x, right = dlr[buf][p][i].y;
-            asm("v_fmac_f32_dpp %0, %1, %2 wave_shr:1 row_mask:0xf bank_mask:0xf" : "+v"(left) : "v"(m.y), "v"(mask_left));
-            asm("v_fmac_f32_dpp %0, %1, %2 wave_shl:1 row_mask:0xf bank_mask:0xf" : "+v"(right) : "v"(m.x), "v"(mask_right));
+            asm("s_mov_b64 vcc, %2\n\tv_cndmask_b32_dpp %0, %1, %0, vcc wave_shr:1 row_mask:0xf bank_mask:0xf"
+                : "+v"(left) : "v"(m.y), "s"(keep_left) : "vcc");
+            asm("s_mov_b64 vcc, %2\n\tv_cndmask_b32_dpp %0, %1, %0, vcc wave_shl:1 row_mask:0xf bank_mask:0xf"
+                : "+v"(right) : "v"(m.x), "s"(keep_right) : "vcc");
             mid[i] = v2f{m.x, m.y};
             out[i] = v2f{left, right};
         }
