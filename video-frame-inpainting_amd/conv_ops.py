@@ -33,8 +33,11 @@ def invalidate_derived(module=None):
     parameters, or of every weight when ``module`` is None.  The cache notices writes that move the tensor's version
     counter (optimizer steps, ``load_state_dict``, ``with torch.no_grad(): p.mul_(2)``) by itself; a write through
     ``p.data`` moves neither the counter nor the pointer (``p.data.normal_()``, ``dist.broadcast(p.data, ...)``, a user's
-    EMA or clipping), so whoever writes that way calls this afterwards -- ``util.weights_init``,
-    ``parallel.broadcast_module_state`` and the environments' ``load`` do."""
+    EMA or clipping), and neither does a kernel or a numpy view that is handed the weight's raw pointer, so whoever writes
+    that way calls this afterwards -- ``parallel.broadcast_module_state``, the environments' ``load``, a replayed captured
+    update (``train_step``), ``fused_step.averaged_weights`` and ``FusedStep.step`` do: the fused optimizer step
+    (``tai_fused_step`` on the device, ``host_step`` on numpy views) is a raw-pointer writer and drops the forms of the module it
+    stepped after every launch, whatever the device-side verdict (tests/derived_cases.py lists the writers and the forms)."""
     if module is None:
         _EPOCH[0] += 1
         return

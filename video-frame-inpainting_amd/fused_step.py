@@ -26,7 +26,7 @@ import math
 import numpy as np
 import torch
 
-from . import grad_guard, parallel
+from . import conv_ops, grad_guard, parallel
 from .grad_guard import CLIPPED, OK, SEG, SKIPPED, GuardGaveUp
 
 REC_WORDS = 32
@@ -272,6 +272,9 @@ class FusedStep(object):
                 _native.launch('tai_fused_step', self.device, tb.rows, rows.ctypes.data, n, n_segments, o.scalars, self.table_len,
                                float(o.k.w1), float(o.k.b2), float(o.k.w2), float(o.k.eps), float(o.k.wE), self.rec, w, int(NT_LOADS),
                                int(self.blocks), None)
+        # the weights were written through raw pointers (numpy views on the host): no version counter moved.  Whatever the verdict --
+        # the host does not know it -- no derived form of this module's weights stays valid; the other module's forms are left alone
+        conv_ops.invalidate_derived(o.module)
         if last:
             self._end_update()
 
