@@ -617,6 +617,56 @@ int tai_temporal_loss(const float* const* preds, int npred, const float* gt,
                       float* const* grads /* NULL, or npred pointers each of which may be NULL */,
                       void* workspace, int B, int T, int C, int H, int W, void* stream /* the HIP stream */);
 
+/* Census (soft ternary) loss of 1-3 predictions against one ground truth, and its gradients, one launch (csrc/census_loss.hip.inc;
+ * losses.CensusLoss; tests/census_loss_ref.py restates it in numpy).  It compares, per pixel, how the pixel relates to its 7 x 7
+ * neighbours (UnFlow's ternary census distance): a constant added to a frame changes nothing.
+ * pred_i (i < npred, npred in 1..3) and gt are fp32, nominally in [-1, 1] and NOT clipped, indexed (b, t, c, r, col) with b < B, t < T,
+ * c < C, r < H, col < W; C is 1 or 3 and H, W >= 7.  Strides are tai_temporal_loss's: a dense [C, H, W] block per (b, t), the element at
+ * b * sb + t * st + c * H * W + r * W + col with the tensor's own batch and time stride, no two blocks overlapping.  A frame is one
+ * (b, t); there are B * T of them, numbered b * T + t.
+ * Definition, per frame; every fp32 operation is a single IEEE operation, no contraction, no reassociation, division and square root
+ * correctly rounded:
+ *   intensity: x = (pred + 1) / 2 per channel (util.inverse_transform);  C = 1: I = x;
+ *     C = 3: I = (0.1140f * x0 + 0.5870f * x1) + 0.2989f * x2 (util.gray01's operand order);  J the same from gt;
+ *   offsets j = (dy, dx) over {-3..3}^2 without (0, 0), in row-major ascending order (dy outer): "the order";
+ *   for a pixel q and an offset j with q and q + j inside the plane:
+ *     s = 255f * (I(q+j) - I(q));  u = 0.81f + s * s;  r = sqrtf(u);  t = s / r;  s', t' the same from J;
+ *     d = t - t';  e = d * d;  n = 0.1f + e;  phi = e / n;
+ *     dphi = ((2f * d) * 0.1f) / (n * n);  tau = 0.81f / (u * r);  w(q, j) = (double)dphi * (double)tau;
+ *   Omega is the interior, rows 3..H-4 and columns 3..W-4: the pixels whose window is whole;
+ *   D(q) = (sum_j (double)phi(q, j)) / 49.0 for q in Omega, in the order, from 0.0 (the centre of the customary 49 contributes 0);
+ *   frame_terms[i][b*T + t] = (sum over Omega of D) / ((H-6) * (W-6));
+ *   totals[i] = (sum of the frame terms in frame order, from 0.0) / (B * T): the loss of prediction i;
+ *     the order of the sum over Omega is the kernel's, but it is fixed: tile partials go to the workspace and are summed per frame in
+ *     tile order; no atomics.
+ * Gradient with respect to I, computed in float64:
+ *   G(q) = -(sum_j m(q, j) * w(q, j)),  m(q, j) = [q in Omega] + [q+j in Omega] (0, 1 or 2, multiplied as a double),
+ *   over the j whose q + j lies in the plane, in the order, from 0.0.  This is the exact adjoint from the pixel's own neighbourhood: the
+ *   term that window q - k sends to q is w(q-k, k), and w(q-k, k) == -w(q, -k) in IEEE arithmetic, because every operation above is
+ *   exactly odd or even in s.  No scatter, no second pass.
+ * Output gradient, rounded once:
+ *   count = (double)(B * T) * ((H-6) * (W-6));  kappa = (255.0 * 0.5) / (49.0 * count);
+ *   C = 1: grad[q] = fp32(G * kappa);  C = 3: channel c gets fp32((G * kappa) * (double)w_c), w = (0.1140f, 0.5870f, 0.2989f);
+ *   it is written with the strides of pred_i.  No gradient goes to gt.
+ * grads may be NULL, and so may any grads[i] (evaluation only); the other outputs keep their bits.
+ * A pixel's grad bits and a frame's frame_terms bits depend on that frame's pixels and on (B T, H, W) only: not on the batch, the other
+ * frames, npred, the other predictions of the launch, or the layout a tensor is stored in.  A NaN in one frame makes that frame's
+ * outputs and the totals non-finite and no other frame's.  preds, grads and strides are host arrays, read before the call returns.  No
+ * allocation, copy or synchronisation: asynchronous on the stream and capturable into a hipGraph.  workspace: 8-byte aligned,
+ * tai_census_loss_workspace_bytes bytes.
+ * TAI_SEPCONV_EINVAL with a message, nothing launched: a null preds / preds[i] / gt / strides / frame_terms / totals / workspace; npred
+ * outside 1..3; a dimension < 1; C outside {1, 3}; H or W < 7; B T C H W >= 2^40, H W >= 2^31, B T >= 2^31 or 2^31 or more 32 x 32
+ * tiles; a stride < 1, strides that reach an offset of 2^40 elements, or strides under which two blocks overlap; float64 buffers not
+ * 8-byte aligned.  The workspace query returns TAI_SEPCONV_EINVAL for the same dimensions.
+ * The last parameter is the HIP stream, spelled `stream` for the reason given at tai_temporal_loss; the refusals are pinned by
+ * tests/test_census_loss_cpu.py. */
+long long tai_census_loss_workspace_bytes(int npred, int B, int T, int C, int H, int W);
+int tai_census_loss(const float* const* preds, int npred, const float* gt,
+                    const long long* strides /* host, [npred + 1][2]: batch, time stride in elements; preds first, gt last */,
+                    double* frame_terms /* [npred][B*T] */, double* totals /* [npred] */,
+                    float* const* grads /* NULL, or npred pointers each of which may be NULL */,
+                    void* workspace, int B, int T, int C, int H, int W, void* stream /* the HIP stream */);
+
 /* The clip pipeline's two ends (csrc/clip_pipeline.hip.inc): what stands between a decoded frame and the models, and between the models
  * and a PNG, bit-equal to the host code (video_frame_inpainting_amd/data.py and util.py) it replaces when asked to.
  *

@@ -1,8 +1,8 @@
 #!/usr/bin/env python3
-"""The fused losses (tai_ssim_loss, tai_image_loss, tai_lap_loss, tai_temporal_loss behind losses.SSIMLoss, ImageLoss, LapLoss,
-TemporalLoss): the launch against the torch ops it replaces, and one eager TAI_gray update with and without the term.
+"""The fused losses (tai_ssim_loss, tai_image_loss, tai_lap_loss, tai_temporal_loss, tai_census_loss behind losses.SSIMLoss, ImageLoss,
+LapLoss, TemporalLoss, CensusLoss): the launch against the torch ops it replaces, and one eager TAI_gray update with and without the term.
 
-  python tools/loss_bench.py --loss {ssim,image,lap,temporal} [--reps 30] [--updates 10] [--out profiles/<loss>_loss_bench.jsonl]
+  python tools/loss_bench.py --loss {ssim,image,lap,temporal,census} [--reps 30] [--updates 10] [--out profiles/<loss>_loss_bench.jsonl]
                              [--no-updates]
 
 (a) launches   at the loss's two shapes (below), loss + gradient:
@@ -33,7 +33,11 @@ temporal  train.py --temporal_weight.  (a) three predictions against one ground 
           (Charbonnier, the default of the flag); torch: the same definition in torch ops (losses._temporal_terms, the module's own
           path for tensors the kernel does not take), once per prediction; bytes as for image.  (b) without the term and with
           --temporal_weight 0.5; the difference is given next to the leg-to-leg spread, and next to what the module alone takes at the
-          update's shape."""
+          update's shape.
+census    train.py --census_weight.  (a) the temporal loss's two shapes and layouts; torch: the same definition in torch ops in float64
+          (losses._census_terms, the module's own path for tensors the kernel does not take), once per prediction.  The kernel is bound
+          by the vector ALU (48 offsets x (2 square roots + 5 divisions) per pixel and prediction), so next to the bytes its rate is given
+          in (pixel, offset, prediction) terms per second.  (b) without the term and with --census_weight 0.5, as for temporal."""
 import argparse
 import ctypes
 import json
@@ -109,10 +113,16 @@ def pixel_rates(pixels, kernel_ms, share):
     return rates
 
 
-def byte_rates(elements, kernel_ms):
+def byte_rates(g, kernel_ms):
+    elements = g.numel()
     nbytes = (2 * NPRED + 1) * 4 * elements
     return {'launch_bytes': nbytes, 'kernel_GBps': round(nbytes / kernel_ms / 1e6, 1),
             'kernel_fraction_of_hbm_peak': round(nbytes / kernel_ms / 1e6 / HBM_PEAK_GBPS, 4), 'hbm_peak_GBps': HBM_PEAK_GBPS}
+
+
+def census_rates(g, kernel_ms):
+    terms = g.numel() // g.shape[2] * 48 * NPRED                  # every pixel of the plane looks at (up to) 48 neighbours, per prediction
+    return {**byte_rates(g, kernel_ms), 'kernel_Gterms_per_s': round(terms / kernel_ms / 1e6, 2)}
 
 
 def planes_head(name, shape, reps, **first):
@@ -148,6 +158,14 @@ def temporal_kernel(preds, g):
                                                           B, Tn, C, H, W))
 
 
+def census_kernel(preds, g):
+    B, Tn, C, H, W = g.shape
+    n = len(preds)
+    strides = (ctypes.c_longlong * (2 * n + 2))(*[v for t in list(preds) + [g] for v in losses._block_strides(t)])
+    return raw_launcher('tai_census_loss', (n, B, Tn, C, H, W), n * B * Tn, n, preds,
+                        lambda p, detail, totals, m, ws: (table(p), n, g.data_ptr(), strides, detail, totals, table(m), ws, B, Tn, C, H, W))
+
+
 def composition(pt, g):
     """MSELoss + GDL of three predictions as the environments run them."""
     mse, gdl = torch.nn.MSELoss(), losses.GDL()
@@ -166,8 +184,8 @@ def sum_of_three(module, pm, g):
 
 
 # Per loss: the shapes; inputs(name, shape) -> (preds, gt); the raw-ABI launcher; the module, how it is called and the torch ops, each ->
-# the tensor to call backward on; head(name, shape, reps, preds, gt) -> the record's fields up to `reps`; rates(elements, kernel ms);
-# which variant the record's verdict compares with torch; value(totals) -> the loss field(s); more(grads, torch grads) -> further fields.
+# the tensor to call backward on; head(name, shape, reps, preds, gt) -> the record's fields up to `reps`; rates
+# (gt, kernel ms); which variant the record's verdict compares with torch; value(totals) -> the loss field(s); more(grads, torch grads) -> further fields.
 # For the update legs: the two environments {leg: (name, keyword arguments)}, the record's settings, the names of its difference and
 # verdict fields (``two_sided``: the verdict takes the difference's size) and the errors it lists.
 LOSSES = {
@@ -175,7 +193,7 @@ LOSSES = {
         shapes=PLANE_SHAPES, inputs=one_pair, kernel=ssim_kernel, module=losses.SSIMLoss, call=lambda m, pm, g: m(pm[0], g),
         torch=lambda pt, g: (1.0 - losses._ssim_planes(pt[0], g).mean(dim=(1, 2, 3)).mean()).to(torch.float32),
         head=lambda name, shape, reps, preds, g: planes_head(name, shape, reps),
-        rates=lambda n, ms: pixel_rates(n, ms, False), verdict='kernel', value=lambda totals: {'loss': float(totals[-1])},
+        rates=lambda g, ms: pixel_rates(g.numel(), ms, False), verdict='kernel', value=lambda totals: {'loss': float(totals[-1])},
         more=lambda grads, ref: {},
         envs={'plain': ('slb_plain', {}), 'ssim': ('slb_ssim', {'ssim_weight': 0.2})}, settings={'ssim_weight': 0.2},
         difference='added_ms_per_update', update_verdict='added_is_more_than_the_spread', two_sided=False,
@@ -193,7 +211,7 @@ LOSSES = {
         shapes=PLANE_SHAPES, inputs=one_pair, kernel=lap_kernel, module=lambda: losses.LapLoss(LEVELS), call=lambda m, pm, g: m(pm[0], g),
         torch=lambda pt, g: losses._lap_terms(pt[0], g, LEVELS)[0].to(torch.float32),
         head=lambda name, shape, reps, preds, g: planes_head(name, shape, reps, levels=LEVELS),
-        rates=lambda n, ms: pixel_rates(n, ms, True), verdict='kernel', value=lambda totals: {'loss': float(totals[-1])},
+        rates=lambda g, ms: pixel_rates(g.numel(), ms, True), verdict='kernel', value=lambda totals: {'loss': float(totals[-1])},
         # (both exact: no word should differ)
         more=lambda grads, ref: {'grad_words_differing_from_torch_autograd': int((grads[0].view(torch.int32) != ref[0].view(torch.int32)).sum())},
         envs={'plain': ('llb_plain', {}), 'lap': ('llb_lap', {'lap_weight': 0.5, 'lap_levels': LEVELS})},
@@ -212,6 +230,18 @@ LOSSES = {
         settings={'temporal_weight': 0.5, 'kind': 'charbonnier'},
         difference='temporal_minus_plain_ms', update_verdict='difference_is_more_than_the_spread', two_sided=True,
         errors=('G_temporal', ('G_temporal', 'G_temporal_forward', 'G_temporal_backward'))),
+    'census': SimpleNamespace(
+        shapes=(('TAI_gray 32 clips x 5, pred time-major', CLIP_SHAPES[0][1]), CLIP_SHAPES[1]), inputs=three_against_one,
+        kernel=census_kernel, module=losses.CensusLoss, call=sum_of_three,
+        torch=lambda pt, g: sum(losses._census_terms(p, g)[0] for p in pt),
+        head=lambda name, shape, reps, preds, g: {'shape': name, 'dims': list(shape), 'npred': NPRED, 'reps': reps,
+                                                  'strides': [list(losses._block_strides(t)) for t in preds + [g]]},
+        rates=census_rates, verdict='module', value=lambda totals: {'losses': [float(x) for x in totals]},
+        more=lambda grads, ref: {},
+        envs={'plain': ('clb_plain', {}), 'census': ('clb_census', {'census_weight': 0.5})},
+        settings={'census_weight': 0.5},
+        difference='census_minus_plain_ms', update_verdict='difference_is_more_than_the_spread', two_sided=True,
+        errors=('G_census', ('G_census', 'G_census_forward', 'G_census_backward'))),
 }
 
 
@@ -255,7 +285,7 @@ def launch_lines(which, reps, out_path):
         emit({'metric': which + '_loss_launch', **loss.head(name, shape, reps, preds, g),
               'library_version': _native.lib().tai_sepconv_version(), 'workspace_bytes': ws_bytes,
               'ms_medians': {k: [round(x, 4) for x in v] for k, v in meds.items()}, 'ms': {k: round(v, 4) for k, v in ms.items()},
-              'spread_ms': round(spread, 4), **loss.rates(g.numel(), ms['kernel']),
+              'spread_ms': round(spread, 4), **loss.rates(g, ms['kernel']),
               'torch_over_kernel': round(ms['torch'] / ms['kernel'], 2), 'torch_over_module': round(ms['torch'] / ms['module'], 2),
               loss.verdict + '_faster_than_torch_by_more_than_the_spread': bool(ms['torch'] - ms[loss.verdict] > spread),
               **loss.value(totals), 'grad_max': scale, 'grad_max_diff_to_torch_autograd': diff, **loss.more(grads, [p.grad for p in pt])},
@@ -301,7 +331,7 @@ def update_lines(which, updates, out_path, module_ms):
           'ms': {k: round(v, 3) for k, v in ms.items()}, 'spread_ms': round(spread, 3),
           loss.difference: round(added, 3), 'ratio': round(ms[term] / ms[base], 4),
           loss.update_verdict: bool((abs(added) if loss.two_sided else added) > spread),
-          **({'module_alone_ms_at_this_shape': None if alone is None else round(alone, 4)} if which == 'temporal' else {}),
+          **({'module_alone_ms_at_this_shape': None if alone is None else round(alone, 4)} if which in ('temporal', 'census') else {}),
           field: [round(errs[k], 5) for k in keys]}, out_path)
 
 

@@ -37,6 +37,11 @@ frame-to-frame differences of prediction and ground truth over the gap and its t
 losses and gradients of all predictions, each read in its own layout); printed lines gain ``G_temporal=`` (and ``G_temporal_forward=
 G_temporal_backward=`` for TAI).  0 = off.
 
+``--census_weight G``: the generator's loss gains G times the census (soft ternary) term of each prediction (losses.CensusLoss: per
+pixel, how it relates to its 7x7 neighbours, compared between prediction and ground truth, so a brightness offset costs nothing; one HIP
+launch per update writes the losses and gradients of all predictions, each read in its own layout); printed lines gain ``G_census=`` (and
+``G_census_forward= G_census_backward=`` for TAI).  0 = off.
+
 ``--image_loss {l2,l1,charbonnier}`` (default ``l2`` = the reference's MSELoss + GDL, untouched): with ``l1`` or ``charbonnier``
 (``--charbonnier_eps E``, default 1e-3) the pointwise term of alpha (Lp + GDL) becomes mean |d| or mean sqrt(d^2 + E^2) for every
 prediction; Lp and GDL then come from losses.ImageLoss, one HIP launch per update for the losses and gradients of all predictions.  The
@@ -83,6 +88,8 @@ def main(args=None):
         raise SystemExit('--temporal_weight must not be negative, found %r' % opt.temporal_weight)
     if not (opt.temporal_eps > 0.0 and opt.temporal_eps != float('inf')):
         raise SystemExit('--temporal_eps must be finite and > 0, found %r' % opt.temporal_eps)
+    if not (opt.census_weight >= 0.0 and opt.census_weight != float('inf')):
+        raise SystemExit('--census_weight must be finite and not negative, found %r' % opt.census_weight)
     if not opt.resumable:
         return _run(opt, None)
     if opt.graph_step and GRAPH_STEP_REFUSAL:
@@ -164,7 +171,7 @@ def _run(opt, stop):
                                       ema_decay=opt.ema_decay, max_iter=opt.max_iter, ssim_weight=opt.ssim_weight,
                                       image_loss=opt.image_loss, charbonnier_eps=opt.charbonnier_eps,
                                       lap_weight=opt.lap_weight, lap_levels=opt.lap_levels, temporal_weight=opt.temporal_weight,
-                                      temporal_kind=opt.temporal_kind, temporal_eps=opt.temporal_eps)
+                                      temporal_kind=opt.temporal_kind, temporal_eps=opt.temporal_eps, census_weight=opt.census_weight)
     env.sync_replicas()
     total_updates = env.start_update
     # a resumed run starts from the best values its snapshot carries (train.py:96-97)

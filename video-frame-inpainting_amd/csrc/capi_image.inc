@@ -3,7 +3,7 @@
 // one workgroup per tile or chunk up to the kernel's GRID_CAP; past it a workgroup strides
 static dim3 capped_grid(long long work, long long cap) { return dim3((unsigned)(work < cap ? work : cap)); }
 
-// the pred[] / grad[] tables of imgloss::Args and temploss::Args: the caller's npred entries, null behind them and for every map
+// the pred[] / grad[] tables of imgloss::Args, temploss::Args and censusloss::Args: the caller's npred entries, null behind them and for every map
 // when the caller passes no table
 template <typename A>
 static void fill_tables(A& a, const float* const* preds, float* const* grads, int npred) {
@@ -173,6 +173,44 @@ int tai_temporal_loss(const float* const* preds, int npred, const float* gt, con
     if (int rc = check_launch("temporal_loss finish_sequences")) return rc;
     hipLaunchKernelGGL(temploss::finish_total, dim3((unsigned)npred), dim3(temploss::THREADS), 0, s, seq_terms, totals, S, T + 1, n_pos, count);
     return check_launch("temporal_loss finish_total");
+}
+
+long long tai_census_loss_workspace_bytes(int npred, int B, int T, int C, int H, int W) {
+    if (censusloss::refusal(npred, B, T, C, H, W)) return TAI_SEPCONV_EINVAL;
+    return npred * censusloss::plan(B, T, H, W).tiles_total * (long long)sizeof(double);
+}
+
+int tai_census_loss(const float* const* preds, int npred, const float* gt, const long long* strides, double* frame_terms, double* totals,
+                    float* const* grads, void* workspace, int B, int T, int C, int H, int W, void* stream) {
+    g_err[0] = 0;
+    if (const char* why = censusloss::call_refusal(preds, npred, gt, strides, frame_terms, totals, workspace, B, T, C, H, W))
+        return fail(TAI_SEPCONV_EINVAL, "%s", why);
+    const censusloss::Plan pl = censusloss::plan(B, T, H, W);
+    censusloss::Args a;
+    fill_tables(a, preds, grads, npred);
+    for (int i = 0; i < censusloss::MAXP; ++i) {
+        a.sb[i] = i < npred ? strides[2 * i] : 0;
+        a.st[i] = i < npred ? strides[2 * i + 1] : 0;
+    }
+    a.gt = gt;
+    a.sb[censusloss::MAXP] = strides[2 * npred];
+    a.st[censusloss::MAXP] = strides[2 * npred + 1];
+    a.part = static_cast<double*>(workspace);
+    a.npred = npred; a.T = T; a.C = C; a.H = H; a.W = W; a.nby = pl.nby; a.nbx = pl.nbx;
+    a.tiles_total = pl.tiles_total;
+    const double interior = (double)(H - 6) * (double)(W - 6);                 // integers below 2^31 and 2^62 / 2^11: exact
+    const double count = (double)pl.frames * interior;
+    a.kappa = (255.0 * 0.5) / (49.0 * count);
+    const long long rows = npred * pl.frames;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    hipLaunchKernelGGL(C == 1 ? censusloss::tile_loss_grad<1> : censusloss::tile_loss_grad<3>, capped_grid(pl.tiles_total, censusloss::GRID_CAP),
+                       dim3(censusloss::THREADS), 0, s, a);
+    if (int rc = check_launch("census_loss tile_loss_grad")) return rc;
+    hipLaunchKernelGGL(censusloss::finish_frames, dim3((unsigned)((rows + censusloss::THREADS - 1) / censusloss::THREADS)),
+                       dim3(censusloss::THREADS), 0, s, a.part, frame_terms, rows, pl.nby * pl.nbx, interior);
+    if (int rc = check_launch("census_loss finish_frames")) return rc;
+    hipLaunchKernelGGL(censusloss::finish_total, dim3((unsigned)npred), dim3(censusloss::THREADS), 0, s, frame_terms, totals, pl.frames);
+    return check_launch("census_loss finish_total");
 }
 
 int tai_clip_from_frames(const unsigned char* frames, long long frames_bytes, const long long* table, const long long* table_host,

@@ -1,5 +1,6 @@
-// What the metric and loss kernels share (frame_metrics, ssim_loss, image_loss, lap_loss, temporal_loss; each includes this file
-// itself): force-inlined device helpers only, so a kernel's code is what it was with the helper written out in its own file.
+// What the metric and loss kernels share (frame_metrics, ssim_loss, image_loss, lap_loss, temporal_loss, census_loss; each includes this
+// file itself): force-inlined device helpers, so a kernel's code is what it was with the helper written out in its own file, and one host
+// check (block_strides_fault) of the two launchers that read [B, T, C, H, W] tensors where they lie.
 #pragma once
 
 namespace losscommon {
@@ -37,6 +38,36 @@ __device__ __forceinline__ void rho_drho(int kind, float d, float e2, float& rho
         rho = __builtin_sqrtf(d * d + e2);
         drho = d / rho;
     }
+}
+
+// One tensor's batch and time strides (temporal_loss, census_loss): 0 when they are positive, every element's offset is below 2^40 and no
+// two of the B x T blocks of chw elements overlap; else which of the three fails.  Two blocks overlap when |db * sb + dt * st| < chw for
+// some (db, dt) != (0, 0): for every db of the shorter axis the dt nearest to -db * sb / st is looked at (the distance is monotone in dt
+// on either side of it).
+enum { STRIDES_OK = 0, STRIDES_NOT_POSITIVE, STRIDES_REACH_2_40, STRIDES_OVERLAP };
+
+inline int block_strides_fault(long long sb, long long st, int B, int T, long long chw) {
+    if (sb < 1 || st < 1) return STRIDES_NOT_POSITIVE;
+    const long long lim = 1LL << 40;
+    if (sb >= lim || st >= lim || (B > 1 && sb > (lim - chw) / (B - 1)) || (T > 1 && st > (lim - chw) / (T - 1)) ||
+        (long long)(B - 1) * sb + (long long)(T - 1) * st + chw > lim)
+        return STRIDES_REACH_2_40;
+    long long sa = sb, so = st;            // sa: the stride of the shorter axis, looped over
+    int na = B, no = T;
+    if (T < B) { sa = st; so = sb; na = T; no = B; }
+    for (long long da = 0; da < na; ++da) {
+        const long long base = da * sa;    // < 2^40
+        long long k = -(base / so);        // the multiples of `so` on either side of -base
+        for (int side = 0; side < 2; ++side, --k) {
+            long long dt = k;
+            if (dt < -(long long)(no - 1)) dt = -(long long)(no - 1);
+            if (dt > (long long)(no - 1)) dt = (long long)(no - 1);
+            if (da == 0 && dt == 0) continue;
+            const long long dist = base + dt * so;
+            if ((dist < 0 ? -dist : dist) < chw) return STRIDES_OVERLAP;
+        }
+    }
+    return STRIDES_OK;
 }
 
 }  // namespace losscommon

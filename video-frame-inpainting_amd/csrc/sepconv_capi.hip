@@ -36,6 +36,7 @@
 #include "image_loss.hip.inc"
 #include "lap_loss.hip.inc"
 #include "temporal_loss.hip.inc"
+#include "census_loss.hip.inc"
 #include "clip_pipeline.hip.inc"
 #include "state_digest.hip.inc"
 #include "grad_stats.hip.inc"
@@ -141,7 +142,7 @@ void wino_div_magic(long long d, unsigned& m, unsigned& sh) {
 
 extern "C" {
 
-int tai_sepconv_version(void) { return 840; }
+int tai_sepconv_version(void) { return 850; }
 
 const char* tai_sepconv_last_error(void) { return g_err; }
 

@@ -220,29 +220,12 @@ inline const char* refusal(int npred, int B, int T, int C, int H, int W) {
     return nullptr;
 }
 
-// One tensor's strides: positive, every element's offset below 2^40, and no two of the B x T blocks of chw elements overlapping.  Two
-// blocks overlap when |db * sb + dt * st| < chw for some (db, dt) != (0, 0): for every db of the shorter axis the dt nearest to
-// -db * sb / st is looked at (the distance is monotone in dt on either side of it).
+// One tensor's strides (losscommon::block_strides_fault), in this entry's words.
 inline const char* stride_refusal(long long sb, long long st, int B, int T, long long chw) {
-    if (sb < 1 || st < 1) return "temporal_loss: strides must be positive";
-    const long long lim = 1LL << 40;
-    if (sb >= lim || st >= lim || (B > 1 && sb > (lim - chw) / (B - 1)) || (T > 1 && st > (lim - chw) / (T - 1)) ||
-        (long long)(B - 1) * sb + (long long)(T - 1) * st + chw > lim)
-        return "temporal_loss: strides reach an offset of 2^40 elements or more";
-    long long sa = sb, so = st;            // sa: the stride of the shorter axis, looped over
-    int na = B, no = T;
-    if (T < B) { sa = st; so = sb; na = T; no = B; }
-    for (long long da = 0; da < na; ++da) {
-        const long long base = da * sa;    // < 2^40
-        long long k = -(base / so);        // the multiples of `so` on either side of -base
-        for (int side = 0; side < 2; ++side, --k) {
-            long long dt = k;
-            if (dt < -(long long)(no - 1)) dt = -(long long)(no - 1);
-            if (dt > (long long)(no - 1)) dt = (long long)(no - 1);
-            if (da == 0 && dt == 0) continue;
-            const long long dist = base + dt * so;
-            if ((dist < 0 ? -dist : dist) < chw) return "temporal_loss: strides under which two (b, t) blocks overlap";
-        }
+    switch (block_strides_fault(sb, st, B, T, chw)) {
+        case STRIDES_NOT_POSITIVE: return "temporal_loss: strides must be positive";
+        case STRIDES_REACH_2_40: return "temporal_loss: strides reach an offset of 2^40 elements or more";
+        case STRIDES_OVERLAP: return "temporal_loss: strides under which two (b, t) blocks overlap";
     }
     return nullptr;
 }

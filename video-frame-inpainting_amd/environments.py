@@ -23,7 +23,7 @@ import torch
 from . import conv_ops, parallel, run_state
 from . import fused_step as fused_step_module
 from .graph import GraphedForward
-from .losses import GDL, IMAGE_LOSS_KINDS, ImageLoss, LapLoss, SSIMLoss, TemporalLoss
+from .losses import GDL, IMAGE_LOSS_KINDS, CensusLoss, ImageLoss, LapLoss, SSIMLoss, TemporalLoss
 from .mcnet import MCNetFillInModel
 from .sn_discriminator import SNDiscriminator
 from .ablations import (BidirectionalSimpleAverageFillInModel, BidirectionalTimeWeightedAverageFillInModel,
@@ -47,7 +47,7 @@ def create_training_environment(fill_in_model, c_dim, checkpoints_dir, name, max
                                 beta, lr, beta1, df_dim, Ip, disc_window_size, padding_size, device=None, graph_step=False,
                                 resumable=False, guard=None, fused_step=False, ema_decay=None, max_iter=100000, ssim_weight=0.0,
                                 image_loss='l2', charbonnier_eps=1e-3, lap_weight=0.0, lap_levels=5, temporal_weight=0.0,
-                                temporal_kind='charbonnier', temporal_eps=1e-3):
+                                temporal_kind='charbonnier', temporal_eps=1e-3, census_weight=0.0):
     if not ssim_weight >= 0.0:
         raise ValueError('ssim_weight must not be negative, found %r' % (ssim_weight,))
     if not lap_weight >= 0.0:
@@ -62,6 +62,8 @@ def create_training_environment(fill_in_model, c_dim, checkpoints_dir, name, max
         raise ValueError('temporal_kind must be one of %s, found %r' % (', '.join(IMAGE_LOSS_KINDS), temporal_kind))
     if not (temporal_eps > 0.0 and temporal_eps != float('inf')):
         raise ValueError('temporal_eps must be finite and > 0, found %r' % (temporal_eps,))
+    if not (census_weight >= 0.0 and census_weight != float('inf')):
+        raise ValueError('census_weight must be finite and not negative, found %r' % (census_weight,))
     if guard is not None and graph_step:
         raise ValueError('a guarded update cannot be a captured one: a replayed update cannot leave out an optimizer step')
     if fused_step and graph_step:
@@ -76,13 +78,15 @@ def create_training_environment(fill_in_model, c_dim, checkpoints_dir, name, max
                                      df_dim, Ip, disc_window_size, max_K, max_T, max_F, padding_size, device=device,
                                      graph_step=graph_step, ssim_weight=ssim_weight, image_loss=image_loss,
                                      charbonnier_eps=charbonnier_eps, lap_weight=lap_weight, lap_levels=lap_levels,
-                                     temporal_weight=temporal_weight, temporal_kind=temporal_kind, temporal_eps=temporal_eps)
+                                     temporal_weight=temporal_weight, temporal_kind=temporal_kind, temporal_eps=temporal_eps,
+                                     census_weight=census_weight)
     elif isinstance(fill_in_model, MCNetFillInModel):
         env = MCNetTrainingEnvironment(fill_in_model, checkpoints_dir, name, image_size, c_dim, alpha, beta, lr, beta1,
                                        df_dim, Ip, disc_window_size, max_K, max_T, max_F, padding_size, device=device,
                                        graph_step=graph_step, ssim_weight=ssim_weight, image_loss=image_loss,
                                      charbonnier_eps=charbonnier_eps, lap_weight=lap_weight, lap_levels=lap_levels,
-                                     temporal_weight=temporal_weight, temporal_kind=temporal_kind, temporal_eps=temporal_eps)
+                                     temporal_weight=temporal_weight, temporal_kind=temporal_kind, temporal_eps=temporal_eps,
+                                     census_weight=census_weight)
     else:
         raise RuntimeError('Tried to create a training environment for object of unsupported type %s'
                            % type(fill_in_model).__name__)
@@ -285,7 +289,7 @@ class BaseTrainingEnvironment(BaseVideoFillInEnvironment):
     # before a capture ends, and one that is missing outlives the capture and faults the HIP runtime when it is closed
     _STEP_OUTPUTS = ('gen_output', 'loss_G', 'Lp', 'gdl', 'L_GAN', 'loss_d_fake', 'loss_d_real', 'loss_D', 'Lp_forward',
                      'Lp_backward', 'gdl_forward', 'gdl_backward', 'ssim', 'ssim_forward', 'ssim_backward', 'lap', 'lap_forward', 'lap_backward',
-                     'temporal', 'temporal_forward', 'temporal_backward')
+                     'temporal', 'temporal_forward', 'temporal_backward', 'census', 'census_forward', 'census_backward')
 
     def train_step(self, preceding_frames, following_frames, gt_middle_frames):
         """One update on a batch: set_train_inputs + forward_train + optimize_parameters (src/train.py:147-169), with
@@ -496,7 +500,8 @@ class L2GDLDiscTrainingEnvironment(BaseTrainingEnvironment):
 
     def __init__(self, fill_in_model, checkpoints_dir, name, image_size, c_dim, alpha, beta, lr, beta1, df_dim, Ip,
                  disc_t, max_K, max_T, max_F, padding_size, device=None, graph_step=False, ssim_weight=0.0, image_loss='l2',
-                 charbonnier_eps=1e-3, lap_weight=0.0, lap_levels=5, temporal_weight=0.0, temporal_kind='charbonnier', temporal_eps=1e-3):
+                 charbonnier_eps=1e-3, lap_weight=0.0, lap_levels=5, temporal_weight=0.0, temporal_kind='charbonnier', temporal_eps=1e-3,
+                 census_weight=0.0):
         super().__init__(fill_in_model, checkpoints_dir, name, lr, beta1, max_K, max_T, max_F, padding_size, device=device,
                          graph_step=graph_step)
         # ssim_weight (train.py --ssim_weight G) > 0: loss_G gains G (1 - mean SSIM) per prediction (losses.SSIMLoss, one HIP launch for
@@ -516,6 +521,11 @@ class L2GDLDiscTrainingEnvironment(BaseTrainingEnvironment):
         # time-major view and is not copied); 0 = no module, no launch, no extra key
         self.temporal_weight = float(temporal_weight)
         self.loss_temporal = TemporalLoss(temporal_kind, temporal_eps) if self.temporal_weight > 0 else None
+        # census_weight (train.py --census_weight G) > 0: loss_G gains G times the census (soft ternary) term of every prediction
+        # (losses.CensusLoss: one HIP launch for all predictions of an update, each read in its own layout); 0 = no module, no launch, no
+        # extra key
+        self.census_weight = float(census_weight)
+        self.loss_census = CensusLoss() if self.census_weight > 0 else None
         self._fake_labels = {}
         self.loss_Lp = torch.nn.MSELoss()
         self.loss_gdl = GDL()
@@ -631,6 +641,14 @@ class L2GDLDiscTrainingEnvironment(BaseTrainingEnvironment):
             self.temporal = temporal[0]
             self.loss_G = self.loss_G + self.temporal_weight * self.temporal
             self._add_further_temporal_losses(temporal[1:])
+        if self.loss_census is not None:
+            census = self.loss_census(tuple(self.gen_output[k] for k in self._IMAGE_LOSS_KEYS), self.gt_middle_frames)
+            self.census = census[0]
+            self.loss_G = self.loss_G + self.census_weight * self.census
+            self._add_further_census_losses(census[1:])
+
+    def _add_further_census_losses(self, losses):
+        """The census terms of ``_IMAGE_LOSS_KEYS[1:]`` (they came from the same launch as ``pred``'s): none here."""
 
     def _add_further_temporal_losses(self, losses):
         """The temporal terms of ``_IMAGE_LOSS_KEYS[1:]`` (they came from the same launch as ``pred``'s): none here."""
@@ -649,6 +667,8 @@ class L2GDLDiscTrainingEnvironment(BaseTrainingEnvironment):
             d['G_lap'] = float(self.lap.item())
         if self.loss_temporal is not None:
             d['G_temporal'] = float(self.temporal.item())
+        if self.loss_census is not None:
+            d['G_census'] = float(self.census.item())
         return d
 
     def train(self):
@@ -705,6 +725,10 @@ class TAITrainingEnvironment(L2GDLDiscTrainingEnvironment):
         self.temporal_forward, self.temporal_backward = losses
         self.loss_G = self.loss_G + self.temporal_weight * (self.temporal_forward + self.temporal_backward)
 
+    def _add_further_census_losses(self, losses):
+        self.census_forward, self.census_backward = losses
+        self.loss_G = self.loss_G + self.census_weight * (self.census_forward + self.census_backward)
+
     def get_current_errors(self):
         d = super().get_current_errors()
         d.update({'G_Lp_forward': float(self.Lp_forward.item()), 'G_gdl_forward': float(self.gdl_forward.item()),
@@ -715,4 +739,6 @@ class TAITrainingEnvironment(L2GDLDiscTrainingEnvironment):
             d.update({'G_lap_forward': float(self.lap_forward.item()), 'G_lap_backward': float(self.lap_backward.item())})
         if self.loss_temporal is not None:
             d.update({'G_temporal_forward': float(self.temporal_forward.item()), 'G_temporal_backward': float(self.temporal_backward.item())})
+        if self.loss_census is not None:
+            d.update({'G_census_forward': float(self.census_forward.item()), 'G_census_backward': float(self.census_backward.item())})
         return d

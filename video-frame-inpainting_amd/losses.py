@@ -1,6 +1,6 @@
 """Image gradient difference loss (reference src/losses/losses.py:4-44, Mathieu et al.), and this build's opt-in losses: SSIMLoss
-(train.py --ssim_weight), ImageLoss (train.py --image_loss l1 / charbonnier), LapLoss (train.py --lap_weight) and TemporalLoss
-(train.py --temporal_weight), each a written definition with a HIP kernel behind it."""
+(train.py --ssim_weight), ImageLoss (train.py --image_loss l1 / charbonnier), LapLoss (train.py --lap_weight), TemporalLoss
+(train.py --temporal_weight) and CensusLoss (train.py --census_weight), each a written definition with a HIP kernel behind it."""
 import collections
 
 import torch
@@ -107,7 +107,7 @@ def _kind_and_eps(name, kind, eps):
 
 
 def _predictions(name, preds):
-    """(single, tuple of 1-3 predictions) of what ImageLoss and TemporalLoss take: one tensor or a tuple."""
+    """(single, tuple of 1-3 predictions) of what ImageLoss, TemporalLoss and CensusLoss take: one tensor or a tuple."""
     single = torch.is_tensor(preds)
     preds = (preds,) if single else tuple(preds)
     if not 1 <= len(preds) <= 3:
@@ -373,7 +373,8 @@ def _temporal_terms(pred, gt, kind, eps):
 
 
 def _block_strides(t):
-    """(batch stride, time stride) in elements if ``t`` [B, T, C, H, W] can be read where it lies by ``tai_temporal_loss``: every
+    """(batch stride, time stride) in elements if ``t`` [B, T, C, H, W] can be read where it lies by ``tai_temporal_loss`` and
+    ``tai_census_loss``: every
     [C, H, W] block dense, the (b, t) blocks apart from each other with one axis nested in the other; else None."""
     B, T, C, H, W = t.shape
     sb, st, sc, sh, sw = t.stride()
@@ -440,5 +441,82 @@ class TemporalLoss(nn.Module):
                 terms.append(tm.detach().to(p.dtype))
                 seqs.append(sq.detach())
             self.last_terms, self.seq_terms = torch.stack(terms), torch.stack(seqs)
+            out = tuple(out)
+        return out[0] if single else out
+
+
+_CENSUS_GRAY = (0.1140, 0.5870, 0.2989)         # util.gray01's weights, in its operand order
+
+
+def _census_terms(pred, gt):
+    """(loss, frame_terms [B * T]) in float64 by torch ops, differentiable by autograd: the definition of ``tai_census_loss``
+    (include/tai_sepconv.h) with the range map in the tensors' own precision and everything behind it in float64 (the constants are the
+    definition's fp32 ones, widened)."""
+    B, T, C, H, W = pred.shape
+    f = lambda v: float(torch.tensor(v, dtype=torch.float32))
+
+    def gray(frames):
+        x = ((frames + 1) / 2).double()                           # util.inverse_transform, not clipped
+        if C == 1:
+            return x[:, :, 0]
+        return (f(_CENSUS_GRAY[0]) * x[:, :, 0] + f(_CENSUS_GRAY[1]) * x[:, :, 1]) + f(_CENSUS_GRAY[2]) * x[:, :, 2]
+
+    def soft_sign(I, dy, dx):                                     # t of every interior pixel for one offset
+        s = 255.0 * (I[:, :, 3 + dy:H - 3 + dy, 3 + dx:W - 3 + dx] - I[:, :, 3:H - 3, 3:W - 3])
+        return s / torch.sqrt(f(0.81) + s * s)
+    I, J = gray(pred), gray(gt)
+    phi_sum = None
+    for dy in range(-3, 4):
+        for dx in range(-3, 4):
+            if dy == 0 and dx == 0:
+                continue
+            d = soft_sign(I, dy, dx) - soft_sign(J, dy, dx)
+            e = d * d
+            phi = e / (f(0.1) + e)
+            phi_sum = phi if phi_sum is None else phi_sum + phi
+    frame_terms = (phi_sum / 49.0).sum(dim=(2, 3)).reshape(B * T) / float((H - 6) * (W - 6))
+    return frame_terms.sum() / float(B * T), frame_terms
+
+
+class CensusLoss(nn.Module):
+    """Census (soft ternary) loss of 1-3 predictions ``[B, T, C, H, W]`` (C 1 or 3; H, W >= 7) against one target, the definition of
+    ``tai_census_loss`` (include/tai_sepconv.h): frames mapped to [0, 1] as ``inverse_transform`` does and NOT clipped, gray for C = 3; per
+    interior pixel and each of its 48 neighbours in the 7x7 window the softened sign t = s / sqrt(0.81 + s^2) of the 255-scaled intensity
+    difference s, and the distance d^2 / (0.1 + d^2) between prediction's and target's t, averaged over the window's 49 positions, the
+    interior and the frames.  A constant added to a frame changes no difference, so it costs nothing.  ``forward(preds, target)`` takes one
+    tensor or a tuple of 1-3 and returns one scalar per prediction (a tuple for a tuple).  CUDA fp32 tensors go through ONE launch of the
+    HIP kernel for all predictions, which reads every tensor in its own layout and writes the losses and their gradient maps; anything
+    else (CPU, float64) evaluates the same definition with torch ops in float64 and is differentiated by autograd.  ``frame_terms`` keeps
+    the last call's per-frame means [n, B * T] (float64), detached.  No parameters, no buffers."""
+
+    def __init__(self):
+        super().__init__()
+        self.frame_terms = None
+
+    def forward(self, preds, target):
+        single, preds = _predictions('CensusLoss', preds)
+        for p in preds:
+            if p.shape != target.shape or p.dim() != 5:
+                raise ValueError('CensusLoss: prediction %s and target %s must have one shape [B, T, C, H, W]'
+                                 % (tuple(p.shape), tuple(target.shape)))
+        B, T, C, H, W = target.shape
+        if C not in (1, 3) or H < 7 or W < 7 or target.numel() == 0:
+            raise ValueError('CensusLoss: needs at least one frame, C in {1, 3} and H, W >= 7 (the 7x7 window), got %s' % (tuple(target.shape),))
+        if all(t.is_cuda and t.dtype == torch.float32 for t in preds + (target,)):
+            n = len(preds)
+            call = _Call('tai_census_loss', (n, B, T, C, H, W),
+                         ('CensusLoss: %d predictions of %s are outside what tai_census_loss takes', (n, tuple(target.shape))), n * B * T, n,
+                         lambda ps, g, frames, totals, ms, ws, strides: (ps, n, g, strides, frames, totals, ms, ws, B, T, C, H, W),
+                         lambda frames, totals: (totals.to(torch.float32), frames.view(n, B * T)), table=True, strided=True)
+            losses, frames = _FusedLoss.apply(call, torch.is_grad_enabled(), target, *preds)
+            self.frame_terms = frames.detach()
+            out = tuple(losses[i] for i in range(n))
+        else:
+            out, frames = [], []
+            for p in preds:
+                loss, ft = _census_terms(p, target.to(device=p.device, dtype=p.dtype))
+                out.append(loss.to(p.dtype))
+                frames.append(ft.detach())
+            self.frame_terms = torch.stack(frames)
             out = tuple(out)
         return out[0] if single else out

@@ -162,6 +162,13 @@ class TrainOptions(BaseOptions):
                             'charbonnier (default) = sqrt(d^2 + eps^2) (--temporal_eps)')
         g.add_argument('--temporal_eps', type=float, default=1e-3, metavar='E',
                        help='(this build, with --temporal_kind charbonnier) the eps of sqrt(d^2 + eps^2); finite and > 0')
+        g.add_argument('--census_weight', type=float, default=0.0, metavar='G',
+                       help="(this build) add G times the census (soft ternary) term of every prediction to the generator's loss "
+                            '(losses.CensusLoss: per pixel, the softened signs of its differences to the 48 neighbours of its 7x7 window, '
+                            'compared between prediction and ground truth on gray frames in [0, 1], unclipped, so a brightness offset '
+                            'costs nothing; losses and gradients of all predictions from one HIP launch, tai_census_loss, on the '
+                            'model\'s own layouts); printed lines gain G_census= (TAI: G_census_forward= G_census_backward= as well).  '
+                            '0 (default) = the loss as before: nothing is launched, no key is added')
         g.add_argument('--max_wall_minutes', type=float, default=None, metavar='M',
                        help='(this build, with --resumable) stop as after SIGTERM once the run has lasted M minutes')
         g.add_argument('--miopen_find_mode', type=str, default=None, choices=['NORMAL', 'FAST', 'HYBRID', 'DYNAMIC_HYBRID'],
