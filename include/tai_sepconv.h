@@ -697,6 +697,48 @@ int tai_clip_from_frames(const unsigned char* frames, long long frames_bytes, co
 int tai_frames_to_uint8(const float* x, unsigned char* out, int N, int C, int Hs, int Ws, int h, int w, int reverse_channels,
                         void* hip_stream);
 
+/* The augmented way in (csrc/clip_augment.hip.inc; train.py --aug_crop / --aug_vflip / --aug_brightness / --aug_contrast / --aug_gamma /
+ * --aug_flicker, training clips only; tests/clip_augment_ref.py restates it in numpy; data._ClipReader.clip is the host path, bit-equal).
+ * tai_clip_from_frames_aug is tai_clip_from_frames with, per frame, a crop window, a top-bottom flip and a level table of its own.
+ *
+ * The definition, per clip of T frames with source size h x w and settings (SMIN, vflip, B, C, G, F):
+ *   draws     unit uniforms u_scale, u_top, u_left, u_vflip, u_gamma, u_gain, u_offset, then u_0 .. u_{T-1}, in this order, ALL of them
+ *             whenever any setting differs from its default (SMIN = 1, vflip off, B = C = G = F = 0), after the clip's window start,
+ *             mirror and reversal draws, from the same generator, before any frame is read;
+ *   crop      in float64: s = SMIN + u_scale (1 - SMIN); ch = max(1, floor(s h)); cw = max(1, floor(s w));
+ *             top = min(floor(u_top (h - ch + 1)), h - ch); left = min(floor(u_left (w - cw + 1)), w - cw); one window for the clip.
+ *             The window is resized to H x W by tai_clip_from_frames's definition (half-pixel centres, fp64, products and sums rounded one
+ *             by one, round half up) with the taps clamped to the WINDOW's edges: resize(frame[top:top+ch, left:left+cw]);
+ *   flips     after the resize: output (y, x) reads resized (H-1-y if vflip, W-1-x if mirror); vflip = the flag and u_vflip > 0.5;
+ *   levels    gamma = (1 + G)^(2 u_gamma - 1); g = 1 + C (2 u_gain - 1); d = B (2 u_offset - 1); e_t = F (2 u_t - 1) for the frame at
+ *             playback position t (after time reversal).  A level table per frame, float64 rounded once:
+ *             for q in 0..255: x = q / 255; if gamma != 1: x = x ** gamma; x = (x - 0.5) g + 0.5 + (d + e_t); x = min(max(x, 0), 1);
+ *             row 0[q] = fore_transform(float32(x)) = float32(x) * 2 - 1 in fp32; rows 1-3 = 0.1140, 0.5870, 0.2989 x row 0 in fp32
+ *             (clip_pipeline.augment_level_tables).  Neutral parameters give clip_pipeline.level_tables() bit for bit;
+ *   padding   rows >= H and columns >= W: level 0 of the NEUTRAL table, never augmented.
+ *
+ * The entry:
+ *   frames, frames_bytes, levels, out, N, c_dim, H, W, pad_h, pad_w   as tai_clip_from_frames; `levels` is the neutral table (padding);
+ *   table / table_host   device and host copy of N descriptors of NINE 64-bit integers
+ *               {0: byte offset of the frame in `frames`, 1: h, 2: w, 3: flags (bit 0 mirror, bit 1 vflip), 4: top, 5: left, 6: ch, 7: cw,
+ *                8: index of the frame's level table};
+ *   tables      device fp32 [n_tables][4][256], 16-byte aligned: one table per clip, or one per frame with flicker.
+ * out(y, x) for y < H, x < W: channel c = row 0 of the frame's table at the level of source channel 2 - c (c_dim 3), or
+ * (row 1[q_B] + row 2[q_G]) + row 3[q_R] (c_dim 1).  A frame's output depends on its own descriptor, table and pixels only.
+ * table_host is checked before anything is launched; the kernel re-checks each descriptor of the device copy before it forms an address
+ * (offset and sizes against frames_bytes, the window inside the frame, the table index below n_tables) and writes the padding level for
+ * every element of a frame whose descriptor fails.
+ * Caller-allocated buffers, no allocation, copy or synchronisation, asynchronous on the stream, capturable into a hipGraph.
+ * TAI_SEPCONV_EINVAL with a message, nothing launched: a null pointer; c_dim outside {1, 3}; non-positive N, H, W, frames_bytes or
+ * n_tables, negative padding; an index space of 2^31 output elements or more; tables not 16-byte aligned; a descriptor with a
+ * non-positive or oversized source size, one that points past frames_bytes, a window with ch or cw < 1, a window outside its frame, or a
+ * table index outside 0..n_tables-1.
+ * The last parameter is the HIP stream, spelled `stream` for the reason given at tai_temporal_loss; the refusals are pinned by
+ * tests/test_clip_augment_cpu.py. */
+int tai_clip_from_frames_aug(const unsigned char* frames, long long frames_bytes, const long long* table, const long long* table_host,
+                             const float* tables, int n_tables, const float* levels, float* out, int N, int c_dim, int H, int W, int pad_h,
+                             int pad_w, void* stream /* the HIP stream */);
+
 /* A 64-bit digest of a training state where it lives (csrc/state_digest.hip.inc; video_frame_inpainting_amd/run_state.py builds the
  * table; no counterpart in the reference, whose snapshots carry no check).  On the raw 32-bit words, integer arithmetic modulo 2^64 only:
  *   mix(z): z += 0x9E3779B97F4A7C15; z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9; z = (z ^ (z >> 27)) * 0x94D049BB133111EB; z ^ (z >> 31)

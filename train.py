@@ -47,6 +47,12 @@ launch per update writes the losses and gradients of all predictions, each read 
 prediction; Lp and GDL then come from losses.ImageLoss, one HIP launch per update for the losses and gradients of all predictions.  The
 printed keys ``G_Lp= G_gdl=`` (``_forward``, ``_backward``) stay and carry the chosen terms.
 
+``--aug_crop SMIN --aug_vflip --aug_brightness B --aug_contrast C --aug_gamma G --aug_flicker F`` (all off by default): training clips
+are cropped to a random window, flipped top-bottom and changed photometrically per clip (and, with ``--aug_flicker``, per frame), by
+draws that follow a clip's window, mirror and reversal draws (data.ClipAugment; include/tai_sepconv.h at tai_clip_from_frames_aug).  The
+host path and ``--device_preprocess`` (one HIP launch, tai_clip_from_frames_aug) give the same bits; validation never augments; a
+``--resumable`` run records the settings and refuses a continuation with others.  Printed lines do not change.
+
   python train.py --name demo --K 5 --T 5 --F 5 --c_dim 1 --image_size 128 --batch_size 4 --model_key TAI_gray \
       --max_iter 10 --synthetic 64
 """
@@ -58,7 +64,7 @@ import torch
 
 import video_frame_inpainting_amd as vfi
 from video_frame_inpainting_amd import clip_pipeline, grad_guard, parallel, run_state, synthetic, tai
-from video_frame_inpainting_amd.data import ContiguousVideoClipDataset, ResumableBatchSampler
+from video_frame_inpainting_amd.data import ClipAugment, ContiguousVideoClipDataset, ResumableBatchSampler
 from video_frame_inpainting_amd.environments import create_training_environment
 from video_frame_inpainting_amd.options import TrainOptions
 from video_frame_inpainting_amd.validation import Validator
@@ -124,13 +130,14 @@ def _run(opt, stop):
     device = torch.device('cuda', local_rank)
     torch.cuda.set_device(device)
     H, W = opt.image_size[0] + opt.padding_size[0], opt.image_size[1] + opt.padding_size[1]
-    loader = None
+    loader, augment = None, None
     if getattr(opt, 'train_video_list_path', None) and not opt.synthetic:
         # --device_preprocess: the workers hand over raw uint8 frames and the GPU builds the (bit-identical) clip tensor
         on_device = bool(getattr(opt, 'device_preprocess', False))
+        augment = ClipAugment.from_options(opt)                      # the training dataset's alone; off = nothing is drawn
         dataset = ContiguousVideoClipDataset(opt.c_dim, opt.train_video_list_path, opt.K + opt.T + opt.F, not opt.no_backwards,
                                              not opt.no_flip, opt.image_size, True, opt.padding_size, seed=opt.seed + 7 * rank,
-                                             raw=on_device, rank=rank)
+                                             raw=on_device, rank=rank, augment=augment)
         collate = clip_pipeline.collate_for(opt.num_threads) if on_device else None
         sampler = None
         if resumable:
@@ -184,7 +191,8 @@ def _run(opt, stop):
     order = np.random.RandomState(opt.seed + 7 * rank)
     if resumable:
         if loader is not None:
-            env.data_state_source = sampler.state
+            # (the augmentation settings are part of what a position yields; recorded only when augmentation is on)
+            env.data_state_source = (lambda: dict(sampler.state(), augment=augment.state())) if augment.on else sampler.state
         else:
             env.data_state_source = lambda: {'kind': 'synthetic', 'n_clips': n_clips, 'batch_size': opt.batch_size, 'order': order.get_state()}
         if env.exact_resume:           # position the clip order where the snapshot left it (no draw from any other generator)
@@ -194,6 +202,7 @@ def _run(opt, stop):
                                    % (saved and saved.get('kind'),))
             if loader is not None:
                 sampler.load_state(saved)
+                augment.check_continues(saved.get('augment'))
             else:
                 if (saved['n_clips'], saved['batch_size']) != (n_clips, opt.batch_size):
                     raise RuntimeError('the snapshot was written with --synthetic %d --batch_size %d: it cannot be continued exactly'

@@ -10,6 +10,12 @@ header, source height, source width, flags with bit 0 = mirror; ``HEADER_ALIGN``
 clip in playback order.  Frames of one batch may differ in source size.  ``collate_raw`` never touches CUDA (DataLoader workers run
 it); the builder owns the pinned staging buffers, in the main process, and with a loader that has no workers (``collate_items``)
 it packs straight into them.
+
+Items that carry an augmentation record (``'aug'``; train.py --aug_*; data.ClipAugment) are packed by ``pack_clips_aug`` instead: the
+header holds ``AUG_DESC_INTS`` int64 per frame (offset, h, w, flags with bit 1 = vflip, then the crop window top, left, ch, cw and the
+index of the frame's level table), a section of fp32 [n_tables][4][256] level tables follows it (``augment_level_tables``: one table per
+clip, one per frame with flicker), then the frames; the batch gains ``'n_tables'`` and the builder launches ``tai_clip_from_frames_aug``
+for it.  Still ONE upload per batch, and nothing changes for a batch without records.
 """
 import numpy as np
 import torch
@@ -20,6 +26,9 @@ from .util import _GRAY_BGR, fore_transform
 HEADER_ALIGN = 256
 DESC_INTS = 4                     # int64 per frame: offset, h, w, flags
 FLAG_MIRROR = 1
+AUG_DESC_INTS = 9                 # int64 per frame of an augmented batch: offset, h, w, flags, top, left, ch, cw, table index
+FLAG_VFLIP = 2
+TABLE_BYTES = 4 * 256 * 4         # one fp32 [4][256] level table
 
 
 def level_tables():
@@ -28,6 +37,29 @@ def level_tables():
     level = fore_transform(torch.arange(256, dtype=torch.int64).to(torch.uint8).float().div(255))
     b, g, r = _GRAY_BGR
     return torch.stack([level, b * level, g * level, r * level]).contiguous()
+
+
+def augment_level_tables(gamma=1.0, gain=1.0, offsets=(0.0,)):
+    """float32 [len(offsets), 4, 256]: the level tables of frames whose levels go through x ** gamma, then gain about 0.5, then an
+    additive offset (include/tai_sepconv.h, tai_clip_from_frames_aug): float64 throughout, clamped to [0, 1], rounded ONCE to float32 and
+    only then mapped by the host path's own torch expressions, as ``level_tables`` forms its rows.  Neutral parameters (1, 1, 0) give
+    ``level_tables()`` bit for bit."""
+    x = np.arange(256, dtype=np.float64) / 255.0
+    if gamma != 1.0:
+        x = x ** np.float64(gamma)
+    x = (x - 0.5) * np.float64(gain) + 0.5
+    x = x[None, :] + np.asarray(offsets, dtype=np.float64)[:, None]
+    x = np.minimum(np.maximum(x, 0.0), 1.0)
+    level = fore_transform(torch.from_numpy(x.astype(np.float32)))
+    b, g, r = _GRAY_BGR
+    return torch.stack([level, b * level, g * level, r * level], dim=1).contiguous()
+
+
+def tables_of_record(aug):
+    """The level tables of one clip's augmentation record (data.ClipAugment.draw): [1, 4, 256] without flicker, [T, 4, 256] with it
+    (the offset of the frame at playback position t is offset + flicker[t])."""
+    flicker = aug['flicker']
+    return augment_level_tables(aug['gamma'], aug['gain'], [aug['offset']] if flicker is None else [aug['offset'] + e for e in flicker])
 
 
 def header_bytes(n_frames):
@@ -76,9 +108,84 @@ def pack_clips(clips, mirrors, out=None):
     return packed
 
 
+def aug_header_bytes(n_frames):
+    return -(-n_frames * AUG_DESC_INTS * 8 // HEADER_ALIGN) * HEADER_ALIGN
+
+
+def _aug_tables(clips, augs, T):
+    if len(augs) != len(clips):
+        raise ValueError('pack_clips_aug: %d clips, %d augmentation records' % (len(clips), len(augs)))
+    for a in augs:
+        if a['flicker'] is not None and len(a['flicker']) != T:
+            raise ValueError('pack_clips_aug: a clip of %d frames carries %d flicker offsets' % (T, len(a['flicker'])))
+    return [tables_of_record(a) for a in augs]
+
+
+def aug_packed_bytes(clips, augs):
+    """Bytes of the augmented packed form of these clips (header + level tables + frames)."""
+    T = clips[0].shape[0]
+    n_tables = sum(1 if a['flicker'] is None else len(a['flicker']) for a in augs)
+    return aug_header_bytes(len(clips) * T) + n_tables * TABLE_BYTES + sum(int(np.prod(c.shape)) for c in clips)
+
+
+def pack_clips_aug(clips, mirrors, augs, out=None):
+    """``pack_clips`` for clips with augmentation records (``augs``: one per clip, with 'window' = (top, left, ch, cw), 'vflip', 'gamma',
+    'gain', 'offset', 'flicker') -> (the packed uint8 tensor, n_tables): header of ``AUG_DESC_INTS`` int64 per frame, the level tables,
+    the frames.  No CUDA call."""
+    clips, T = _as_clips(clips)
+    tables = _aug_tables(clips, augs, T)
+    n = len(clips) * T
+    head = aug_header_bytes(n)
+    n_tables = sum(t.shape[0] for t in tables)
+    first = head + n_tables * TABLE_BYTES
+    need = first + sum(c.numel() for c in clips)
+    if out is None:
+        packed = torch.empty(need, dtype=torch.uint8)
+    else:
+        if out.dtype != torch.uint8 or out.dim() != 1 or out.numel() < need or not out.is_contiguous():
+            raise ValueError('pack_clips_aug: out must be a contiguous uint8 buffer of at least %d bytes' % need)
+        packed = out[:need]
+    packed[:head].zero_()
+    table = packed[:n * AUG_DESC_INTS * 8].view(torch.int64).view(n, AUG_DESC_INTS)
+    section = packed[head:first].view(torch.float32).view(n_tables, 4, 256)
+    offset, k = 0, 0
+    for i, (c, mirror, aug, tab) in enumerate(zip(clips, mirrors, augs, tables)):
+        _, h, w, _ = c.shape
+        top, left, ch, cw = (int(v) for v in aug['window'])
+        if not (0 <= top and 0 <= left and 1 <= ch and 1 <= cw and top + ch <= h and left + cw <= w):
+            raise ValueError('pack_clips_aug: the window %r lies outside a %d x %d frame' % ((top, left, ch, cw), h, w))
+        rows = table[i * T:(i + 1) * T]
+        rows[:, 0] = offset + torch.arange(T, dtype=torch.int64) * (h * w * 3)
+        rows[:, 1], rows[:, 2] = h, w
+        rows[:, 3] = (FLAG_MIRROR if mirror else 0) | (FLAG_VFLIP if aug['vflip'] else 0)
+        rows[:, 4], rows[:, 5], rows[:, 6], rows[:, 7] = top, left, ch, cw
+        rows[:, 8] = k + (torch.arange(T, dtype=torch.int64) if aug['flicker'] is not None else 0)
+        section[k:k + tab.shape[0]].copy_(tab)
+        k += tab.shape[0]
+        packed[first + offset:first + offset + c.numel()].view(c.shape).copy_(c)
+        offset += c.numel()
+    return packed, n_tables
+
+
+def _augs_of(items):
+    """The augmentation records of a batch's items, or None when it carries none (all items of a batch come from one dataset)."""
+    augs = [it.get('aug') for it in items]
+    if all(a is None for a in augs):
+        return None
+    if any(a is None for a in augs):
+        raise ValueError('a batch mixes items with and without an augmentation record')
+    return augs
+
+
 def collate_raw(items):
-    """DataLoader ``collate_fn`` for raw-mode items -> ``{'packed': uint8 [bytes], 'B': int, 'T': int, 'clip_label': [str]}``.
+    """DataLoader ``collate_fn`` for raw-mode items -> ``{'packed': uint8 [bytes], 'B': int, 'T': int, 'clip_label': [str]}``; items with
+    an augmentation record give the augmented packed form and ``'n_tables'`` beside it (the level tables are built here, in the worker).
     Ordinary memory, no CUDA call: this is what DataLoader workers run."""
+    augs = _augs_of(items)
+    if augs is not None:
+        packed, n_tables = pack_clips_aug([it['frames'] for it in items], [it['mirror'] for it in items], augs)
+        return {'packed': packed, 'n_tables': n_tables, 'B': len(items), 'T': int(items[0]['frames'].shape[0]),
+                'clip_label': [it['clip_label'] for it in items]}
     return {'packed': pack_clips([it['frames'] for it in items], [it['mirror'] for it in items]),
             'B': len(items), 'T': int(items[0]['frames'].shape[0]), 'clip_label': [it['clip_label'] for it in items]}
 
@@ -95,8 +202,10 @@ def collate_for(num_workers):
 
 
 def table_of(batch):
-    """The descriptor table of a packed batch: an int64 [B T, 4] view of its header."""
+    """The descriptor table of a packed batch: an int64 [B T, 4] view of its header ([B T, 9] for an augmented batch)."""
     n = batch['B'] * batch['T']
+    if 'n_tables' in batch:
+        return batch['packed'][:n * AUG_DESC_INTS * 8].view(torch.int64).view(n, AUG_DESC_INTS)
     return batch['packed'][:n * DESC_INTS * 8].view(torch.int64).view(n, DESC_INTS)
 
 
@@ -106,7 +215,8 @@ class _Slot(object):
 
 
 class DeviceClipBuilder(object):
-    """Packed raw batches -> model-ready clips on ``device`` (``tai_clip_from_frames``), on the current torch stream.
+    """Packed raw batches -> model-ready clips on ``device`` (``tai_clip_from_frames``; ``tai_clip_from_frames_aug`` for a batch that
+    carries augmentation records, and only for such a batch), on the current torch stream.
 
     Staging: two slots used in turn, each a pinned host buffer and a device buffer that grow to the largest batch seen.  ``build``
     copies (a packed batch from DataLoader workers) or packs (raw items from a loader without workers) the batch into the slot's
@@ -142,6 +252,8 @@ class DeviceClipBuilder(object):
         [B, T, C, H + pad_h, W + pad_w] on the device; asynchronous (the caller's stream orders its consumers)."""
         B, T = int(batch['B']), int(batch['T'])
         n = B * T
+        if 'n_tables' in batch or ('items' in batch and _augs_of(batch['items']) is not None):
+            return self._build_augmented(batch, B, T)
         head = header_bytes(n)
         (H, W), (ph, pw) = self.image_size, self.padding_size
         with torch.cuda.device(self.device):
@@ -163,6 +275,37 @@ class DeviceClipBuilder(object):
             # the descriptor table is validated on the host from the staging buffer's header before anything is launched
             _native.launch('tai_clip_from_frames', self.device, slot.dev.data_ptr() + head, nbytes - head, slot.dev, slot.host, self._levels,
                            out, n, self.c_dim, H, W, ph, pw)
+        return out
+
+
+    def _build_augmented(self, batch, B, T):
+        """``build`` for a batch that carries augmentation records: the same staging and ONE upload (header, level tables and frames
+        together), then ``tai_clip_from_frames_aug``."""
+        n = B * T
+        head = aug_header_bytes(n)
+        (H, W), (ph, pw) = self.image_size, self.padding_size
+        with torch.cuda.device(self.device):
+            if 'packed' in batch:
+                packed, n_tables = batch['packed'], int(batch['n_tables'])
+                first = head + n_tables * TABLE_BYTES
+                if packed.dtype != torch.uint8 or packed.dim() != 1 or n_tables < 1 or packed.numel() <= first or not packed.is_contiguous():
+                    raise ValueError('DeviceClipBuilder.build: not an augmented packed batch')
+                nbytes = packed.numel()
+                slot = self._slot(nbytes)
+                slot.host[:nbytes].copy_(packed)
+            else:
+                clips, _ = _as_clips([it['frames'] for it in batch['items']])
+                augs = _augs_of(batch['items'])
+                nbytes = aug_packed_bytes(clips, augs)
+                slot = self._slot(nbytes)
+                _, n_tables = pack_clips_aug(clips, [it['mirror'] for it in batch['items']], augs, out=slot.host)
+                first = head + n_tables * TABLE_BYTES
+            slot.dev[:nbytes].copy_(slot.host[:nbytes], non_blocking=True)
+            slot.event.record(torch.cuda.current_stream(self.device))
+            out = torch.empty(B, T, self.c_dim, H + ph, W + pw, dtype=torch.float32, device=self.device)
+            # the descriptor table is validated on the host from the staging buffer's header before anything is launched
+            _native.launch('tai_clip_from_frames_aug', self.device, slot.dev.data_ptr() + first, nbytes - first, slot.dev, slot.host,
+                           slot.dev.data_ptr() + head, n_tables, self._levels, out, n, self.c_dim, H, W, ph, pw)
         return out
 
 

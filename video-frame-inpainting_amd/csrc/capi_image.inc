@@ -240,6 +240,24 @@ int tai_clip_from_frames(const unsigned char* frames, long long frames_bytes, co
     return check_launch("clip_from_frames");
 }
 
+int tai_clip_from_frames_aug(const unsigned char* frames, long long frames_bytes, const long long* table, const long long* table_host,
+                             const float* tables, int n_tables, const float* levels, float* out, int N, int c_dim, int H, int W, int pad_h,
+                             int pad_w, void* stream) {
+    g_err[0] = 0;
+    if (const char* why = clipaug::call_refusal(frames, frames_bytes, table, table_host, tables, n_tables, levels, out, N, c_dim, H, W, pad_h, pad_w))
+        return fail(TAI_SEPCONV_EINVAL, "%s", why);
+    const long long Hp = (long long)H + pad_h, Wp = (long long)W + pad_w;
+    const clipaug::Geometry g = clipaug::geometry(Hp, Wp);
+    const long long items = (long long)N * g.bands;
+    const bool vec4 = Wp % 4 == 0 && aligned(out, 16);
+    auto kern = c_dim == 1 ? (vec4 ? clipaug::from_frames_aug<1, true> : clipaug::from_frames_aug<1, false>)
+                           : (vec4 ? clipaug::from_frames_aug<3, true> : clipaug::from_frames_aug<3, false>);
+    hipLaunchKernelGGL(kern, capped_grid(items, clipaug::GRID_CAP), dim3(clipaug::THREADS), 0, static_cast<hipStream_t>(stream), frames,
+                       frames_bytes, table, tables, n_tables, levels, out, H, W, (int)Hp, (int)Wp, g.runs_per_row, g.rw, g.band_rows, g.bands,
+                       items);
+    return check_launch("clip_from_frames_aug");
+}
+
 int tai_frames_to_uint8(const float* x, unsigned char* out, int N, int C, int Hs, int Ws, int h, int w, int reverse_channels,
                         void* hip_stream) {
     g_err[0] = 0;

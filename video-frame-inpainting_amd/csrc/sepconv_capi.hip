@@ -38,6 +38,7 @@
 #include "temporal_loss.hip.inc"
 #include "census_loss.hip.inc"
 #include "clip_pipeline.hip.inc"
+#include "clip_augment.hip.inc"
 #include "state_digest.hip.inc"
 #include "grad_stats.hip.inc"
 #include "fused_step.hip.inc"
@@ -142,7 +143,7 @@ void wino_div_magic(long long d, unsigned& m, unsigned& sh) {
 
 extern "C" {
 
-int tai_sepconv_version(void) { return 850; }
+int tai_sepconv_version(void) { return 860; }
 
 const char* tai_sepconv_last_error(void) { return g_err; }
 

@@ -103,6 +103,70 @@ def resize_bilinear(frame, height, width):
     return np.clip(np.floor(out + 0.5), 0, 255).astype(np.uint8)
 
 
+class ClipAugment(object):
+    """The opt-in training augmentation (train.py --aug_crop / --aug_vflip / --aug_brightness / --aug_contrast / --aug_gamma /
+    --aug_flicker; the definition is include/tai_sepconv.h's, at tai_clip_from_frames_aug).  ``on`` when any setting differs from its
+    default; a dataset then draws N_CLIP_DRAWS + seq_len unit uniforms per clip in one fixed order -- all of them whichever flags are
+    set, so switching one flag never shifts another's stream."""
+
+    N_CLIP_DRAWS = 7                  # u_scale, u_top, u_left, u_vflip, u_gamma, u_gain, u_offset; then one per frame
+    _FIELDS = ('crop', 'vflip', 'brightness', 'contrast', 'gamma', 'flicker')
+
+    def __init__(self, crop=1.0, vflip=False, brightness=0.0, contrast=0.0, gamma=0.0, flicker=0.0):
+        self.crop, self.vflip = float(crop), bool(vflip)
+        self.brightness, self.contrast, self.gamma, self.flicker = float(brightness), float(contrast), float(gamma), float(flicker)
+        for flag, ok, want in (('aug_crop', 0.0 < self.crop <= 1.0, 'in (0, 1]'),
+                               ('aug_brightness', 0.0 <= self.brightness < 1.0, 'in [0, 1)'),
+                               ('aug_contrast', 0.0 <= self.contrast < 1.0, 'in [0, 1)'),
+                               ('aug_gamma', 0.0 <= self.gamma < float('inf'), 'finite and >= 0'),
+                               ('aug_flicker', 0.0 <= self.flicker < 1.0, 'in [0, 1)')):
+            if not ok:                # (a NaN fails every comparison)
+                raise ValueError('--%s must be %s, found %r' % (flag, want, getattr(self, flag[4:])))
+
+    @classmethod
+    def from_options(cls, opt):
+        return cls(opt.aug_crop, opt.aug_vflip, opt.aug_brightness, opt.aug_contrast, opt.aug_gamma, opt.aug_flicker)
+
+    @property
+    def on(self):
+        return self.state() != ClipAugment().state()
+
+    def state(self):
+        """The settings as plain values: what a resumable run records (only when ``on``) and compares on a continuation."""
+        return {k: getattr(self, k) for k in self._FIELDS}
+
+    def check_continues(self, saved):
+        """Refuse to continue a run whose saved data state carries other augmentation settings (``saved``: its 'augment' entry, None
+        when it ran without augmentation), in the words of ``ResumableBatchSampler.load_state``."""
+        mine = self.state() if self.on else None
+        if saved != mine:
+            raise ValueError('the saved clip order has augment = %r, this run has %r: it cannot be continued exactly' % (saved, mine))
+
+    def draw(self, rng, seq_len):
+        """One clip's record from N_CLIP_DRAWS + seq_len draws of ``rng``; the crop window waits for the frame size (``window``)."""
+        u = [rng.random() for _ in range(self.N_CLIP_DRAWS + seq_len)]
+        return {'u_crop': (u[0], u[1], u[2]), 'smin': self.crop,
+                'vflip': bool(self.vflip and u[3] > 0.5),
+                'gamma': (1.0 + self.gamma) ** (2.0 * u[4] - 1.0),
+                'gain': 1.0 + self.contrast * (2.0 * u[5] - 1.0),
+                'offset': self.brightness * (2.0 * u[6] - 1.0),
+                'flicker': tuple(self.flicker * (2.0 * v - 1.0) for v in u[self.N_CLIP_DRAWS:]) if self.flicker > 0.0 else None}
+
+
+def crop_window(h, w, smin, u_scale, u_top, u_left):
+    """(top, left, ch, cw) of the crop window in an h x w frame, in float64 (Python floats)."""
+    s = smin + u_scale * (1.0 - smin)
+    ch, cw = max(1, int(np.floor(s * h))), max(1, int(np.floor(s * w)))
+    top = min(int(np.floor(u_top * (h - ch + 1))), h - ch)
+    left = min(int(np.floor(u_left * (w - cw + 1))), w - cw)
+    return top, left, ch, cw
+
+
+def with_window(aug, h, w):
+    """The record with its crop window placed in an h x w frame."""
+    return dict(aug, window=crop_window(h, w, aug['smin'], *aug['u_crop']))
+
+
 class ClipRecord(object):
     """One parsed line of a video list.  Formats (reference base_dataset.py:147-156, :214-222), frame numbers 1-indexed and
     inclusive in the file, 0-indexed here:
@@ -147,7 +211,10 @@ class _ClipReader(object):
             warn('Failed to read frame %d in %s: %s' % (index, getattr(source, '_filename', '?'), e))
             return None
 
-    def clip(self, source, indexes, mirror, reverse):
+    def clip(self, source, indexes, mirror, reverse, aug=None):
+        """``aug``: the clip's augmentation record (ClipAugment.draw) or None = the reference's pipeline, untouched."""
+        if aug is not None:
+            return self._augmented_clip(source, indexes, mirror, reverse, aug)
         frames = []
         for t in indexes:
             raw = self.frame(source, t)
@@ -163,6 +230,35 @@ class _ClipReader(object):
             frames.reverse()
         clip = fore_transform(torch.stack(frames))                  # T x C x H x W in [-1, 1]
         return bgr2gray(clip) if self.c_dim == 1 else clip
+
+    def _augmented_clip(self, source, indexes, mirror, reverse, aug):
+        """The host path of the augmented pipeline (include/tai_sepconv.h, tai_clip_from_frames_aug): crop, resize, BGR, flips, the
+        frame's level table on the image area, then the neutral padding.  Bit-equal to the device path and to tests/clip_augment_ref.py."""
+        from .clip_pipeline import level_tables, tables_of_record
+        levels = []
+        for t in indexes:
+            raw = self.frame(source, t)
+            if raw is None:
+                return None
+            if not levels:            # one window for the clip: the record's own if it was placed already (``with_window``)
+                top, left, ch, cw = aug.get('window') or crop_window(raw.shape[0], raw.shape[1], aug['smin'], *aug['u_crop'])
+            img = resize_bilinear(raw[top:top + ch, left:left + cw], self.image_size[0], self.image_size[1])[:, :, ::-1]
+            if aug['vflip']:
+                img = img[::-1]
+            if mirror:
+                img = img[:, ::-1]
+            levels.append(torch.from_numpy(np.ascontiguousarray(img)).permute(2, 0, 1).long())         # [3, H, W] levels, BGR
+        if reverse:
+            levels.reverse()
+        tables, neutral = tables_of_record(aug), level_tables()
+        H, W = self.image_size
+        C = 3 if self.c_dim != 1 else 1
+        pad = neutral[0, 0] if C == 3 else (neutral[1, 0] + neutral[2, 0]) + neutral[3, 0]
+        clip = pad.repeat(len(levels), C, H + self.padding_size[0], W + self.padding_size[1])
+        for i, q in enumerate(levels):                               # the frame at playback position i reads table i (flicker) or 0
+            tab = tables[i if tables.shape[0] > 1 else 0]
+            clip[i, :, :H, :W] = tab[0][q] if C == 3 else ((tab[1][q[0]] + tab[2][q[1]]) + tab[3][q[2]])[None]
+        return clip
 
     def raw_clip(self, source, indexes, reverse):
         """The decoded frames of one clip as they are, uint8 RGB [T, h, w, 3] in playback order (``reverse`` applied): what the
@@ -253,6 +349,11 @@ class ContiguousVideoClipDataset(data.Dataset):
     and ``numpy.random`` modules, which in a data-parallel run is also where (K, T, F) used to come from -- one rank's
     decode retry would desynchronise every rank's model shapes.
 
+    ``augment`` (a ``ClipAugment`` that is on; train.py --aug_*): after those three draws a clip draws its augmentation record -- a fixed
+    number of uniforms, before any frame is read -- and the clip is cropped, flipped and photometrically changed by it; a raw item carries
+    the record as ``'aug'`` for the device path, which gives the same bits.  Window start, mirror and reversal stay those of the same
+    run without it.
+
     ``raw=True`` (the device clip pipeline, clip_pipeline.py): an item is ``{'frames': uint8 [T, h, w, 3] RGB as decoded, in
     playback order, 'mirror': bool, 'clip_label': str}`` -- the same draws in the same order pick the same window, mirror and
     reversal; the resize, flip, padding, range map and gray conversion are left to the GPU.
@@ -262,7 +363,7 @@ class ContiguousVideoClipDataset(data.Dataset):
     [start frame, mirror, reverse], for whoever wants to compare orders."""
 
     def __init__(self, c_dim, video_list_path, seq_length, backwards, flip, image_size, resample_on_fail, padding_size,
-                 seed=0, raw=False, rank=0):
+                 seed=0, raw=False, rank=0, augment=None):
         super().__init__()
         with open(video_list_path, 'r') as f:
             self.files = [line.strip() for line in f.readlines()]
@@ -272,6 +373,7 @@ class ContiguousVideoClipDataset(data.Dataset):
         self._seed = int(seed)
         self._rank = int(rank)
         self.raw = bool(raw)
+        self.augment = augment if augment is not None and augment.on else None      # a ClipAugment that is on, else nothing is drawn
         self.rng = random.Random(self._seed)
 
     def worker_init(self, worker_id):
@@ -299,13 +401,17 @@ class ContiguousVideoClipDataset(data.Dataset):
         start = rng.randint(first, last - self.seq_len + 1)
         mirror = self.flip and rng.random() > 0.5
         reverse = self.backwards and rng.random() > 0.5
+        # the augmentation's draws: after the three above, from the same generator, all of them, before any frame is read
+        aug = self.augment.draw(rng, self.seq_len) if self.augment is not None else None
         if self.raw:
             frames = self.reader.raw_clip(source, range(start, start + self.seq_len), reverse)
             if frames is None:
                 return None, 'Failed to sample frames starting at %d in %s' % (start, record.path)
             item = {'frames': frames, 'mirror': bool(mirror), 'clip_label': record.label([(first, last)])}
+            if aug is not None:
+                item['aug'] = with_window(aug, frames.shape[1], frames.shape[2])
         else:
-            clip = self.reader.clip(source, range(start, start + self.seq_len), mirror, reverse)
+            clip = self.reader.clip(source, range(start, start + self.seq_len), mirror, reverse, **({} if aug is None else {'aug': aug}))
             if clip is None:
                 return None, 'Failed to sample frames starting at %d in %s' % (start, record.path)
             item = {'targets': clip, 'clip_label': record.label([(first, last)])}

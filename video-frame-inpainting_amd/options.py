@@ -174,8 +174,33 @@ class TrainOptions(BaseOptions):
         g.add_argument('--miopen_find_mode', type=str, default=None, choices=['NORMAL', 'FAST', 'HYBRID', 'DYNAMIC_HYBRID'],
                        help='MIOPEN_FIND_MODE for this run (package default FAST: first update 1.4 s instead of 22 s, later updates '
                             '2-3 %% slower; NORMAL pays the search once and is the choice for a long run)')
+        g = self.parser.add_argument_group('Training augmentation parameters (this build; training clips only -- validation legs and '
+                                           'predict.py never augment; host path and --device_preprocess give the same bits; with every '
+                                           'flag at its default nothing is drawn or launched)')
+        g.add_argument('--aug_crop', type=float, default=1.0, metavar='SMIN',
+                       help='per clip, resize a random window of the source frame instead of the whole frame: its side is a uniform share '
+                            'in [SMIN, 1] of the frame, the same window for all frames of the clip; SMIN in (0, 1], 1 = off')
+        g.add_argument('--aug_vflip', action='store_true', help='per clip, flip top-bottom with probability 1/2')
+        g.add_argument('--aug_brightness', type=float, default=0.0, metavar='B',
+                       help='per clip, an additive offset uniform in [-B, B] on the [0, 1] scale; 0 <= B < 1')
+        g.add_argument('--aug_contrast', type=float, default=0.0, metavar='C',
+                       help='per clip, a gain uniform in [1 - C, 1 + C] about 0.5; 0 <= C < 1')
+        g.add_argument('--aug_gamma', type=float, default=0.0, metavar='G',
+                       help='per clip, gamma = (1 + G)^u with u uniform in [-1, 1]; G >= 0')
+        g.add_argument('--aug_flicker', type=float, default=0.0, metavar='F',
+                       help='per FRAME, a further additive offset uniform in [-F, F]: the exposure difference between frames that the '
+                            'census term (--census_weight) does not charge; 0 <= F < 1')
         g = self.parser.add_argument_group('Training visualization parameters')
         g.add_argument('--tensorboard_dir', type=str, default='tb')
+
+    def parse(self, args=None, allow_unknown=False, require_gpu=True):
+        opt = super().parse(args, allow_unknown, require_gpu)
+        from .data import ClipAugment
+        try:                                   # an augmentation setting outside its range is refused here, with the flag named
+            ClipAugment.from_options(opt)
+        except ValueError as e:
+            self.parser.error(str(e))
+        return opt
 
 
 class TestOptions(BaseOptions):
