@@ -841,6 +841,39 @@ int tai_fused_step(const long long* table, const long long* table_host, int n_en
                    long long table_len, float w1, float b2, float w2, float eps, float wE, const long long* record, int which, int nt,
                    int blocks, void* workspace, void* hip_stream);
 
+/* The fused step with a learning-rate schedule, a warm-up and decoupled weight decay (train.py --fused_step --lr_schedule
+ * {constant,step,cosine} --warmup_updates W --lr_decay_every E --lr_gamma g --lr_min_ratio r --weight_decay wd; restated in
+ * tests/fused_step_decay_ref.py).  The schedule is the host's table and nothing else: Python floats (float64, the math module) for
+ * t' = 1 ... table_len, with L the optimizer's base rate and N the number of steps the table is built for:
+ *     warm(t')  = t' / W                                   if t' <= W, else 1.0
+ *     constant:   s(t') = 1.0
+ *     step:       s(t') = g ** ((t' - 1) // E)
+ *     cosine:     s(t') = 1.0                              for t' <= W
+ *                 u = min(1.0, (t' - W) / max(1, N - W))
+ *                 s(t') = r + (1.0 - r) * (0.5 * (1.0 + math.cos(math.pi * u)))
+ *     lr(t')    = (L * warm(t')) * s(t')
+ *     step_size[t'] = f32(lr(t') / (1 - beta1**t'))        bc2s[t'] as above
+ *     decay[t']     = f32(lr(t') * wd)
+ * t' counts the steps taken -- a skipped step does not advance it -- so the schedule follows them and is saved with the optimizer
+ * state.  With the constant schedule, W = 0 and wd = 0 the table is the one above bit for bit.  A schedule with wd = 0 needs no other
+ * kernel: tai_fused_step runs on the scheduled table.  With wd > 0, tai_fused_step_decay; per element, single IEEE fp32 operations as
+ * above, only the line for p changes:
+ *     p1 = p - (decay[t'] * p)         for entries whose flag says "decays"; p1 = p for the others
+ *     p' = p1 - step_size[t'] * (m' / s)
+ *     e' = e + wE * (p' - e)
+ * An entry without the flag never multiplies its p by anything: a non-finite p there behaves as in tai_fused_step.  A skipped verdict
+ * changes no byte.
+ *
+ * tai_fused_step_decay: table / table_host and record as tai_fused_step takes them; flags / flags_host, a device and a host copy of one
+ * 64-bit word per entry, 8-byte aligned, bit 0 = the entry decays, any value other than 0 or 1 refused from flags_host before anything
+ * is launched; scalars: device fp32 [3][table_len], step_size, bc2s, then decay.  The row's flag is read once per segment, the scalars
+ * once per workgroup; loads are plain.  The results depend neither on blocks nor on repetition from equal state, and with every flag 0
+ * they are tai_fused_step's.  No workspace today.  No allocation, copy or synchronisation; asynchronous on the stream. */
+long long tai_fused_step_decay_workspace_bytes(int n_entries, long long n_segments);
+int tai_fused_step_decay(const long long* table, const long long* table_host, const long long* flags, const long long* flags_host,
+                         int n_entries, long long n_segments, const float* scalars, long long table_len, float w1, float b2, float w2,
+                         float eps, float wE, const long long* record, int which, int blocks, void* workspace, void* stream);
+
 /* Text of the last error on the calling thread ("" if none). */
 const char* tai_sepconv_last_error(void);
 

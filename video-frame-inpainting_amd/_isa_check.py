@@ -13,6 +13,8 @@ fstep::step_segments (the fused optimizer step, csrc/fused_step.hip.inc): its ar
    correctly rounded division (five each) and square root (two each, the next-up / next-down residual test behind v_sqrt_f32).  So the
    number of fp32 fma / fmac / mad instructions must be exactly 5 x divisions + 2 x square roots -- one more would be a contracted
    a * b + c of the definition -- every square root must be the refined form, and there is no scratch.
+   fstep::step_segments_decay (the same step with the weight-decay line, tai_fused_step_decay): the same rule under its own name
+   (check_fused_step_decay, part of check()): its decay line must stay a multiplication and a subtraction.
 """
 import re
 
@@ -70,15 +72,29 @@ def check(asm):
         want = 252 if name in wrw else 216
         if n != want:
             bad.append('%s: %d MFMAs in the chunk loops, expected %d' % (name, n, want))
-    return bad
+    return bad + check_fused_step_decay(asm)
 
 
 def check_fused_step(asm):
     """-> list of violations of the fused optimizer step's kernels (see the module's docstring)."""
-    bad = []
     found = kernels(asm, '_ZN5fstep13step_segments')
+    bad = []
     if len(found) != 2:
         bad.append('expected two fstep::step_segments kernels (plain and non-temporal loads), found %d' % len(found))
+    return bad + _step_arithmetic(found)
+
+
+def check_fused_step_decay(asm):
+    """-> list of violations of fstep::step_segments_decay (tai_fused_step_decay): the same rule under its own name."""
+    found = kernels(asm, '_ZN5fstep19step_segments_decay')
+    bad = []
+    if len(found) != 1:
+        bad.append('expected one fstep::step_segments_decay kernel, found %d' % len(found))
+    return bad + _step_arithmetic(found)
+
+
+def _step_arithmetic(found):
+    bad = []
     for name, (lines, desc) in found.items():
         ops = [l.split()[0] for l in lines if l.startswith('\t') and l.split() and l.split()[0].startswith(('v_', 'scratch_'))]
         count = lambda *prefixes: sum(1 for o in ops if o.startswith(prefixes))

@@ -43,6 +43,17 @@ int grad_table_ok(const char* who, const long long* table_host, int n_entries, l
                        });
 }
 
+// the table of tai_fused_step and tai_fused_step_decay: rows of {p, g, m, v, step tensor, e, elements, first segment}
+int step_table_ok(const char* who, const long long* table_host, int n_entries, long long n_segments) {
+    return check_table(who, "p, g, m, v (4-byte aligned, 0 exactly when empty), step, e, 0 <= elements < 2^40", table_host, n_entries,
+                       fstep::ROW, fstep::SEG, n_segments, [](const long long* row, long long next) {
+                           const long long n = row[6];
+                           bool ok = count_ok(n) && row[7] == next && (row[4] & 3) == 0;
+                           for (int a = 0; a < 4 && ok; ++a) ok = (row[a] & 3) == 0 && (row[a] == 0) == (n == 0);
+                           return ok && (row[5] & 3) == 0 && (n != 0 || row[5] == 0) ? n : -1;
+                       });
+}
+
 }  // namespace
 
 extern "C" {
@@ -150,13 +161,7 @@ int tai_fused_step(const long long* table, const long long* table_host, int n_en
     if (!table || !table_host || !scalars || !record) return fail(TAI_SEPCONV_EINVAL, "%s", "fused_step: null pointer");
     if (n_entries <= 0 || blocks < 0 || blocks > 65536 || (which != 0 && which != 1) || table_len < 1 || !aligned(record, 8) || !aligned(scalars, 4))
         return fail(TAI_SEPCONV_EINVAL, "%s", "fused_step: needs n_entries > 0, 0 <= blocks <= 65536, which in {0, 1}, table_len >= 1, aligned record and scalars");
-    const int ok = check_table("fused_step", "p, g, m, v (4-byte aligned, 0 exactly when empty), step, e, 0 <= elements < 2^40", table_host, n_entries,
-                               fstep::ROW, fstep::SEG, n_segments, [](const long long* row, long long next) {
-                                   const long long n = row[6];
-                                   bool ok = count_ok(n) && row[7] == next && (row[4] & 3) == 0;
-                                   for (int a = 0; a < 4 && ok; ++a) ok = (row[a] & 3) == 0 && (row[a] == 0) == (n == 0);
-                                   return ok && (row[5] & 3) == 0 && (n != 0 || row[5] == 0) ? n : -1;
-                               });
+    const int ok = step_table_ok("fused_step", table_host, n_entries, n_segments);
     if (ok != TAI_SEPCONV_OK) return ok;
     const fstep::Scalars k = {w1, b2, w2, eps, wE};
     const dim3 grid(table_blocks(n_segments > 0 ? n_segments : 1, blocks)), block(fstep::THREADS);
@@ -164,6 +169,27 @@ int tai_fused_step(const long long* table, const long long* table_host, int n_en
     hipLaunchKernelGGL(nt ? fstep::step_segments<true> : fstep::step_segments<false>, grid, block, 0, s, table, n_entries, n_segments, scalars, table_len,
                        k, record, which);
     return check_launch("fused_step");
+}
+
+long long tai_fused_step_decay_workspace_bytes(int n_entries, long long n_segments) {
+    if (n_entries <= 0 || n_segments < 0) return TAI_SEPCONV_EINVAL;
+    return 0;
+}
+
+int tai_fused_step_decay(const long long* table, const long long* table_host, const long long* flags, const long long* flags_host,
+                         int n_entries, long long n_segments, const float* scalars, long long table_len, float w1, float b2, float w2,
+                         float eps, float wE, const long long* record, int which, int blocks, void* workspace, void* stream) {
+    g_err[0] = 0;
+    (void)workspace;
+    if (const char* why = fstep::refusal(table, table_host, flags, flags_host, n_entries, scalars, table_len, record, which, blocks))
+        return fail(TAI_SEPCONV_EINVAL, "%s", why);
+    const int ok = step_table_ok("fused_step_decay", table_host, n_entries, n_segments);
+    if (ok != TAI_SEPCONV_OK) return ok;
+    const fstep::Scalars k = {w1, b2, w2, eps, wE};
+    const dim3 grid(table_blocks(n_segments > 0 ? n_segments : 1, blocks)), block(fstep::THREADS);
+    hipLaunchKernelGGL(fstep::step_segments_decay, grid, block, 0, static_cast<hipStream_t>(stream), table, flags, n_entries, n_segments, scalars,
+                       table_len, k, record, which);
+    return check_launch("fused_step_decay");
 }
 
 }  // extern "C"

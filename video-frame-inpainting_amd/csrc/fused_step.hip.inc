@@ -11,6 +11,9 @@
 //     p' = p - step_size[t'] * (m' / s)
 //     e' = e + wE * (p' - e)              (entries that carry an EMA tensor)
 // and every `step` tensor of the table holds float(t') afterwards.  A skipped step changes no byte.
+// tai_fused_step_decay (step_segments_decay; train.py --weight_decay) puts one line in front of p's for the entries whose flag is set,
+//     p1 = p - (decay[t'] * p)
+// and takes p1 for p: decoupled weight decay, two more fp32 operations per element and no more bytes.
 //
 // On the hardware: the 16384-element segments and the grid-stride walk of gstat::segment_stats; one workgroup of 256 lanes per segment,
 // four rounds of 16-byte loads per array in flight per lane where every address of the segment is 16-byte aligned and the segment is
@@ -253,6 +256,119 @@ __global__ __launch_bounds__(THREADS) void step_segments(const long long* __rest
             }
         }
     }
+}
+
+// p1 = p - (decay * p): the decoupled weight decay, in front of element()
+template <typename T>
+__device__ __forceinline__ T decayed(const T p, const float decay) {
+#pragma clang fp contract(off)
+    const T dp = p * decay;
+    return p - dp;
+}
+
+// tai_fused_step_decay: step_segments' walk (plain loads) with the decay line for the entries whose flag is set.  A kernel of its own
+// name and body: step_segments stays the code it was.  scalars: device fp32 [3][table_len], the third row decay[t' - 1], read once per
+// workgroup; flags[t] bit 0: entry t decays, read once per segment.  An entry without the flag multiplies its p by nothing.
+__global__ __launch_bounds__(THREADS) void step_segments_decay(const long long* __restrict__ table, const long long* __restrict__ flags,
+                                                               int n_entries, long long n_segments, const float* __restrict__ scalars,
+                                                               long long table_len, const Scalars k, const long long* __restrict__ rec,
+                                                               int which) {
+    if (rec[R_VERDICT + which] == SKIPPED) return;
+    const long long tprime = rec[R_TPRIME + which];
+    if (tprime < 1 || tprime > table_len) return;
+    const float c = __uint_as_float((unsigned int)rec[R_COEFF + which]);
+    const float step_size = scalars[tprime - 1], bc2s = scalars[table_len + tprime - 1], decay = scalars[2 * table_len + tprime - 1];
+    for (long long t = (long long)blockIdx.x * THREADS + threadIdx.x; t < n_entries; t += (long long)gridDim.x * THREADS) {
+        const gfloats step = (gfloats)(unsigned long long)table[ROW * t + 4];
+        if (step) *step = (float)tprime;
+    }
+    for (long long seg = blockIdx.x; seg < n_segments; seg += gridDim.x) {
+        int lo = 0, hi = n_entries - 1;                  // the LAST row with first segment <= seg
+        while (lo < hi) {
+            const int mid = (lo + hi + 1) >> 1;
+            if (table[ROW * (long long)mid + 7] <= seg) lo = mid; else hi = mid - 1;
+        }
+        const long long* row = table + ROW * (long long)lo;
+        const unsigned long long n = (unsigned long long)row[6];
+        const unsigned long long first = (unsigned long long)(seg - row[7]) * SEG;
+        if (row[0] == 0 || first >= n) continue;
+        const bool decays = (flags[lo] & 1) != 0;
+        const unsigned int count = n - first < SEG ? (unsigned int)(n - first) : SEG;
+        const gfloats p = (gfloats)(unsigned long long)row[0] + first;
+        const cgfloats g = (cgfloats)(unsigned long long)row[1] + first;
+        const gfloats m = (gfloats)(unsigned long long)row[2] + first;
+        const gfloats v = (gfloats)(unsigned long long)row[3] + first;
+        const gfloats e = row[5] ? (gfloats)(unsigned long long)row[5] + first : (gfloats)0;
+        const unsigned long long low = (unsigned long long)p | (unsigned long long)g | (unsigned long long)m | (unsigned long long)v |
+                                       (unsigned long long)e;
+        if (count == SEG && (low & 15) == 0) {
+            const gvecs pv = (gvecs)p + threadIdx.x;
+            const cgvecs gv = (cgvecs)g + threadIdx.x;
+            const gvecs mv = (gvecs)m + threadIdx.x;
+            const gvecs vv = (gvecs)v + threadIdx.x;
+            const gvecs ev = e ? (gvecs)e + threadIdx.x : (gvecs)0;
+            for (int b = 0; b < ROUNDS / BATCH; ++b) {
+                f4v xp[BATCH], xg[BATCH], xm[BATCH], xv[BATCH], xe[BATCH];
+#pragma unroll
+                for (int r = 0; r < BATCH; ++r) {
+                    const int at = (b * BATCH + r) * THREADS;
+                    xg[r] = gv[at];
+                    xm[r] = mv[at];
+                    xv[r] = vv[at];
+                    xp[r] = pv[at];
+                }
+                if (ev) {
+#pragma unroll
+                    for (int r = 0; r < BATCH; ++r) xe[r] = ev[(b * BATCH + r) * THREADS];
+                }
+                if (decays) {
+#pragma unroll
+                    for (int r = 0; r < BATCH; ++r) xp[r] = decayed(xp[r], decay);
+                }
+#pragma unroll
+                for (int r = 0; r < BATCH; ++r) {
+                    element(xp[r], xg[r], xm[r], xv[r], c, k, step_size, bc2s);
+                }
+#pragma unroll
+                for (int r = 0; r < BATCH; ++r) {
+                    const int at = (b * BATCH + r) * THREADS;
+                    pv[at] = xp[r];
+                    mv[at] = xm[r];
+                    vv[at] = xv[r];
+                }
+                if (ev) {
+#pragma unroll
+                    for (int r = 0; r < BATCH; ++r) {
+                        const f4v a = average(xe[r], xp[r], k.wE);
+                        ev[(b * BATCH + r) * THREADS] = a;
+                    }
+                }
+            }
+        } else {
+            for (unsigned int i = threadIdx.x; i < count; i += THREADS) {
+                float xp = p[i], xm = m[i], xv = v[i];
+                if (decays) xp = decayed(xp, decay);
+                element(xp, g[i], xm, xv, c, k, step_size, bc2s);
+                p[i] = xp;
+                m[i] = xm;
+                v[i] = xv;
+                if (e) e[i] = average(e[i], xp, k.wE);
+            }
+        }
+    }
+}
+
+// what tai_fused_step_decay refuses apart from its table's rows, before anything is launched; null: the rows are looked at next
+inline const char* refusal(const void* table, const long long* table_host, const void* flags, const long long* flags_host, int n_entries,
+                           const void* scalars, long long table_len, const void* record, int which, int blocks) {
+    if (!table || !table_host || !flags || !flags_host || !scalars || !record) return "fused_step_decay: null pointer";
+    if (n_entries <= 0 || blocks < 0 || blocks > 65536 || (which != 0 && which != 1) || table_len < 1)
+        return "fused_step_decay: needs n_entries > 0, 0 <= blocks <= 65536, which in {0, 1}, table_len >= 1";
+    if (((unsigned long long)record & 7) != 0 || ((unsigned long long)flags & 7) != 0 || ((unsigned long long)scalars & 3) != 0)
+        return "fused_step_decay: record and flags must be 8-byte aligned, scalars 4-byte aligned";
+    for (int t = 0; t < n_entries; ++t)
+        if (flags_host[t] != 0 && flags_host[t] != 1) return "fused_step_decay: a flag word must be 0 or 1 (bit 0: the entry decays)";
+    return nullptr;
 }
 
 }  // namespace fstep

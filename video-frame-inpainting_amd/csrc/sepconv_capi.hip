@@ -143,7 +143,7 @@ void wino_div_magic(long long d, unsigned& m, unsigned& sh) {
 
 extern "C" {
 
-int tai_sepconv_version(void) { return 860; }
+int tai_sepconv_version(void) { return 870; }
 
 const char* tai_sepconv_last_error(void) { return g_err; }
 

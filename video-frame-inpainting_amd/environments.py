@@ -47,7 +47,8 @@ def create_training_environment(fill_in_model, c_dim, checkpoints_dir, name, max
                                 beta, lr, beta1, df_dim, Ip, disc_window_size, padding_size, device=None, graph_step=False,
                                 resumable=False, guard=None, fused_step=False, ema_decay=None, max_iter=100000, ssim_weight=0.0,
                                 image_loss='l2', charbonnier_eps=1e-3, lap_weight=0.0, lap_levels=5, temporal_weight=0.0,
-                                temporal_kind='charbonnier', temporal_eps=1e-3, census_weight=0.0):
+                                temporal_kind='charbonnier', temporal_eps=1e-3, census_weight=0.0, lr_D=None, lr_schedule=None,
+                                weight_decay=0.0):
     if not ssim_weight >= 0.0:
         raise ValueError('ssim_weight must not be negative, found %r' % (ssim_weight,))
     if not lap_weight >= 0.0:
@@ -71,6 +72,11 @@ def create_training_environment(fill_in_model, c_dim, checkpoints_dir, name, max
     if ema_decay is not None and not fused_step:
         raise ValueError('--ema_decay needs --fused_step: the average is kept by the fused optimizer step')
     fused_step_module.check_ema_decay(ema_decay)
+    # lr_schedule: a fused_step.Schedule (train.py --lr_schedule --warmup_updates --lr_decay_every --lr_gamma --lr_min_ratio) or None
+    (lr_schedule or fused_step_module.Schedule()).check()
+    fused_step_module.check_weight_decay(weight_decay)
+    if not fused_step and fused_step_module.needs_fused_step(lr_schedule, weight_decay):
+        raise ValueError(fused_step_module.needs_fused_step(lr_schedule, weight_decay))
     if isinstance(fill_in_model, (TAIFillInModel, TimeWeightedInterpolationFillInModel,
                                   BidirectionalSimpleAverageFillInModel, BidirectionalTimeWeightedAverageFillInModel)):
         env = TAITrainingEnvironment(      # environments.py:29-31
@@ -92,8 +98,11 @@ def create_training_environment(fill_in_model, c_dim, checkpoints_dir, name, max
                            % type(fill_in_model).__name__)
     env.resumable = bool(resumable)
     env.guard = guard
+    if lr_D is not None and hasattr(env, 'optimizer_D'):      # only another number handed to the second optimizer
+        env.optimizer_D.param_groups[0]['lr'] = float(lr_D)
     if fused_step:
-        env.fused = fused_step_module.FusedStep(env.device, max_iter, guard=guard, ema_decay=ema_decay)
+        env.fused = fused_step_module.FusedStep(env.device, max_iter, guard=guard, ema_decay=ema_decay, schedule=lr_schedule,
+                                                weight_decay=weight_decay)
         env.fused.attach('G', env.generator, env.optimizer_G)
         if hasattr(env, 'optimizer_D'):
             env.fused.attach('D', env.discriminator, env.optimizer_D)
@@ -383,6 +392,14 @@ class BaseTrainingEnvironment(BaseVideoFillInEnvironment):
         self.start_sum_avg_psnr_err = snapshot['sum_avg_psnr_err']
         self.start_sum_avg_ssim_err = snapshot['sum_avg_ssim_err']
         self._step_graphs.clear()
+        if self.resumable and snapshot.get('run_state') is not None:
+            # another schedule (a cosine over another --max_iter too) is another run: refused before anything is loaded
+            saved = snapshot['run_state'].get('lr_schedule')
+            if self.fused is not None:
+                self.fused.check_continues(saved)
+            elif saved is not None:
+                raise ValueError('the snapshot was written with a learning-rate schedule or weight decay (%s), this run has neither: '
+                                 'it cannot be continued exactly' % ' '.join('--%s %s' % kv for kv in sorted(saved.items())))
         self._load_training_state(snapshot)
         if self.fused is not None:
             self.fused.after_load(snapshot, (snapshot.get('run_state') or {}).get('ema') if self.resumable else None)

@@ -10,6 +10,12 @@ with ``scalar_table`` / ``constants`` computed once in Python floats and rounded
 in the record.  A skipped step changes nothing.  Tensors that live on the host (the tests' CPU environment, gloo) take ``host_step``:
 the same definition in numpy, the same bits.
 
+``--lr_schedule / --warmup_updates / --weight_decay``: the schedule is the table and nothing else -- ``scheduled_table`` puts lr(t') of
+``learning_rates`` where ``scalar_table`` has lr, so the rate follows the steps TAKEN (a skipped step does not advance t') and is saved
+with the optimizer state -- and the decoupled decay is one line in front of p's, p1 = p - (decay[t'] * p) with decay[t'] =
+f32(lr(t') wd), for the generator's parameters with two or more dimensions: ``tai_fused_step_decay`` in place of ``tai_fused_step``
+exactly when an optimizer has such an entry (restated in tests/fused_step_decay_ref.py).
+
 ``FusedStep`` belongs to one training environment.  The optimizers stay ``torch.optim.Adam`` objects used as state containers
 (``exp_avg``, ``exp_avg_sq``, ``step`` live where the parameters live; ``optimizer_state_dict`` writes ``step`` the way the eager
 optimizer does, ``after_load`` converts it back).  The guard's counters live in the record; the record is copied into a pinned slot
@@ -50,6 +56,79 @@ def scalar_table(lr, beta1, beta2, length):
     return step_size, bc2s
 
 
+SCHEDULES = ('constant', 'step', 'cosine')
+
+
+class Schedule(collections.namedtuple('Schedule', 'kind warmup_updates decay_every gamma min_ratio')):
+    """``--lr_schedule kind --warmup_updates W --lr_decay_every E --lr_gamma g --lr_min_ratio r``; the defaults are the constant rate."""
+    __slots__ = ()
+
+    def __new__(cls, kind='constant', warmup_updates=0, decay_every=10000, gamma=0.5, min_ratio=0.01):
+        return super().__new__(cls, str(kind), int(warmup_updates), int(decay_every), float(gamma), float(min_ratio))
+
+    @property
+    def on(self):
+        return self.kind != 'constant' or self.warmup_updates > 0
+
+    def check(self):
+        """Raises ValueError naming the flag whose value is refused."""
+        if self.kind not in SCHEDULES:
+            raise ValueError('--lr_schedule must be one of %s, found %r' % (', '.join(SCHEDULES), self.kind))
+        if self.warmup_updates < 0:
+            raise ValueError('--warmup_updates must not be negative, found %r' % (self.warmup_updates,))
+        if self.decay_every < 1:
+            raise ValueError('--lr_decay_every must be at least 1, found %r' % (self.decay_every,))
+        if not 0.0 <= self.gamma <= 1.0:
+            raise ValueError('--lr_gamma must lie in [0, 1], found %r' % (self.gamma,))
+        if not 0.0 <= self.min_ratio <= 1.0:
+            raise ValueError('--lr_min_ratio must lie in [0, 1], found %r' % (self.min_ratio,))
+
+
+def check_weight_decay(wd):
+    if not (float(wd) >= 0.0 and float(wd) != float('inf')):
+        raise ValueError('--weight_decay must be finite and not negative, found %r' % (wd,))
+
+
+def needs_fused_step(schedule, weight_decay):
+    """The words with which a run without ``--fused_step`` is refused, or None."""
+    schedule = schedule or Schedule()
+    for on, flag in ((schedule.kind != 'constant', '--lr_schedule %s' % schedule.kind), (schedule.warmup_updates > 0, '--warmup_updates'),
+                     (weight_decay > 0.0, '--weight_decay')):
+        if on:
+            return '%s needs --fused_step: the schedule is the fused optimizer step\'s scalar table, the decay a line of its kernel' % flag
+    return None
+
+
+def learning_rates(lr, length, schedule=None, n_steps=None):
+    """lr(t') for t' = 1 ... length as Python floats (include/tai_sepconv.h); ``n_steps``: the N of the cosine, ``length`` by default."""
+    sc = schedule or Schedule()
+    L, W, N = float(lr), sc.warmup_updates, int(length if n_steps is None else n_steps)
+    out = []
+    for t in range(1, length + 1):
+        warm = t / W if t <= W else 1.0
+        if sc.kind == 'step':
+            s = sc.gamma ** ((t - 1) // sc.decay_every)
+        elif sc.kind == 'cosine' and t > W:
+            u = min(1.0, (t - W) / max(1, N - W))
+            s = sc.min_ratio + (1.0 - sc.min_ratio) * (0.5 * (1.0 + math.cos(math.pi * u)))
+        else:
+            s = 1.0
+        out.append((L * warm) * s)
+    return out
+
+
+def scheduled_table(lr, beta1, beta2, length, schedule=None, weight_decay=0.0, n_steps=None):
+    """(step_size, bc2s, decay): ``scalar_table`` with lr(t') of the schedule in place of lr, and decay[t'] = f32(lr(t') * wd).  With the
+    constant schedule, no warm-up and no decay the first two are ``scalar_table``'s bit for bit."""
+    step_size, bc2s, decay = np.empty(length, np.float32), np.empty(length, np.float32), np.empty(length, np.float32)
+    beta1, beta2, wd = float(beta1), float(beta2), float(weight_decay)
+    for t, rate in enumerate(learning_rates(lr, length, schedule, n_steps), 1):
+        step_size[t - 1] = np.float32(rate / (1.0 - beta1 ** t))
+        bc2s[t - 1] = np.float32(math.sqrt(1.0 - beta2 ** t))
+        decay[t - 1] = np.float32(rate * wd)
+    return step_size, bc2s, decay
+
+
 def constants(beta1, beta2, ema_decay=None):
     d = 0.0 if ema_decay is None else float(ema_decay)
     return Constants(np.float32(1.0 - float(beta1)), np.float32(float(beta2)), np.float32(1.0 - float(beta2)), np.float32(1e-8),
@@ -61,10 +140,13 @@ def check_ema_decay(d):
         raise ValueError('--ema_decay must lie strictly between 0 and 1, found %r' % (d,))
 
 
-def host_step(p, g, m, v, e, c, step_size, bc2s, k):
-    """The definition on float32 numpy arrays, in place (``e`` may be None; ``g`` is left alone)."""
+def host_step(p, g, m, v, e, c, step_size, bc2s, k, decay=None):
+    """The definition on float32 numpy arrays, in place (``e`` may be None; ``g`` is left alone).  ``decay``: decay[t'] for an entry
+    that decays (p1 = p - (decay * p) first), None for one that does not: its p is multiplied by nothing."""
     c, step_size, bc2s = np.float32(c), np.float32(step_size), np.float32(bc2s)
     with np.errstate(all='ignore'):
+        if decay is not None:
+            np.subtract(p, np.multiply(np.float32(decay), p), out=p)
         g1 = np.multiply(g, c) if c < np.float32(1) else g
         d = np.subtract(g1, m)
         np.add(m, np.multiply(k.w1, d), out=m)
@@ -139,12 +221,13 @@ class _Tables(object):
     """Device buffers of one optimizer's tables (the statistics' rows of four, the step's rows of eight), filled through pinned memory so
     that a change of a gradient's address costs a copy the host does not wait for."""
 
-    def __init__(self, n, n_segments, device):
+    def __init__(self, n, n_segments, device, with_flags=False):
         from . import _native
-        self.n, self.n_segments = n, n_segments
-        self.both = torch.empty(12 * n, dtype=torch.int64, device=device)
-        self.stats, self.rows = self.both[:4 * n], self.both[4 * n:]
-        self.pinned = [torch.empty(12 * n, dtype=torch.int64).pin_memory() for _ in range(2)]
+        self.n, self.n_segments, self.with_flags = n, n_segments, bool(with_flags)
+        words = (13 if with_flags else 12) * n           # with_flags: tai_fused_step_decay's word per entry behind the rows, one upload
+        self.both = torch.empty(words, dtype=torch.int64, device=device)
+        self.stats, self.rows, self.flags = self.both[:4 * n], self.both[4 * n:12 * n], self.both[12 * n:]
+        self.pinned = [torch.empty(words, dtype=torch.int64).pin_memory() for _ in range(2)]
         self.events = [None, None]
         self.flip = 0
         self.host = None
@@ -152,8 +235,8 @@ class _Tables(object):
         self.workspace = torch.empty(nbytes // 8 + 2, dtype=torch.int64, device=device)
         self.result = torch.zeros(5 * (n + 1), dtype=torch.int32, device=device)      # grad_guard._Buffers' layout
 
-    def upload(self, stats_rows, step_rows_):
-        host = np.concatenate([stats_rows.reshape(-1), step_rows_.reshape(-1)])
+    def upload(self, stats_rows, step_rows_, flags=None):
+        host = np.concatenate([stats_rows.reshape(-1), step_rows_.reshape(-1)] + ([flags] if self.with_flags else []))
         if self.host is not None and np.array_equal(self.host, host):
             return
         i = self.flip
@@ -168,17 +251,27 @@ class _Tables(object):
 
 
 class _Optimizer(object):
-    def __init__(self, module, optimizer, k, step_size, bc2s, device):
+    def __init__(self, module, optimizer, k, step_size, bc2s, device, decay=None, rates=None):
         self.module, self.optimizer, self.k = module, optimizer, k
         self.step_size, self.bc2s = step_size, bc2s
-        self.scalars = torch.from_numpy(np.concatenate([step_size, bc2s])).to(device) if device.type == 'cuda' else None
+        self.decay = decay                           # decay[t' - 1] (fp32) of an optimizer whose weights decay, else None
+        self.rates = rates                           # lr(t') as Python floats, for the printed line
+        rows = [step_size, bc2s] + ([decay] if decay is not None else [])
+        self.scalars = torch.from_numpy(np.concatenate(rows)).to(device) if device.type == 'cuda' else None
         self.names = []
         self.tables = None
 
 
 class FusedStep(object):
-    def __init__(self, device, max_steps, guard=None, ema_decay=None):
+    def __init__(self, device, max_steps, guard=None, ema_decay=None, schedule=None, weight_decay=0.0):
         check_ema_decay(ema_decay)
+        self.schedule = schedule or Schedule()
+        self.schedule.check()
+        check_weight_decay(weight_decay)
+        self.weight_decay = float(weight_decay)
+        self.max_steps = int(max_steps)              # the N of the cosine
+        self._base_lr = {}                           # optimizer -> the rate its table was built from
+        self.last_rate = {}                          # optimizer -> lr(t') of its last taken step, as of the last record applied
         self.device = torch.device(device)
         self.on_device = self.device.type == 'cuda'
         self.guard = guard
@@ -202,9 +295,47 @@ class FusedStep(object):
         if group['eps'] != 1e-8 or group['weight_decay'] != 0 or group['amsgrad'] or group.get('maximize') or group.get('capturable'):
             raise ValueError('fused step: the definition is plain Adam with eps 1e-8 (no weight decay, amsgrad, maximize, capturable)')
         beta1, beta2 = group['betas']
-        step_size, bc2s = scalar_table(group['lr'], beta1, beta2, self.table_len)
         k = constants(beta1, beta2, self.ema_decay if which == 'G' else None)
-        self._opt[which] = _Optimizer(module, optimizer, k, step_size, bc2s, self.device)
+        self._base_lr[which] = float(group['lr'])
+        if not self.scheduled:
+            step_size, bc2s = scalar_table(group['lr'], beta1, beta2, self.table_len)
+            self._opt[which] = _Optimizer(module, optimizer, k, step_size, bc2s, self.device)
+            return
+        # the decay is the generator's alone (the discriminator's weights are spectrally normalised); the torch optimizer's own
+        # weight_decay stays 0: it is a state container here
+        wd = self.weight_decay if which == 'G' else 0.0
+        step_size, bc2s, decay = scheduled_table(group['lr'], beta1, beta2, self.table_len, self.schedule, wd, self.max_steps)
+        self._opt[which] = _Optimizer(module, optimizer, k, step_size, bc2s, self.device, decay if wd > 0.0 else None,
+                                      learning_rates(group['lr'], self.table_len, self.schedule, self.max_steps) if self.schedule.on else None)
+
+    @property
+    def scheduled(self):
+        """A schedule, a warm-up or a decay is on: the tables are ``scheduled_table``'s and the run state records the settings."""
+        return self.schedule.on or self.weight_decay > 0.0
+
+    def settings(self):
+        """What a continuation must repeat (run_state's ``lr_schedule``), or None without a schedule, a warm-up and a decay."""
+        if not self.scheduled:
+            return None
+        sc = self.schedule
+        out = {'lr_schedule': sc.kind, 'warmup_updates': sc.warmup_updates, 'lr_decay_every': sc.decay_every, 'lr_gamma': sc.gamma,
+               'lr_min_ratio': sc.min_ratio, 'weight_decay': self.weight_decay, 'max_iter': self.max_steps}
+        out.update(('lr' if which == 'G' else 'lr_D', lr) for which, lr in self._base_lr.items())
+        return out
+
+    def check_continues(self, saved):
+        """Refuse (ValueError) a continuation whose settings are not those the snapshot's run recorded; both are named."""
+        mine = self.settings()
+        if saved != mine:
+            show = lambda s: 'no schedule, warm-up or decay' if s is None else ' '.join('--%s %s' % kv for kv in sorted(s.items()))
+            raise ValueError('the snapshot was written with %s, this run has %s: another schedule is another run, it cannot be continued '
+                             'exactly' % (show(saved), show(mine)))
+
+    def rates_suffix(self):
+        """`` lr_G= lr_D=`` of the last taken steps for a printed line (after ``read``), '' without a schedule or a warm-up."""
+        if not self.schedule.on:
+            return ''
+        return ''.join(' lr_%s=%.6g' % (which, self.last_rate.get(which, 0.0)) for which in 'GD' if which in self._opt)
 
     def _entries(self, which):
         o = self._opt[which]
@@ -226,15 +357,18 @@ class FusedStep(object):
                     self.ema[n] = (p if src is None else src).detach().to(p.device, torch.float32).clone().reshape(-1)
         o.names = [n for n, _ in named]
         params = [p.detach() for _, p in named]
+        # the entries that decay: the weights (two or more dimensions) of an optimizer with a decay table, never a bias
+        flags = np.array([int(o.decay is not None and p.dim() >= 2) for _, p in named], np.int64)
         return (params, [p.grad.detach() for _, p in named], [state[p]['exp_avg'] for _, p in named],
                 [state[p]['exp_avg_sq'] for _, p in named], [state[p]['step'] for _, p in named],
-                [self.ema[n] if with_ema else None for n, _ in named])
+                [self.ema[n] if with_ema else None for n, _ in named], flags)
 
     # ---- the step
     def step(self, which, last):
         """The step of optimizer ``which`` ('G' or 'D') on the gradients its parameters hold now; ``last``: it is the update's last."""
         o, w = self._opt[which], WHICH[which]
-        params, grads, ms, vs, steps, emas = self._entries(which)
+        params, grads, ms, vs, steps, emas, flags = self._entries(which)
+        decays = bool(flags.any())                       # tai_fused_step_decay exactly then; tai_fused_step otherwise
         guard = self.guard
         max_norm = 0.0 if guard is None or guard.clip_grad_norm is None else guard.clip_grad_norm
         patience = NO_PATIENCE if guard is None else guard.patience
@@ -245,10 +379,11 @@ class FusedStep(object):
             host_verdict(self.rec, sumsq, nonfinite, max_norm, w, last, patience, self.table_len)
             if self.rec[R_VERDICT + w] != SKIPPED:
                 t, c = int(self.rec[R_TPRIME + w]), record_coefficient(self.rec, w)
-                for p, g, m, v, s, e in zip(params, grads, ms, vs, steps, emas):
+                for p, g, m, v, s, e, f in zip(params, grads, ms, vs, steps, emas, flags):
                     if p.numel():
                         host_step(p.numpy().reshape(-1), g.numpy().reshape(-1), m.numpy().reshape(-1), v.numpy().reshape(-1),
-                                  None if e is None else e.numpy(), c, o.step_size[t - 1], o.bc2s[t - 1], o.k)
+                                  None if e is None else e.numpy(), c, o.step_size[t - 1], o.bc2s[t - 1], o.k,
+                                  o.decay[t - 1] if f else None)
                     s.fill_(float(t))
         else:
             from . import _native
@@ -256,11 +391,11 @@ class FusedStep(object):
             n = rows.shape[0]
             stats_rows = np.ascontiguousarray(rows[:, [1, 6, 6, 7]])
             stats_rows[:, 2] = 0
-            if o.tables is None or (o.tables.n, o.tables.n_segments) != (n, n_segments):
-                o.tables = _Tables(n, n_segments, self.device)
+            if o.tables is None or (o.tables.n, o.tables.n_segments, o.tables.with_flags) != (n, n_segments, decays):
+                o.tables = _Tables(n, n_segments, self.device, with_flags=decays)
             tb = o.tables
             with torch.cuda.device(self.device):
-                tb.upload(stats_rows, rows)
+                tb.upload(stats_rows, rows, flags)
                 sumsq_ptr = bad_ptr = None
                 if guard is not None:
                     base = tb.result.data_ptr()
@@ -269,9 +404,14 @@ class FusedStep(object):
                                    base, base + 16 * (n + 1), bad_ptr)
                 _native.launch('tai_step_verdict', self.device, sumsq_ptr, bad_ptr, n, float(max_norm), w, int(bool(last)), patience,
                                self.table_len, self.rec)
-                _native.launch('tai_fused_step', self.device, tb.rows, rows.ctypes.data, n, n_segments, o.scalars, self.table_len,
-                               float(o.k.w1), float(o.k.b2), float(o.k.w2), float(o.k.eps), float(o.k.wE), self.rec, w, int(NT_LOADS),
-                               int(self.blocks), None)
+                if decays:
+                    _native.launch('tai_fused_step_decay', self.device, tb.rows, rows.ctypes.data, tb.flags, flags.ctypes.data, n, n_segments,
+                                   o.scalars, self.table_len, float(o.k.w1), float(o.k.b2), float(o.k.w2), float(o.k.eps), float(o.k.wE),
+                                   self.rec, w, int(self.blocks), None)
+                else:
+                    _native.launch('tai_fused_step', self.device, tb.rows, rows.ctypes.data, n, n_segments, o.scalars, self.table_len,
+                                   float(o.k.w1), float(o.k.b2), float(o.k.w2), float(o.k.eps), float(o.k.wE), self.rec, w, int(NT_LOADS),
+                                   int(self.blocks), None)
         # the weights were written through raw pointers (numpy views on the host): no version counter moved.  Whatever the verdict --
         # the host does not know it -- no derived form of this module's weights stays valid; the other module's forms are left alone
         conv_ops.invalidate_derived(o.module)
@@ -336,6 +476,10 @@ class FusedStep(object):
         if rec[R_OVERFLOW]:
             raise RuntimeError('fused step: an optimizer was asked for more than the %d steps its scalar table holds (--max_iter)'
                                % self.table_len)
+        if self.schedule.on:                             # the rate of the last taken step: t is the number of steps made
+            for which, o in self._opt.items():
+                t = int(rec[R_T + WHICH[which]])
+                self.last_rate[which] = o.rates[t - 1] if t >= 1 else 0.0
         g = self.guard
         if g is None:
             return

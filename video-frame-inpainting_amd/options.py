@@ -129,6 +129,23 @@ class TrainOptions(BaseOptions):
                        help="(this build, with --fused_step) keep an exponential moving average of the generator's weights, "
                             'e <- e + (1 - d)(p - e) after every step, 0 < d < 1: snapshots gain generator_ema, validation scores the '
                             'averaged weights and model_best.ckpt is chosen by them (predict.py --weights ema)')
+        g.add_argument('--lr_D', type=float, default=None, metavar='X',
+                       help="(this build) the discriminator's base learning rate; default: --lr.  Works with or without --fused_step")
+        g.add_argument('--lr_schedule', type=str, default='constant', choices=['constant', 'step', 'cosine'],
+                       help='(this build, with --fused_step) the learning rate over the steps TAKEN (a skipped step does not advance it), '
+                            'for both optimizers: constant (default), step = x --lr_gamma every --lr_decay_every steps, cosine = from the '
+                            'base rate down to --lr_min_ratio of it at --max_iter.  The schedule is the fused step\'s scalar table '
+                            '(include/tai_sepconv.h); printed lines gain lr_G= lr_D=')
+        g.add_argument('--warmup_updates', type=int, default=0, metavar='W',
+                       help='(this build, with --fused_step) the rate rises linearly over the first W steps, t / W of the base rate at step t')
+        g.add_argument('--lr_decay_every', type=int, default=10000, metavar='E', help='(with --lr_schedule step) steps between two decays; >= 1')
+        g.add_argument('--lr_gamma', type=float, default=0.5, metavar='g', help='(with --lr_schedule step) the factor of a decay; 0 <= g <= 1')
+        g.add_argument('--lr_min_ratio', type=float, default=0.01, metavar='r',
+                       help='(with --lr_schedule cosine) the final rate over the base rate; 0 <= r <= 1')
+        g.add_argument('--weight_decay', type=float, default=0.0, metavar='wd',
+                       help="(this build, with --fused_step) decoupled weight decay (AdamW), p <- p - lr wd p in front of the Adam update, for "
+                            "the generator's parameters with two or more dimensions (convolution and ConvLSTM weights): never a bias, never "
+                            'the discriminator, whose weights are spectrally normalised.  One HIP launch, tai_fused_step_decay.  0 = off')
         g.add_argument('--ssim_weight', type=float, default=0.0, metavar='G',
                        help="(this build) add G (1 - mean SSIM) of every prediction against the ground truth to the generator's loss "
                             '(losses.SSIMLoss: 7x7 window, float frames in [0, 1] with L = 1, unclipped, float64 window arithmetic; loss and '

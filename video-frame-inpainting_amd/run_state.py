@@ -17,6 +17,9 @@ state digest that says whether two states are.
   ema          (only with train.py --ema_decay) the names of the generator parameters that carry an average, in table order; the averaged
                values are the snapshot's ``generator_ema``, and they are the entries behind the guard's in the digest's table then, and
                only then
+  lr_schedule  (only with train.py --lr_schedule / --warmup_updates / --weight_decay) the settings of the fused step's scalar table
+               (fused_step.FusedStep.settings: both base rates, the schedule, W, E, g, r, wd and the N of --max_iter); a continuation
+               with others is refused.  Nothing enters the digest: the schedule's position t' is the optimizer state's ``step``
 ``restore(env, run_state)`` puts all of it back, the generator states LAST, and returns this rank's 'data' entry.
 
 The digest (``tai_state_digest``, csrc/state_digest.hip.inc) reads every tensor of the state once, where it lives: about 0.5 GB of
@@ -301,6 +304,9 @@ def capture(env):
         state['guard'] = _guard_counters(env)
     if _ema_entries(env) is not None:
         state['ema'] = list(env.fused.ema)
+    fused = getattr(env, 'fused', None)
+    if fused is not None and fused.settings() is not None:
+        state['lr_schedule'] = fused.settings()
     return state
 
 
