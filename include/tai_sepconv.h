@@ -739,6 +739,30 @@ int tai_clip_from_frames_aug(const unsigned char* frames, long long frames_bytes
                              const float* tables, int n_tables, const float* levels, float* out, int N, int c_dim, int H, int W, int pad_h,
                              int pad_w, void* stream /* the HIP stream */);
 
+/* Per-frame damage statistics of a whole video in one pass (csrc/frame_scan.hip.inc; video_frame_inpainting_amd/restore.py classifies
+ * frames by them; tests/frame_scan_ref.py restates them in numpy; no counterpart in the reference, whose predict.py is told where the gap is).
+ *   frames   device buffer of n_frames uint8 frames of frame_bytes bytes each (h w c in any layout), back to back; the base address may
+ *            have any alignment, and frame_bytes is any number in 1 .. 2^31 - 1, so successive frames may take every alignment modulo 16;
+ *   stats    device int64 [n_frames][4], 8-byte aligned.  Row i, over the bytes v_i[k] of frame i, all exact integers:
+ *              0: s1    = sum_k v_i[k];
+ *              1: s2    = sum_k v_i[k] * v_i[k];
+ *              2: sad   = sum_k |v_i[k] - v_{i-1}[k]|                  (0 for i = 0);
+ *              3: ndiff = #{k : |v_i[k] - v_{i-1}[k]| > tol}           (0 for i = 0), 0 <= tol <= 254;
+ *   workspace  tai_frame_scan_workspace_bytes(n_frames, frame_bytes) bytes, 8-byte aligned (per-segment partial sums).
+ * The sums are integers, so every row has one correct bit pattern whatever the order of summation.  Row i depends on frames i - 1 and i
+ * only: not on n_frames, not on the base alignment, not on where the scanned range starts -- scanning frames [j, n) gives row 0 =
+ * (s1, s2, 0, 0) of frame j and then rows j + 1 .. of scanning [0, n).
+ * Two launches (a walk that reads every byte 1 + 1/8 times and a per-frame finish; no atomics), no allocation, copy or synchronisation:
+ * asynchronous on the stream and capturable into a hipGraph.
+ * TAI_SEPCONV_EINVAL with a message naming the argument, nothing launched: frames, stats or workspace null; n_frames < 1; frame_bytes < 1
+ * or >= 2^31; n_frames x frame_bytes above 2^40; tol outside 0..254; stats or workspace not 8-byte aligned.  The workspace query returns
+ * TAI_SEPCONV_EINVAL for the same sizes.
+ * The last parameter is the HIP stream, spelled `stream` for the reason given at tai_temporal_loss; the refusals are pinned by
+ * tests/test_restore_cpu.py. */
+long long tai_frame_scan_workspace_bytes(long long n_frames, long long frame_bytes);
+int tai_frame_scan(const unsigned char* frames, long long n_frames, long long frame_bytes, int tol, long long* stats /* [n_frames][4] */,
+                   void* workspace, void* stream /* the HIP stream */);
+
 /* A 64-bit digest of a training state where it lives (csrc/state_digest.hip.inc; video_frame_inpainting_amd/run_state.py builds the
  * table; no counterpart in the reference, whose snapshots carry no check).  On the raw 32-bit words, integer arithmetic modulo 2^64 only:
  *   mix(z): z += 0x9E3779B97F4A7C15; z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9; z = (z ^ (z >> 27)) * 0x94D049BB133111EB; z ^ (z >> 31)

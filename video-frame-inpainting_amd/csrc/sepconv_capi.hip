@@ -39,6 +39,7 @@
 #include "census_loss.hip.inc"
 #include "clip_pipeline.hip.inc"
 #include "clip_augment.hip.inc"
+#include "frame_scan.hip.inc"
 #include "state_digest.hip.inc"
 #include "grad_stats.hip.inc"
 #include "fused_step.hip.inc"
@@ -143,7 +144,7 @@ void wino_div_magic(long long d, unsigned& m, unsigned& sh) {
 
 extern "C" {
 
-int tai_sepconv_version(void) { return 870; }
+int tai_sepconv_version(void) { return 880; }
 
 const char* tai_sepconv_last_error(void) { return g_err; }
 
@@ -163,4 +164,5 @@ const char* tai_sepconv_source_hash(void) { return k_source_hash + 16; }
 #include "capi_wino.inc"
 #include "capi_bf16.inc"
 #include "capi_image.inc"
+#include "capi_scan.inc"
 #include "capi_tables.inc"

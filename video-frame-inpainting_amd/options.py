@@ -244,3 +244,35 @@ class TestOptions(BaseOptions):
                        help='(this build) precision of the inference convolutions: fp32 (default) or bf16 = opt-in: the layers with at '
                             'least 16 input and output channels and k in {3, 5, 7} take bf16 operands (rounded to nearest even), exact '
                             'products and fp32 sums (conv_ops.set_conv_precision)')
+
+
+class RestoreOptions(BaseOptions):
+    """restore.py: the model and snapshot flags of TestOptions, and what the repair of one damaged video needs."""
+
+    def __init__(self):
+        super().__init__()
+        g = self.parser.add_argument_group('Snapshot parameters')
+        g.add_argument('--snapshot_file_name', type=str, default='model_best.ckpt')
+        g.add_argument('--random_init', action='store_true', help='skip the snapshot load and keep the seeded xavier initialisation')
+        g.add_argument('--weights', type=str, default='raw', choices=['raw', 'ema'],
+                       help="which weights of the snapshot to run: raw = its generator (default), ema = its generator_ema")
+        g.add_argument('--conv_precision', type=str, default='fp32', choices=['fp32', 'bf16'],
+                       help='precision of the inference convolutions (as predict.py)')
+        g = self.parser.add_argument_group('Restoration parameters')
+        g.add_argument('--input', type=str, required=True,
+                       help='the damaged video: a directory of frame images (names that all end in a number are indexed by that number, '
+                            'absent numbers are missing frames), an AVI (zero-length chunks are missing frames), a .npy / .npz frame array')
+        g.add_argument('--output_dir', type=str, required=True, help='where frame_%%06d.png and report.json are written')
+        g.add_argument('--detect', type=str, default='missing',
+                       help='comma-separated detectors out of missing,dup,blank (or none).  missing = the source has no such frame; '
+                            'dup = at most --dup_share of the bytes differ from the previous frame by more than --dup_tol (defaults: an '
+                            'exact repeat, the signature of a dropped frame -- note that this flags EVERY frame of a static scene, by '
+                            'definition); blank = the variance of the frame is at most --blank_var (default: a constant frame)')
+        g.add_argument('--gaps', type=str, default='', metavar='a-b,c-d',
+                       help='frames to treat as damaged whatever the detectors say (0-based, inclusive)')
+        g.add_argument('--dup_tol', type=int, default=0, help='(dup) a byte differs when it moved by more than this; 0..254')
+        g.add_argument('--dup_share', type=float, default=0.0, help='(dup) share of the bytes that may differ in a repeat; 0..1')
+        g.add_argument('--blank_var', type=float, default=0.0, help='(blank) largest variance, in squared grey levels, of a blank frame')
+        g.add_argument('--max_T', type=int, default=None, help='longest gap that is filled; default --T')
+        g.add_argument('--chunk_frames', type=int, default=256, help='frames decoded, uploaded and scanned at a time')
+        g.add_argument('--dry_run', action='store_true', help='scan, plan and write report.json only; needs no GPU')

@@ -94,6 +94,10 @@ class AviVideo(object):
     def get_length(self):
         return len(self._frames)
 
+    def dropped_frames(self):
+        """Indexes of the frames whose chunk has length 0: the frames ``get_data`` answers with the previous picture."""
+        return [i for i, (_, size) in enumerate(self._frames) if size == 0]
+
     def get_data(self, index):
         if not 0 <= index < len(self._frames):
             raise IndexError('frame %d of %d in %s' % (index, len(self._frames), self._filename))
