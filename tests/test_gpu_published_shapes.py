@@ -13,6 +13,8 @@ from video_frame_inpainting_amd import metrics, synthetic
 from video_frame_inpainting_amd.graph import GraphedForward
 from oracle import tai_oracle, train_oracle
 
+import kink_sides  # noqa: E402
+
 pytestmark = pytest.mark.gpu
 DEV = 'cuda:0'
 KEYS = ('pred', 'pred_forward', 'pred_backward', 'interp_net_outputs_1', 'interp_net_outputs_2')
@@ -116,30 +118,6 @@ def _color_env(tmp_path, K, T, F, H, W):
     return env, u
 
 
-class _KinkSides(object):
-    """Which side of LeakyReLU's kink each pre-activation of the product's discriminator fell on, per evaluation (4 layers each): the
-    oracle's D half differentiates the same piecewise-linear function (as tests/test_gpu_training.py does)."""
-
-    def __init__(self, monkeypatch):
-        from video_frame_inpainting_amd import sn_discriminator as snd
-        self.layers = []
-        orig = snd._WindowScaledConvLReLU.apply
-
-        def spy(*args):
-            y = orig(*args)
-            self.layers.append((y.detach() > 0).cpu())
-            return y
-        monkeypatch.setattr(snd._WindowScaledConvLReLU, 'apply', staticmethod(spy))
-
-    def masks_of_call(self, call, B):
-        out = {}
-        for li, key in enumerate(train_oracle.SN_CONV_KEYS):
-            m = self.layers[4 * call + li]
-            for t0 in range(m.shape[0] // B):
-                out[(t0, key)] = m[t0 * B:(t0 + 1) * B]
-        return out
-
-
 def _update(env, P, Fo, GT, K, T, F):
     """One G + D update's gradients (the reference's step order, environments.py:348-355, without the optimiser steps)."""
     env.set_train_inputs(P, Fo, GT)
@@ -164,7 +142,9 @@ def test_training_update_at_160x208_matches_the_oracle_runs_in_tree_and_reproduc
     10 x 13 kernel-network bottom, the weight gradients on rows of 26-104 pixels, the discriminator's 10 x 13 space-to-depth layer and the
     two 3-channel layers at full resolution all run in-tree -- and a second identical step gives the same losses and the same bits in
     every discriminator gradient and every gradient of the kernel network and the merge layers (whose 15 x 20 / 10 x 13 planes are the
-    odd-plane route).  The MC-Net generator's gradients of two identical updates differ in the last bits (~2e-7 of their maximum) at the
+    odd-plane route).  Before the oracle's D half takes the product's LeakyReLU sides, all 4 layers of all 3 discriminator evaluations are
+    held to the float64 layer on their own operands (kink_sides.check_layer) at the first, the middle and the last of the 9 windows -- the
+    images at both ends of the batch-stacked planes and one inside; the other 6 windows' layer outputs are the only thing left out.  The MC-Net generator's gradients of two identical updates differ in the last bits (~2e-7 of their maximum) at the
     parent commit's 128 x 128 gray update as well, where no shape of this route occurs: they are held to 1e-5 here."""
     from conftest import DispatchAt, miopen_convolutions
     K, T, F, H, W, B = 4, 3, 4, 160, 208, 2
@@ -176,7 +156,7 @@ def test_training_update_at_160x208_matches_the_oracle_runs_in_tree_and_reproduc
     P, GT, Fo = synthetic.split_clip(clips, K, T, F)
     DispatchAt(monkeypatch, 16)
     odd = _OddPlaneRoutes(monkeypatch)
-    sides = _KinkSides(monkeypatch)
+    sides = kink_sides.DiscriminatorSpy(monkeypatch, kink_sides.ends_and_middle)
     with torch.profiler.profile(activities=[torch.profiler.ProfilerActivity.CPU], record_shapes=True) as prof:
         g1, d1 = _update(env, P, Fo, GT, K, T, F)
     convs = miopen_convolutions(prof)
@@ -184,15 +164,22 @@ def test_training_update_at_160x208_matches_the_oracle_runs_in_tree_and_reproduc
     assert any(H2 == 10 and W2 == 13 for (_, _, H2, W2) in odd.taken), odd.taken
     errs = env.get_current_errors()
     assert len(sides.layers) == 12, len(sides.layers)           # D(fake) in the G loss, D(fake.detach()), D(real): 4 layers each
+    # every layer call of the product against the float64 layer on its own operands, BEFORE its kink sides go anywhere
+    layer_results = kink_sides.check_discriminator_calls(sides)
 
     # the CPU oracle
     keys = [k for k in GRAD_KEYS if k in gen_sd]
     assert len(keys) == len(GRAD_KEYS), sorted(set(GRAD_KEYS) - set(keys))
     disc = train_oracle.DiscriminatorState(disc_sd, u, IP, DISC_T)
     terms, g_ref, _, fake = train_oracle.generator_leg(gen_sd, disc, 3, 4, 51, P, GT, Fo, ALPHA, BETA, keys)
+    disc_own = train_oracle.DiscriminatorState(disc.sd, disc.u, IP, DISC_T)
     d_terms, d_ref = train_oracle.discriminator_leg(disc, fake, P, GT, Fo, sides.masks_of_call(1, B), sides.masks_of_call(2, B))
+    with kink_sides.OracleSides() as own:               # the sides the oracle's own rounding picks: counted against the imposed ones, not bounded
+        train_oracle.discriminator_leg(disc_own, fake, P, GT, Fo)
     losses = {k: float(v) for k, v in list(terms.items()) + list(d_terms.items())}
-    report = []
+    print('\n'.join(['== TAI_color gf_dim 64 B %d K %d T %d F %d %dx%d, 32-clip dispatch' % (B, K, T, F, H, W)] +
+                    kink_sides.report_lines(sides, layer_results, own.differences(sides, B))))
+    report, worst = [], {'G': 0.0, 'D': 0.0}
     for k in sorted(losses):
         rel = abs(errs[k] - losses[k]) / max(abs(losses[k]), 1e-12)
         report.append('%-16s gpu %.7g oracle %.7g rel %.2e' % (k, errs[k], losses[k], rel))
@@ -203,13 +190,16 @@ def test_training_update_at_160x208_matches_the_oracle_runs_in_tree_and_reproduc
         err = float((g1[k].cpu() - g_ref[k]).abs().max())
         report.append('%-44s max|g| %.3e  err/max %.2e' % (k, scale, err / max(scale, 1e-30)))
         assert scale > 1e-7, report[-1]
+        worst['G'] = max(worst['G'], err / scale)
         assert err <= GRAD_RTOL * scale, report[-1]
     for k in sorted(d_ref):
         scale = float(d_ref[k].abs().max())
         err = float((d1[k].cpu() - d_ref[k]).abs().max())
         report.append('%-44s max|g| %.3e  err/max %.2e' % ('D.' + k, scale, err / max(scale, 1e-30)))
         assert scale > 1e-7, report[-1]
+        worst['D'] = max(worst['D'], err / scale)
         assert err <= D_GRAD_RTOL * scale, report[-1]
+    report.append('worst err/max: generator %.2e (bound %.0e)  discriminator %.2e (bound %.0e)' % (worst['G'], GRAD_RTOL, worst['D'], D_GRAD_RTOL))
     print('\n'.join(report))
 
     # the spectral-norm state moved during the step: put it back, then the same step once more -- the same bits

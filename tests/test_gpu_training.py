@@ -13,6 +13,8 @@ from video_frame_inpainting_amd import synthetic
 from video_frame_inpainting_amd.environments import TAITrainingEnvironment
 from oracle import train_oracle
 
+import kink_sides  # noqa: E402
+
 pytestmark = pytest.mark.gpu
 DEV = 'cuda:0'
 ALPHA, BETA, IP, DISC_T = 1.0, 0.02, 3, 3            # options.py:79-80 defaults; exp_args KTH Ip / disc_t
@@ -26,8 +28,11 @@ GRAD_KEYS = ('generator.motion_enc.dyn_conv1.0.weight',      # first convolution
              'kernelnet.moduleConv.0.0.weight', 'kernelnet.moduleUpsample.3.1.weight',
              'kernelnet.moduleVertical1.7.weight', 'kernelnet.moduleHorizontal2.7.bias')
 LOSS_RTOL = 2e-4          # loss terms, relative
-GRAD_RTOL = 5e-3          # generator: max |g_gpu - g_oracle| <= GRAD_RTOL * max |g_oracle| per parameter
-D_GRAD_RTOL = 2e-5        # discriminator, the oracle differentiating on the product's side of every LeakyReLU kink (_KinkSides): measured <= 6.6e-7
+# generator: max |g_gpu - g_oracle| <= GRAD_RTOL * max |g_oracle| per parameter -- full width (measured <= 4.6e-5) and reduced width
+# (measured <= 4.0e-4: profiles/r05_training_parity.txt)
+GRAD_RTOL_FULL, GRAD_RTOL_REDUCED = 5e-4, 1e-3
+D_GRAD_RTOL = 2e-5        # discriminator, the oracle differentiating on the product's side of every LeakyReLU kink (tests/kink_sides.py, which
+                          # first holds every layer call of the product to the float64 layer): measured <= 6.6e-7
                           # (profiles/r05_training_parity.txt; with the oracle's own sides 3.3e-3 -- one element, tests/test_train_oracle_cpu.py)
 
 
@@ -65,40 +70,18 @@ def _oracle_generator_leg(key, gen_sd, disc_sd, u, P, GT, Fo):
     return _ORACLE[key]
 
 
-class _KinkSides(object):
-    """Records, for every discriminator evaluation of the product, which side of LeakyReLU's kink each pre-activation fell on
-    (the sign of the layer's output: LeakyReLU keeps it).  The oracle's D half then differentiates the same piecewise-linear
-    function (train_oracle.DiscriminatorState.forward, ``masks``): one element of conv_layers.0 at rounding distance from zero
-    otherwise decides 3e-3 of that layer's weight gradient (tests/test_train_oracle_cpu.py)."""
-
-    def __init__(self, monkeypatch):
-        from video_frame_inpainting_amd import sn_discriminator as snd
-        self.layers = []
-        orig = snd._WindowScaledConvLReLU.apply
-
-        def spy(*args):
-            y = orig(*args)
-            self.layers.append((y.detach() > 0).cpu())
-            return y
-        monkeypatch.setattr(snd._WindowScaledConvLReLU, 'apply', staticmethod(spy))
-
-    def masks_of_call(self, call, B):
-        """{(window, layer key): bool [B, Co, H, W]} of the ``call``-th discriminator evaluation (4 layers each, windows along the batch)."""
-        out = {}
-        for li, key in enumerate(train_oracle.SN_CONV_KEYS):
-            m = self.layers[4 * call + li]
-            for t0 in range(m.shape[0] // B):
-                out[(t0, key)] = m[t0 * B:(t0 + 1) * B]
-        return out
-
-
-def _step_and_compare(tmp_path, monkeypatch, gf_dim, kf_dim, df_dim, B, K=5, T=5, F=5, H=128, W=128, profile=False, tag=''):
+def _step_and_compare(tmp_path, monkeypatch, gf_dim, kf_dim, df_dim, B, grad_rtol, K=5, T=5, F=5, H=128, W=128, profile=False, tag='',
+                      keep=None):
+    """``keep``: the windows whose discriminator layers are held to the float64 layer (kink_sides.check_layer) before the oracle takes the
+    product's kink sides -- None: every window (the reduced-width cases); kink_sides.ends_and_middle at full width: the first, the middle
+    and the last of the 13 windows of each evaluation (the images at both ends of the batch-stacked planes and one inside).  The other 10
+    windows' layer outputs are the only thing that check leaves out; their sides are imposed all the same."""
     env, u = _seeded_env(tmp_path, gf_dim, kf_dim, df_dim, K, T, F, H, W)
     gen_sd = {k: v.detach().cpu().clone() for k, v in env.generator.state_dict().items()}
     disc_sd = {k: v.detach().cpu().clone() for k, v in env.discriminator.state_dict().items()}
     clips = torch.from_numpy(synthetic.make_clips(B, K + T + F, 1, H, W, synthetic.SEEDS['cfg3']))
     P, GT, Fo = synthetic.split_clip(clips, K, T, F)
-    sides = _KinkSides(monkeypatch)
+    sides = kink_sides.DiscriminatorSpy(monkeypatch, keep)
 
     # the product: the reference's step order (environments.py:348-355) without the two optimiser updates
     import contextlib
@@ -119,16 +102,23 @@ def _step_and_compare(tmp_path, monkeypatch, gf_dim, kf_dim, df_dim, B, K=5, T=5
         d_gpu = {k: p.grad.detach().cpu().clone() for k, p in env.discriminator.named_parameters()}
     errs = env.get_current_errors()
     assert len(sides.layers) == 12, len(sides.layers)           # D(fake) in the G loss, D(fake.detach()), D(real): 4 layers each
+    # every layer call of the product against the float64 layer on its own operands, BEFORE its kink sides go anywhere
+    layer_results = kink_sides.check_discriminator_calls(sides)
 
     terms, g_ref, fake, sd1, u1 = _oracle_generator_leg((gf_dim, kf_dim, df_dim, B, K, T, F, H, W), gen_sd, disc_sd, u, P, GT, Fo)
     disc = train_oracle.DiscriminatorState(sd1, u1, IP, DISC_T)
     d_terms, d_ref = train_oracle.discriminator_leg(disc, fake, P, GT, Fo, sides.masks_of_call(1, B), sides.masks_of_call(2, B))
-    # ... and with the oracle's own rounding deciding the sides, for the record (what the bound had to absorb before)
+    # ... and with the oracle's own rounding deciding the sides, for the record (what the bound had to absorb before; how many of the
+    # imposed sides differ from these is reported, not bounded: with every layer legitimate on its own input, they are the two runs'
+    # slightly different inputs landing on either side of the kink)
     disc_own = train_oracle.DiscriminatorState(sd1, u1, IP, DISC_T)
-    _, d_own = train_oracle.discriminator_leg(disc_own, fake, P, GT, Fo)
+    with kink_sides.OracleSides() as own:
+        _, d_own = train_oracle.discriminator_leg(disc_own, fake, P, GT, Fo)
     losses = {k: float(v) for k, v in list(terms.items()) + list(d_terms.items())}
 
-    report = ['== %s gf_dim %d B %d K %d T %d F %d %dx%d' % (tag, gf_dim, B, K, T, F, H, W)]
+    print('\n'.join(['== %s gf_dim %d B %d K %d T %d F %d %dx%d' % (tag, gf_dim, B, K, T, F, H, W)] +
+                    kink_sides.report_lines(sides, layer_results, own.differences(sides, B))))
+    report = []
     worst = {'G': 0.0, 'D': 0.0, 'D own sides': 0.0}
     for k in sorted(losses):
         rel = abs(errs[k] - losses[k]) / max(abs(losses[k]), 1e-12)
@@ -141,7 +131,7 @@ def _step_and_compare(tmp_path, monkeypatch, gf_dim, kf_dim, df_dim, B, K=5, T=5
         report.append('%-44s max|g| %.3e  err/max %.2e' % (k, scale, err / max(scale, 1e-30)))
         assert scale > 1e-7, report[-1]
         worst['G'] = max(worst['G'], err / scale)
-        assert err <= GRAD_RTOL * scale, report[-1]
+        assert err <= grad_rtol * scale, report[-1]
     for k in sorted(d_ref):
         scale = float(d_ref[k].abs().max())
         err = float((d_gpu[k] - d_ref[k]).abs().max())
@@ -152,7 +142,7 @@ def _step_and_compare(tmp_path, monkeypatch, gf_dim, kf_dim, df_dim, B, K=5, T=5
         worst['D'], worst['D own sides'] = max(worst['D'], err / scale), max(worst['D own sides'], own / scale)
         assert err <= D_GRAD_RTOL * scale, report[-1]
     report.append('worst err/max: generator %.2e (bound %.0e)  discriminator %.2e (bound %.0e; %.2e with the oracle deciding the kink sides itself)'
-                  % (worst['G'], GRAD_RTOL, worst['D'], D_GRAD_RTOL, worst['D own sides']))
+                  % (worst['G'], grad_rtol, worst['D'], D_GRAD_RTOL, worst['D own sides']))
     # the discriminator's weights were renormalised 3 x 13 times in place on both sides: same end state
     for k, v in env.discriminator.state_dict().items():
         ref = disc.sd[k]
@@ -164,12 +154,12 @@ def _step_and_compare(tmp_path, monkeypatch, gf_dim, kf_dim, df_dim, B, K=5, T=5
 
 
 def test_training_step_cfg3_geometry_reduced_width(tmp_path, monkeypatch):
-    _step_and_compare(tmp_path, monkeypatch, gf_dim=8, kf_dim=4, df_dim=8, B=2)
+    _step_and_compare(tmp_path, monkeypatch, gf_dim=8, kf_dim=4, df_dim=8, B=2, grad_rtol=GRAD_RTOL_REDUCED)
 
 
 def test_training_step_full_width(tmp_path, monkeypatch):
     """TAI_gray as configs[2] trains it (gf_dim 64, kf_dim 32, df_dim 64), B = 2."""
-    _step_and_compare(tmp_path, monkeypatch, gf_dim=64, kf_dim=32, df_dim=64, B=2)
+    _step_and_compare(tmp_path, monkeypatch, gf_dim=64, kf_dim=32, df_dim=64, B=2, grad_rtol=GRAD_RTOL_FULL, keep=kink_sides.ends_and_middle)
 
 
 def test_training_step_full_width_at_the_32_clip_dispatch(tmp_path, monkeypatch, dispatch_at_32_clips):
@@ -179,7 +169,8 @@ def test_training_step_full_width_at_the_32_clip_dispatch(tmp_path, monkeypatch,
     send a 2-clip batch to MIOpen (conv_ops.WINO_MIN_WORKGROUPS).  Same oracle, same bounds; and no ATen convolution ran at all
     (environments.py:348-379, mcnet.py:259-294, SNDiscriminator.py:113-133)."""
     from conftest import miopen_convolutions
-    _, prof = _step_and_compare(tmp_path, monkeypatch, gf_dim=64, kf_dim=32, df_dim=64, B=2, profile=True, tag='32-clip dispatch')
+    _, prof = _step_and_compare(tmp_path, monkeypatch, gf_dim=64, kf_dim=32, df_dim=64, B=2, grad_rtol=GRAD_RTOL_FULL, profile=True,
+                                tag='32-clip dispatch', keep=kink_sides.ends_and_middle)
     # since round 5 that includes the discriminator (its 4 x 4 stride-2 layers as 3 x 3 layers on space-to-depth planes) and the weight
     # gradients of the 8 x 8 / 4 x 4 layers (rows widened to the weight-gradient kernel's 16 pixels): no ATen convolution in the update
     convs = miopen_convolutions(prof)
@@ -216,7 +207,7 @@ def test_forward_train_of_32_clips_equals_the_2_clip_forward_at_its_dispatch(tmp
 
 def test_training_step_short_context_nonsquare(tmp_path, monkeypatch):
     """sample_KTF draws K, F >= 2 and T >= 1 per step (environments.py:417-427): K != F (no direction fusion), T = 2."""
-    _step_and_compare(tmp_path, monkeypatch, gf_dim=8, kf_dim=4, df_dim=8, B=2, K=4, T=2, F=3, H=64, W=96)
+    _step_and_compare(tmp_path, monkeypatch, gf_dim=8, kf_dim=4, df_dim=8, B=2, grad_rtol=GRAD_RTOL_REDUCED, K=4, T=2, F=3, H=64, W=96)
 
 
 @pytest.mark.gpu

@@ -709,8 +709,11 @@ def w43_data(c, seed=1, outliers=True):
 
 
 def tile_mag(mag, tile=4):
-    """The largest magnitude sum of each tile x tile output tile, at every pixel of that tile."""
-    return F.interpolate(F.max_pool2d(mag, tile), scale_factor=tile, mode='nearest')
+    """The largest magnitude sum of each tile x tile output tile, at every pixel of that tile (tiles counted from the plane's origin; a
+    plane whose side is no multiple of ``tile`` ends in partial tiles)."""
+    H, W = mag.shape[-2:]
+    m = F.max_pool2d(mag, tile, ceil_mode=True)
+    return m.repeat_interleave(tile, -2).repeat_interleave(tile, -1)[..., :H, :W]
 
 
 def tile_ratio(got, ref, mag):
