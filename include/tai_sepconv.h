@@ -763,6 +763,66 @@ long long tai_frame_scan_workspace_bytes(long long n_frames, long long frame_byt
 int tai_frame_scan(const unsigned char* frames, long long n_frames, long long frame_bytes, int tol, long long* stats /* [n_frames][4] */,
                    void* workspace, void* stream /* the HIP stream */);
 
+/* The frame scan's four integers per BLOCK of every frame (csrc/block_scan.hip.inc; restore.py --detect_blocks tells partly damaged frames
+ * by them; tests/block_scan_ref.py restates them in numpy; no counterpart in the reference).
+ *   frames   device buffer of n_frames uint8 frames [h][w][c], back to back, c in 1..4; the base address may have any alignment and w c is
+ *            any number, so rows take every alignment modulo 16;
+ *   bs       block size in pixels, 8, 16 or 32; Bh = ceil(h / bs), Bw = ceil(w / bs); block (by, bx) is the pixels
+ *            [by bs, min(h, by bs + bs)) x [bx bs, min(w, bx bs + bs)) with all their channels -- edge blocks are ragged and hold fewer bytes;
+ *   stats    device int64 [n_frames][Bh][Bw][4], 8-byte aligned.  Row (i, by, bx), over the bytes of that block of frame i, is
+ *            tai_frame_scan's (s1, s2, sad against the same bytes of frame i - 1, ndiff = #{|d| > tol}); sad = ndiff = 0 for i = 0;
+ *   workspace  tai_block_scan_workspace_bytes(n_frames, h, w, c, bs) bytes, 8-byte aligned.  This version needs none (the query
+ *            returns 0 for every size it takes, every block is summed inside one workgroup) and never touches the pointer, which may be
+ *            null; callers that honour the query stay correct should a later version need one.
+ * Identity: summing the rows of frame i over its blocks gives row i of tai_frame_scan(frames, n_frames, h w c, tol) on the same buffer
+ * (the blocks partition the frame's bytes); tests/test_gpu_block_scan.py holds it.
+ * The sums are integers, so every row has one correct bit pattern.  Row i depends on frames i - 1 and i only: not on n_frames, not on the
+ * base alignment, not on where the scanned range starts.  Every byte is read 1 + 1/8 times.  A block holds at most 32 * 32 * 4 = 4096
+ * bytes and 4096 * 255^2 < 2^32: lane and block sums are 32-bit, the output int64.
+ * One launch, no atomics, no allocation, copy or synchronisation: asynchronous on the stream and capturable into a hipGraph.
+ * TAI_SEPCONV_EINVAL with a message naming the argument, nothing launched: frames or stats null; n_frames < 1; h or w < 1; c outside 1..4;
+ * bs outside {8, 16, 32}; h w c >= 2^31; n_frames h w c above 2^40; tol outside 0..254; stats, or a non-empty workspace, not 8-byte
+ * aligned.  The workspace query returns TAI_SEPCONV_EINVAL for the same sizes.
+ * The last parameter is the HIP stream, spelled `stream` for the reason given at tai_temporal_loss; the refusals are pinned by
+ * tests/test_restore_blocks_cpu.py. */
+long long tai_block_scan_workspace_bytes(long long n_frames, int h, int w, int c, int bs);
+int tai_block_scan(const unsigned char* frames, long long n_frames, int h, int w, int c, int bs, int tol,
+                   long long* stats /* [n_frames][Bh][Bw][4] */, void* workspace, void* stream /* the HIP stream */);
+
+/* The way out of PARTLY damaged frames (csrc/damage_composite.hip.inc; restore.py composites the frames whose flag byte is PARTIAL;
+ * tests/damage_composite_ref.py restates it in numpy): the model's prediction where the damage is, the pipeline's own pixels elsewhere,
+ * a linear ramp of `feather` pixels between them, for a whole batch of frames in one launch.
+ *   pred, src   device fp32 buffers of pred_elems / src_elems elements holding frames [C][Hs][Ws] (padding included): the model's
+ *               output and the pipeline's frames, read in place;
+ *   table       device copy, and table_host a host copy, of n_items items of four 64-bit integers {element offset of the predicted frame
+ *               in pred, element offset of the source frame in src, index of the frame's block map, index of the output frame};
+ *   blocks      device uint8 [n_maps][Bh][Bw], non-zero = damaged, in SOURCE coordinates (blocks of bs x bs source pixels);
+ *   r0, r1, c0, c1   device int32 [h], [h], [w], [w]: the source rows / columns that the bilinear resize of the way in reads WITH NON-ZERO
+ *               WEIGHT at model row y / column x.  The host builds them from the expression of tai_clip_from_frames:
+ *               s = (i + 0.5) * (n_in / n_out) - 0.5 in float64, i0 = clip(floor(s)), i1 = clip(floor(s) + 1) if s - floor(s) > 0, else i0
+ *               (restore.tap_tables).  The kernel does no floating point for geometry; a tap outside the map counts as undamaged;
+ *   out         device uint8 [n_out][h][w][C]: every byte of an item's output frame is written, no other frame is touched.
+ * Definition, in integers behind u (the u of tai_frames_to_uint8: clip, truncating, NaN -> 0):
+ *   core     D(y, x) = 1 iff blocks[m][ty / bs][tx / bs] != 0 for some ty in {r0[y], r1[y]}, tx in {c0[x], c1[x]};
+ *   feather  R = feather + 1; A(y, x) = max(0, R - dist), dist = the Chebyshev distance from (y, x) to the nearest pixel with D = 1
+ *            inside the h x w frame: A = R on the core, one less per pixel, 0 from distance R on; feather = 0 is a hard replace;
+ *   pixels   P = u(pred[c'][y][x]), S = u(src[c'][y][x]), c' = C - 1 - c when reverse_channels, else c;
+ *   blend    out[y][x][c] = floor((2 (A P + (R - A) S) + R) / (2 R)).
+ * Hence A = R gives P and A = 0 gives S byte for byte, and a frame without a damaged block is what tai_frames_to_uint8 writes for src.
+ * A frame's bits depend on its own item only: not on the other items, their order, or the kernel's tiling.
+ * table_host is checked before anything is launched; the kernel re-checks each item of the device copy before it forms an address and
+ * leaves the output frame of a failed item untouched.
+ * One launch, no atomics, no allocation, copy or synchronisation: asynchronous on the stream and capturable into a hipGraph.
+ * TAI_SEPCONV_EINVAL with a message, nothing launched: a null pointer; C outside {1, 3}; bs outside {8, 16, 32}; feather outside 0..15;
+ * non-positive n_items, n_maps, n_out, Bh or Bw; h, w outside 1..Hs, 1..Ws; an index space of 2^31 or more; an item whose predicted or
+ * source frame lies outside pred_elems / src_elems, or whose map or output index is out of range.
+ * The last parameter is the HIP stream, spelled `stream` for the reason given at tai_temporal_loss; the refusals are pinned by
+ * tests/test_restore_blocks_cpu.py. */
+int tai_damage_composite(const float* pred, long long pred_elems, const float* src, long long src_elems, const long long* table,
+                         const long long* table_host, long long n_items, const unsigned char* blocks, long long n_maps, int Bh, int Bw,
+                         int bs, const int* r0, const int* r1, const int* c0, const int* c1, unsigned char* out, long long n_out, int C,
+                         int Hs, int Ws, int h, int w, int feather, int reverse_channels, void* stream /* the HIP stream */);
+
 /* A 64-bit digest of a training state where it lives (csrc/state_digest.hip.inc; video_frame_inpainting_amd/run_state.py builds the
  * table; no counterpart in the reference, whose snapshots carry no check).  On the raw 32-bit words, integer arithmetic modulo 2^64 only:
  *   mix(z): z += 0x9E3779B97F4A7C15; z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9; z = (z ^ (z >> 27)) * 0x94D049BB133111EB; z ^ (z >> 31)

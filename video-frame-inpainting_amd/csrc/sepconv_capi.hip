@@ -40,6 +40,8 @@
 #include "clip_pipeline.hip.inc"
 #include "clip_augment.hip.inc"
 #include "frame_scan.hip.inc"
+#include "block_scan.hip.inc"
+#include "damage_composite.hip.inc"
 #include "state_digest.hip.inc"
 #include "grad_stats.hip.inc"
 #include "fused_step.hip.inc"
@@ -144,7 +146,7 @@ void wino_div_magic(long long d, unsigned& m, unsigned& sh) {
 
 extern "C" {
 
-int tai_sepconv_version(void) { return 880; }
+int tai_sepconv_version(void) { return 890; }
 
 const char* tai_sepconv_last_error(void) { return g_err; }
 

@@ -276,3 +276,23 @@ class RestoreOptions(BaseOptions):
         g.add_argument('--max_T', type=int, default=None, help='longest gap that is filled; default --T')
         g.add_argument('--chunk_frames', type=int, default=256, help='frames decoded, uploaded and scanned at a time')
         g.add_argument('--dry_run', action='store_true', help='scan, plan and write report.json only; needs no GPU')
+        g = self.parser.add_argument_group('Partly damaged frames (off unless --detect_blocks or --damage_map is given)')
+        g.add_argument('--detect_blocks', type=str, default='',
+                       help='comma-separated block detectors out of dup,blank (or none; default: off).  Per block of --block_size source '
+                            'pixels: blank = the variance of the block is at most --block_blank_var (default: a constant block, what a '
+                            'decoder paints); dup = at most --block_dup_share of the block\'s bytes differ from the same block of the '
+                            'previous frame by more than --dup_tol (default: an exact repeat, what concealment by copying leaves).  A '
+                            'flagged block counts as damage only in a run of at most --max_T frames that touches neither the first nor '
+                            'the last frame: letterbox bars and static backgrounds are flagged in long runs and are content, by '
+                            'definition.  Neither detector sees noisy damage or damage that fills only part of a block; a block that '
+                            'really is constant or still for a few frames IS flagged')
+        g.add_argument('--block_size', type=int, default=16, choices=[8, 16, 32], help='block size in SOURCE pixels')
+        g.add_argument('--feather', type=int, default=4,
+                       help='width in model pixels of the ramp between the prediction and the kept pixels; 0..15, 0 = a hard replace')
+        g.add_argument('--block_share', type=float, default=0.5,
+                       help='a frame with more than this share of its blocks damaged is replaced whole, like any gap frame; 0..1')
+        g.add_argument('--block_dup_share', type=float, default=0.0, help='(block dup) share of a block\'s bytes that may differ; 0..1')
+        g.add_argument('--block_blank_var', type=float, default=0.0, help='(block blank) largest variance of a blank block')
+        g.add_argument('--damage_map', type=str, default=None, metavar='FILE.npy',
+                       help='uint8 or bool [n_frames, Bh, Bw], non-zero = damaged: blocks to treat as damaged whatever the detectors '
+                            'say (not filtered by the run rule, as --gaps is not)')

@@ -11,6 +11,17 @@ a static scene: that is the definition, not a fault of the detector); BLANK = 4 
 frame); LISTED = 8 the caller named it.  Only the detectors asked for set their bit.  Every comparison is made in Python integers and
 fractions: there is no rounding to argue about.
 
+Partly damaged frames (opt-in: ``--detect_blocks``, ``--damage_map``).  Pass 1 also takes the four integers per block of
+``--block_size`` source pixels (``block_scan``: ``tai_block_scan`` on the chunk the frame scan already uploaded).  ``classify_blocks``
+raw-flags a block as ``blank`` (nb s2 - s1^2 <= block_blank_var nb^2, nb the bytes of THAT block) or ``dup`` (ndiff <= floor(block_dup_share
+nb), never in frame 0); ``damage_runs`` keeps, at one block position, a maximal run of raw-flagged frames only if it has at most max_T
+frames and touches neither the first nor the last frame of the video -- letterbox bars and static backgrounds are long runs or reach an
+end, so they are content; a painted or concealed macroblock is a short run.  ``--damage_map`` is OR-ed in unfiltered.  A frame with
+1 <= count <= floor(block_share Bh Bw) damaged blocks gets PARTIAL = 16, one with more MOSTLY = 32; the planner treats both as gap frames
+(context frames are always wholly intact).  ``fill`` composites a position whose flag byte is exactly PARTIAL (``tai_damage_composite``:
+the prediction where a model pixel's resize taps touch a damaged block, the pipeline's pixels elsewhere, a ramp of ``--feather`` pixels
+between) and overwrites every other position whole, as before.
+
 The planner's one rule (``plan_gaps``): maximal runs of flagged frames are gaps; two runs with exactly ONE intact frame between them are
 merged into one gap over both runs and that frame (the model needs two context frames; one alone is no context) -- the frame between is
 kept as it is and the prediction at its position is discarded; merging repeats until no such pair is left.  K = min(K, intact frames
@@ -29,7 +40,11 @@ import torch
 from . import _native
 
 MISSING, DUPLICATE, BLANK, LISTED = 1, 2, 4, 8
+PARTIAL, MOSTLY = 16, 32             # some / more than --block_share of the frame's blocks are damaged
 DETECTORS = ('missing', 'dup', 'blank')
+BLOCK_DETECTORS = ('dup', 'blank')
+BLOCK_SIZES = (8, 16, 32)
+MAX_FEATHER = 15
 STATUSES = ('fill', 'no_context_before', 'no_context_after', 'too_long')
 MIN_CONTEXT = 2                      # mcnet.py: the motion encoder takes frame differences, K >= 2 (and F >= 2 for the backward pass)
 
@@ -69,6 +84,44 @@ def scan_frames(frames_u8, tol=0):
     stats = torch.empty(n, 4, dtype=torch.int64, device=frames_u8.device)
     workspace = torch.empty(need // 8, dtype=torch.int64, device=frames_u8.device)
     _native.launch('tai_frame_scan', frames_u8.device, frames_u8, n, frame_bytes, tol, stats, workspace)
+    return stats
+
+
+def _block_scan_numpy(v, bs, tol):
+    """The four integers of include/tai_sepconv.h (tai_block_scan) for uint8 [n, h, w, c], in int64 [n, Bh, Bw, 4].  The frame is padded
+    with zeros up to whole blocks: a zero adds nothing to s1 and s2, and a zero against a zero nothing to sad and ndiff."""
+    n, h, w, c = v.shape
+    Bh, Bw = -(-h // bs), -(-w // bs)
+    p = np.zeros((n, Bh * bs, Bw * bs, c), dtype=np.int64)
+    p[:, :h, :w] = v
+    cells = lambda a: a.reshape(a.shape[0], Bh, bs, Bw, bs, c).sum(axis=(2, 4, 5))
+    out = np.zeros((n, Bh, Bw, 4), dtype=np.int64)
+    out[..., 0] = cells(p)
+    out[..., 1] = cells(p * p)
+    d = np.abs(p[1:] - p[:-1])
+    out[1:, ..., 2] = cells(d)
+    out[1:, ..., 3] = cells((d > tol).astype(np.int64))
+    return out
+
+
+def block_scan(frames_u8, bs, tol=0):
+    """uint8 tensor [n, h, w, c] (contiguous) -> int64 [n, Bh, Bw, 4] = (s1, s2, sad, ndiff) per block of bs x bs pixels, on the tensor's
+    device.  A CUDA tensor goes through ``tai_block_scan`` on the current stream (asynchronous); a CPU tensor is computed with numpy,
+    the same integers, so ``--dry_run`` needs no GPU."""
+    if not (torch.is_tensor(frames_u8) and frames_u8.dtype == torch.uint8 and frames_u8.dim() == 4 and frames_u8.is_contiguous()):
+        raise ValueError('block_scan: expected a contiguous uint8 tensor [n, h, w, c]')
+    bs, tol = int(bs), int(tol)
+    n, h, w, c = (int(k) for k in frames_u8.shape)
+    if bs not in BLOCK_SIZES or not 0 <= tol <= 254 or not 1 <= c <= 4 or min(n, h, w) < 1:
+        raise ValueError('block_scan: needs bs in %s, tol in 0..254, c in 1..4 and at least one non-empty frame' % (BLOCK_SIZES,))
+    if not frames_u8.is_cuda:
+        return torch.from_numpy(_block_scan_numpy(frames_u8.numpy(), bs, tol))
+    need = _native.lib().tai_block_scan_workspace_bytes(n, h, w, c, bs)
+    if need < 0:
+        raise ValueError('block_scan: %d frames of %d x %d x %d are refused by tai_block_scan' % (n, h, w, c))
+    stats = torch.empty(n, -(-h // bs), -(-w // bs), 4, dtype=torch.int64, device=frames_u8.device)
+    workspace = torch.empty(need // 8, dtype=torch.int64, device=frames_u8.device) if need else None
+    _native.launch('tai_block_scan', frames_u8.device, frames_u8, n, h, w, c, bs, tol, stats, workspace)
     return stats
 
 
@@ -127,6 +180,112 @@ def classify(stats, frame_bytes, present, listed, detect, dup_share=0.0, blank_v
             f |= LISTED
         flags[i] = f
     return flags
+
+
+# ---------------------------------------------------------------------------------------------------------------- damaged blocks
+
+def parse_detect_blocks(text):
+    """'dup,blank' -> the set of block detectors; '' or 'none' -> none (the feature is off unless --damage_map is given)."""
+    names = [s.strip() for s in str(text or '').split(',') if s.strip()]
+    if names == ['none']:
+        names = []
+    bad = [s for s in names if s not in BLOCK_DETECTORS]
+    if bad:
+        raise ValueError('--detect_blocks: unknown detector %r (choose from %s)' % (bad[0], ', '.join(BLOCK_DETECTORS)))
+    return frozenset(names)
+
+
+def classify_blocks(bstats, h, w, c, bs, detect, block_dup_share=0.0, block_blank_var=0.0):
+    """bstats [n, Bh, Bw, 4] (``block_scan`` of frames [h, w, c]) -> bool [n, Bh, Bw]: the RAW flags, before ``damage_runs``."""
+    rows = np.asarray(bstats.cpu() if torch.is_tensor(bstats) else bstats)
+    detect = frozenset(detect)
+    if not detect <= set(BLOCK_DETECTORS):
+        raise ValueError('classify_blocks: detect must be a subset of %s' % (BLOCK_DETECTORS,))
+    share, var = Fraction(block_dup_share), Fraction(block_blank_var)
+    if not 0 <= share <= 1 or var < 0:
+        raise ValueError('classify_blocks: block_dup_share must be in [0, 1] and block_blank_var >= 0')
+    n, Bh, Bw = rows.shape[:3]
+    if (Bh, Bw) != (-(-h // bs), -(-w // bs)) or rows.shape[3] != 4:
+        raise ValueError('classify_blocks: statistics of shape %s do not belong to frames of %d x %d in blocks of %d' % (rows.shape, h, w, bs))
+    raw = np.zeros((n, Bh, Bw), dtype=bool)
+    for by in range(Bh):
+        for bx in range(Bw):
+            nb = (min(h, (by + 1) * bs) - by * bs) * (min(w, (bx + 1) * bs) - bx * bs) * c        # the bytes of THIS block
+            dup_max, var_max = (share * nb).__floor__(), var * nb * nb
+            for i, (s1, s2, _, ndiff) in enumerate(rows[:, by, bx].tolist()):
+                raw[i, by, bx] = ('dup' in detect and i >= 1 and ndiff <= dup_max) or ('blank' in detect and nb * s2 - s1 * s1 <= var_max)
+    return raw
+
+
+def damage_runs(raw, max_T):
+    """The rule that tells damage from content: raw flags bool [n, Bh, Bw] -> damaged bool [n, Bh, Bw].  Along time, at one block
+    position, a maximal run of raw-flagged frames is damage only if it has at most ``max_T`` frames and touches neither frame 0 nor
+    frame n - 1."""
+    raw = np.asarray(raw, dtype=bool)
+    n = raw.shape[0]
+    out = np.zeros_like(raw)
+    for by, bx in zip(*np.nonzero(raw.any(axis=0))):
+        col, i = raw[:, by, bx].tolist(), 0
+        while i < n:
+            if not col[i]:
+                i += 1
+                continue
+            j = i
+            while j + 1 < n and col[j + 1]:
+                j += 1
+            if j - i + 1 <= max_T and i > 0 and j < n - 1:
+                out[i:j + 1, by, bx] = True
+            i = j + 1
+    return out
+
+
+def load_damage_map(path, shape):
+    """--damage_map FILE.npy: uint8 or bool [n, Bh, Bw], non-zero = damaged -> bool array; a wrong shape or type is refused."""
+    m = np.load(path, allow_pickle=False)
+    if m.dtype not in (np.uint8, np.bool_):
+        raise ValueError('--damage_map: %s holds %s, expected uint8 or bool' % (path, m.dtype))
+    if tuple(m.shape) != tuple(shape):
+        raise ValueError('--damage_map: %s has shape %s, the video has %s blocks [n, Bh, Bw]' % (path, tuple(m.shape), tuple(shape)))
+    return m != 0
+
+
+def block_flags(damaged, block_share=0.5):
+    """damaged bool [n, Bh, Bw] -> uint8 [n]: PARTIAL for 1 <= count <= floor(block_share Bh Bw) damaged blocks, MOSTLY above that."""
+    damaged = np.asarray(damaged, dtype=bool)
+    share = Fraction(block_share)
+    if not 0 <= share <= 1:
+        raise ValueError('--block_share must be in [0, 1]')
+    most = (share * damaged.shape[1] * damaged.shape[2]).__floor__()
+    counts = damaged.reshape(damaged.shape[0], -1).sum(axis=1).tolist()
+    return np.array([0 if k == 0 else (PARTIAL if k <= most else MOSTLY) for k in counts], dtype=np.uint8)
+
+
+def tap_tables(n_in, n_out):
+    """int32 (i0, i1), each [n_out]: the source indices that ``data.resize_bilinear`` / the clip kernel's ``tap`` multiply by a NON-ZERO
+    weight at output index i (i1 = i0 where the fraction is 0, so also for the identity).  The same float64 expression as theirs."""
+    src = (np.arange(n_out, dtype=np.float64) + 0.5) * (n_in / float(n_out)) - 0.5
+    fl = np.floor(src)
+    i0 = np.clip(fl.astype(np.int64), 0, n_in - 1)
+    i1 = np.where(src - fl > 0, np.clip(fl.astype(np.int64) + 1, 0, n_in - 1), i0)
+    return i0.astype(np.int32), i1.astype(np.int32)
+
+
+def composite_device(pred, src, items, blocks, taps, bs, h, w, feather, rgb):
+    """One ``tai_damage_composite`` launch on the current stream.  ``pred`` / ``src``: fp32 CUDA tensors whose storage holds the frames
+    [C, Hs, Ws] the items point into (element offsets from the tensors' first element); ``items``: rows (pred offset, src offset, map, output
+    frame); ``blocks``: uint8 [n_maps, Bh, Bw]; ``taps``: (r0, r1, c0, c1) int32 CUDA tensors.  -> uint8 CUDA [n_out, h, w, C]."""
+    C, Hs, Ws = (int(k) for k in src.shape[-3:])
+    table_host = torch.tensor(items, dtype=torch.int64).reshape(-1, 4)
+    table = table_host.to(pred.device)
+    blocks = torch.as_tensor(blocks).to(device=pred.device, dtype=torch.uint8).contiguous()
+    n_maps, Bh, Bw = (int(k) for k in blocks.shape)
+    n_out = int(table_host[:, 3].max()) + 1
+    out = torch.empty(n_out, h, w, C, dtype=torch.uint8, device=pred.device)
+    elems = lambda t: t.untyped_storage().nbytes() // 4 - t.storage_offset()
+    _native.launch('tai_damage_composite', pred.device, pred, elems(pred), src, elems(src), table, table_host.data_ptr(), table_host.shape[0],
+                   blocks, n_maps, Bh, Bw, int(bs), taps[0], taps[1], taps[2], taps[3], out, n_out, C, Hs, Ws, int(h), int(w), int(feather),
+                   int(bool(rgb)))
+    return out
 
 
 # ---------------------------------------------------------------------------------------------------------------- the planner
@@ -254,6 +413,14 @@ class Restorer(object):
             raise ValueError('--dup_tol must be in 0..254')
         if min(opt.K, opt.F) < MIN_CONTEXT or opt.T < 1 or self.max_T < 1:
             raise ValueError('restore: needs K, F >= %d and T, max_T >= 1' % MIN_CONTEXT)
+        # partly damaged frames: off unless --detect_blocks or --damage_map is given; then nothing below differs from before
+        self.detect_blocks = parse_detect_blocks(getattr(opt, 'detect_blocks', ''))
+        self.damage_map = getattr(opt, 'damage_map', None) or None
+        self.blocks_on = bool(self.detect_blocks) or self.damage_map is not None
+        self.block_size, self.feather = int(getattr(opt, 'block_size', 16)), int(getattr(opt, 'feather', 4))
+        if self.blocks_on and (self.block_size not in BLOCK_SIZES or not 0 <= self.feather <= MAX_FEATHER):
+            raise ValueError('--block_size must be one of %s and --feather in 0..%d' % (BLOCK_SIZES, MAX_FEATHER))
+        self.block_stats = self.damaged = self.flags = self.source_size = None
 
     def _chunks(self, reader):
         """(first frame, uint8 [m, h, w, 3]) over the source, in order; all frames of a source share one size."""
@@ -271,12 +438,17 @@ class Restorer(object):
         the pair statistics cross the chunk boundaries."""
         n, tol = reader.get_length(), int(self.opt.dup_tol)
         rows, buf, frame_bytes = [], None, None
+        brows = [] if self.detect_blocks else None                           # one more launch per chunk, on the same buffer
         for a, frames in self._chunks(reader):
             m = frames.shape[0]
             if buf is None:
                 frame_bytes = frames[0].numel()
+                self.source_size = (int(frames.shape[1]), int(frames.shape[2]))
                 buf = torch.empty((self.chunk + 1,) + tuple(frames.shape[1:]), dtype=torch.uint8, device=device)
             buf[1:m + 1].copy_(frames, non_blocking=True)
+            if brows is not None:
+                part = block_scan(buf[1:m + 1] if a == 0 else buf[:m + 1], self.block_size, tol)
+                brows.append((part if a == 0 else part[1:]).cpu())
             if a == 0:
                 rows.append(scan_frames(buf[1:m + 1], tol).cpu())
             else:
@@ -284,13 +456,29 @@ class Restorer(object):
             buf[0].copy_(buf[m])
         stats = torch.cat(rows)
         assert stats.shape == (n, 4)
+        self.block_stats = torch.cat(brows) if brows is not None else None
         return stats, frame_bytes
 
     def plan(self, reader, present, device):
         stats, frame_bytes = self.scan(reader, device)
         listed = parse_gaps(getattr(self.opt, 'gaps', None), reader.get_length())
         flags = classify(stats, frame_bytes, present, listed, self.detect, self.opt.dup_share, self.opt.blank_var)
+        if self.blocks_on:
+            flags = flags | block_flags(self.damaged_blocks(reader.get_length()), self.opt.block_share)
+        self.flags = flags
         return stats, flags, plan_gaps(flags, self.opt.K, self.opt.F, self.max_T)
+
+    def damaged_blocks(self, n):
+        """-> bool [n, Bh, Bw] (kept in ``self.damaged``): the detectors' raw flags through the run rule, OR the caller's map."""
+        (h, w), bs = self.source_size, self.block_size
+        damaged = np.zeros((n, -(-h // bs), -(-w // bs)), dtype=bool)
+        if self.detect_blocks:
+            raw = classify_blocks(self.block_stats, h, w, 3, bs, self.detect_blocks, self.opt.block_dup_share, self.opt.block_blank_var)
+            damaged |= damage_runs(raw, self.max_T)
+        if self.damage_map is not None:
+            damaged |= load_damage_map(self.damage_map, damaged.shape)
+        self.damaged = damaged
+        return damaged
 
     def model_frames(self, reader):
         """Pass 2's way in -> fp32 [n, C, H + pad, W + pad] on the device: every frame as the models take it."""
@@ -305,10 +493,13 @@ class Restorer(object):
 
     def fill(self, video, gaps, out_u8):
         """Run the ``fill`` gaps through the model, grouped by (K, T, F) in batches of at most --batch_size, and write their pixels
-        into ``out_u8`` [n, h, w, C] at the gaps' positions."""
+        into ``out_u8`` [n, h, w, C] at the gaps' positions.  A position whose flag byte is exactly PARTIAL is composited
+        (``tai_damage_composite``, one launch per batch); every other position is overwritten whole."""
         from . import clip_pipeline
         opt, env = self.opt, self.env
         (h, w), rgb = opt.image_size, opt.c_dim == 3
+        partial = set(np.nonzero(self.flags == PARTIAL)[0].tolist()) if self.blocks_on else set()
+        taps = None
         groups = {}
         for g in gaps:
             if g['status'] == 'fill':
@@ -322,10 +513,29 @@ class Restorer(object):
                 env.T = T
                 env.eval()
                 env.forward_test()
-                pixels = clip_pipeline.to_uint8_host(env.gen_output['pred'], h, w, rgb)           # [B, T, h, w, C]
-                for b, g in enumerate(batch):
-                    for p in g['positions']:
-                        out_u8[p] = pixels[b, p - g['start']]
+                pred = env.gen_output['pred']                                                     # [B, T, C, Hs, Ws]
+                where = [(b, p) for b, g in enumerate(batch) for p in g['positions']]
+                if any(p not in partial for _, p in where):
+                    pixels = clip_pipeline.to_uint8_host(pred, h, w, rgb)                         # [B, T, h, w, C]
+                    for b, p in where:
+                        if p not in partial:
+                            out_u8[p] = pixels[b, p - batch[b]['start']]
+                mine = [(b, p) for b, p in where if p in partial]
+                if mine:
+                    # one launch for the batch's partly damaged frames; pred and video are read in place, by element offset
+                    if taps is None:
+                        taps = [torch.from_numpy(t).to(env.device) for n_in, n_out in zip(self.source_size, (h, w))
+                                for t in tap_tables(n_in, n_out)]
+                    if pred.dtype != torch.float32 or not pred[0, 0].is_contiguous():
+                        pred = pred.float().contiguous()
+                    if not video[0].is_contiguous():
+                        video = video.contiguous()
+                    items = [[b * pred.stride(0) + (p - batch[b]['start']) * pred.stride(1), p * video.stride(0), k, k]
+                             for k, (b, p) in enumerate(mine)]
+                    done = composite_device(pred, video, items, self.damaged[[p for _, p in mine]].astype(np.uint8), taps, self.block_size,
+                                            h, w, self.feather, rgb).cpu().numpy()
+                    for k, (_, p) in enumerate(mine):
+                        out_u8[p] = done[k]
 
     def run(self, path, output_dir):
         from . import clip_pipeline
@@ -354,6 +564,14 @@ class Restorer(object):
                        for i, r in enumerate(stats.tolist())],
             'gaps': [{k: g[k] for k in ('start', 'T', 'K', 'F', 'status', 'positions')} for g in gaps],
         }
+        if self.blocks_on:                   # with the feature off the report has exactly the keys it had before
+            report['settings'].update({'detect_blocks': sorted(self.detect_blocks), 'block_size': self.block_size, 'feather': self.feather,
+                                       'block_share': float(opt.block_share), 'block_dup_share': float(opt.block_dup_share),
+                                       'block_blank_var': float(opt.block_blank_var), 'damage_map': self.damage_map or ''})
+            for f in report['frames']:
+                f['blocks'] = [[int(by), int(bx)] for by, bx in zip(*np.nonzero(self.damaged[f['index']]))]
+            for g in report['gaps']:
+                g['composited'] = [p for p in g['positions'] if g['status'] == 'fill' and int(flags[p]) == PARTIAL]
         with open(os.path.join(output_dir, 'report.json'), 'w') as f:
             json.dump(report, f, indent=1)
         return report
