@@ -1,6 +1,7 @@
-"""What the four fused-loss GPU test files (test_gpu_{ssim,image,lap,temporal}_loss.py) share: bit views and relative errors, the tiny
-model's train.py runs and how their output is read, and the three test bodies that are the same for every loss up to its flags and
-keys -- graph replay against eager, straight against split, graph_step.  A plain module, imported the way sepconv_cases.py is."""
+"""What the five fused-loss GPU test files (test_gpu_{ssim,image,lap,temporal,census}_loss.py) share: bit views and relative errors, the
+tiny model's train.py runs and how their output is read, and the three test bodies that are the same for every loss up to its flags and
+keys -- graph replay against eager, straight against split, graph_step; and, for test_loss_terms_cpu.py and test_gpu_loss_terms.py,
+loss_G's fold written out.  A plain module, imported the way sepconv_cases.py is."""
 import gc
 import re
 
@@ -118,3 +119,59 @@ def check_graph_step(tmp_path, capsys, flags, terms, changing=None, replays_diff
     assert all(len(set(found[key])) > 1 for key in (changing or found))
     if replays_differ:
         assert any(v[2] != v[3] for v in found.values())
+
+
+# ---------------------------------------------------------------------------------------------------------------- loss_G's fold
+
+TERM_WEIGHTS = {'ssim_weight': 0.2, 'lap_weight': 0.5, 'temporal_weight': 0.3, 'census_weight': 0.7}          # all different: a mixed-up weight shows
+
+
+def check_fold(env, image_loss, on, three):
+    """After one update of ``env`` (``on``: the keys of TERM_WEIGHTS that are on; ``three``: TAITrainingEnvironment): loss_G's bits are
+    those of the fp32 left-to-right fold of the environment's value attributes, written out here addend by addend and not read from the
+    environment's own table; no tensor with autograd history stays on the environment outside the step outputs; the printed keys are the
+    ones listed here."""
+    w = {k: (v if k in on else 0.0) for k, v in TERM_WEIGHTS.items()}
+    a, b = env.alpha, env.beta
+    g = torch.zeros(1, device=env.loss_G.device)
+    if image_loss == 'l2':
+        g = g + a * (env.Lp + env.gdl)
+        g = g + b * env.L_GAN
+    else:
+        g = g + a * env.image
+        g = g + b * env.L_GAN
+        if three:
+            g = g + a * (env.image_forward + env.image_backward)
+    if w['ssim_weight']:
+        g = g + w['ssim_weight'] * env.ssim
+    if w['lap_weight']:
+        g = g + w['lap_weight'] * env.lap
+    if w['temporal_weight']:
+        g = g + w['temporal_weight'] * env.temporal
+        if three:
+            g = g + w['temporal_weight'] * (env.temporal_forward + env.temporal_backward)
+    if w['census_weight']:
+        g = g + w['census_weight'] * env.census
+        if three:
+            g = g + w['census_weight'] * (env.census_forward + env.census_backward)
+    if three and image_loss == 'l2':
+        g = g + a * (env.Lp_forward + env.Lp_backward + env.gdl_forward + env.gdl_backward)
+    if three and w['ssim_weight']:
+        g = g + w['ssim_weight'] * (env.ssim_forward + env.ssim_backward)
+    if three and w['lap_weight']:
+        g = g + w['lap_weight'] * (env.lap_forward + env.lap_backward)
+    print(image_loss, sorted(on), 'loss_G', float(env.loss_G.detach()), 'fold', float(g.detach()))
+    assert g.dtype == env.loss_G.dtype == torch.float32 and g.shape == env.loss_G.shape
+    assert torch.equal(g.detach().view(torch.int32), env.loss_G.detach().view(torch.int32))
+
+    def with_history(v):
+        return any(t.grad_fn is not None for t in (v.values() if isinstance(v, dict) else [v]) if torch.is_tensor(t))
+    alive = sorted(k for k, v in vars(env).items() if with_history(v))
+    assert 'loss_G' in alive and set(alive) <= set(env._STEP_OUTPUTS), (alive, env._STEP_OUTPUTS)
+
+    ends = ['', '_forward', '_backward'] if three else ['']
+    keys = ['D_fake', 'D_real', 'G_GAN', 'G_loss'] + ['G_' + name + end for name in ('Lp', 'gdl') for end in ends]
+    keys += ['G_' + k[:-len('_weight')] + end for k in TERM_WEIGHTS if w[k] for end in ends]
+    errors = env.get_current_errors()
+    assert sorted(errors) == sorted(keys)
+    assert all(np.isfinite(v) for v in errors.values())

@@ -170,10 +170,10 @@ def composition(pt, g):
     """MSELoss + GDL of three predictions as the environments run them."""
     mse, gdl = torch.nn.MSELoss(), losses.GDL()
     time_major = L2GDLDiscTrainingEnvironment._time_major_01
-    gt = time_major(g)                                   # as the environments do: gt's copy is made once per compute_loss_G,
-    x = time_major(pt[0])                                # by the base class for pred ...
+    gt = time_major(g)                                   # as the environments do: gt's copy is made once per pass of compute_loss_G,
+    x = time_major(pt[0])                                # for pred ...
     total = mse(x, gt) + gdl(x, gt)
-    gt = time_major(g)                                   # ... and by TAITrainingEnvironment for pred_forward and pred_backward
+    gt = time_major(g)                                   # ... and for pred_forward and pred_backward
     xf, xb = time_major(pt[1]), time_major(pt[2])
     return total + (mse(xf, gt) + mse(xb, gt) + gdl(xf, gt) + gdl(xb, gt))
 
@@ -298,7 +298,7 @@ def launch_lines(which, reps, out_path):
 def make_env(name, **kw):
     torch.manual_seed(0)
     env = create_training_environment(vfi.create_model('TAI_gray'), 1, os.path.join(ROOT, 'build', 'no_checkpoints'), name,
-                                      K, T, F, [SIZE, SIZE], 1.0, 0.02, 1e-4, 0.5, 64, 3, 3, [0, 0], device=DEV, **kw)
+                                      K, T, F, [SIZE, SIZE], 1.0, 0.02, 1e-4, 0.5, 64, 3, 3, [0, 0], device=DEV, losses=losses.LossSettings(**kw))
     env.K, env.T, env.F = K, T, F
     env.train()
     return env

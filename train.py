@@ -73,6 +73,7 @@ import video_frame_inpainting_amd as vfi
 from video_frame_inpainting_amd import clip_pipeline, fused_step, grad_guard, parallel, run_state, synthetic, tai
 from video_frame_inpainting_amd.data import ClipAugment, ContiguousVideoClipDataset, ResumableBatchSampler
 from video_frame_inpainting_amd.environments import create_training_environment
+from video_frame_inpainting_amd.losses import LossSettings
 from video_frame_inpainting_amd.options import TrainOptions
 from video_frame_inpainting_amd.validation import Validator
 
@@ -98,20 +99,11 @@ def main(args=None):
     if not opt.fused_step and fused_step.needs_fused_step(schedule, opt.weight_decay):
         raise SystemExit(fused_step.needs_fused_step(schedule, opt.weight_decay))
     opt.schedule = schedule
-    if not opt.ssim_weight >= 0.0:
-        raise SystemExit('--ssim_weight must not be negative, found %r' % opt.ssim_weight)
-    if not (opt.charbonnier_eps > 0.0 and opt.charbonnier_eps != float('inf')):
-        raise SystemExit('--charbonnier_eps must be finite and > 0, found %r' % opt.charbonnier_eps)
-    if not opt.lap_weight >= 0.0:
-        raise SystemExit('--lap_weight must not be negative, found %r' % opt.lap_weight)
-    if opt.lap_weight > 0.0 and not 1 <= opt.lap_levels <= 6:
-        raise SystemExit('--lap_levels must be 1..6, found %r' % opt.lap_levels)
-    if not opt.temporal_weight >= 0.0:
-        raise SystemExit('--temporal_weight must not be negative, found %r' % opt.temporal_weight)
-    if not (opt.temporal_eps > 0.0 and opt.temporal_eps != float('inf')):
-        raise SystemExit('--temporal_eps must be finite and > 0, found %r' % opt.temporal_eps)
-    if not (opt.census_weight >= 0.0 and opt.census_weight != float('inf')):
-        raise SystemExit('--census_weight must be finite and not negative, found %r' % opt.census_weight)
+    opt.losses = LossSettings.from_options(opt)
+    try:
+        opt.losses.check()
+    except ValueError as e:
+        raise SystemExit(str(e))
     if not opt.resumable:
         return _run(opt, None)
     if opt.graph_step and GRAPH_STEP_REFUSAL:
@@ -191,10 +183,7 @@ def _run(opt, stop):
                                       opt.image_size, opt.alpha, opt.beta, opt.lr, opt.beta1, opt.df_dim, opt.Ip,
                                       opt.disc_window_size, opt.padding_size, device=device,
                                       graph_step=opt.graph_step, resumable=resumable, guard=guard, fused_step=opt.fused_step,
-                                      ema_decay=opt.ema_decay, max_iter=opt.max_iter, ssim_weight=opt.ssim_weight,
-                                      image_loss=opt.image_loss, charbonnier_eps=opt.charbonnier_eps,
-                                      lap_weight=opt.lap_weight, lap_levels=opt.lap_levels, temporal_weight=opt.temporal_weight,
-                                      temporal_kind=opt.temporal_kind, temporal_eps=opt.temporal_eps, census_weight=opt.census_weight,
+                                      ema_decay=opt.ema_decay, max_iter=opt.max_iter, losses=opt.losses,
                                       lr_D=opt.lr_D, lr_schedule=opt.schedule, weight_decay=opt.weight_decay)
     env.sync_replicas()
     total_updates = env.start_update

@@ -15,6 +15,9 @@ What differs (same arithmetic):
   * ``optimize_parameters`` all-reduces generator and discriminator gradients across data-parallel ranks (parallel.py)
     right after each backward, in the reference's G-then-D order; with one process it is the reference's step.
 """
+import collections
+import functools
+import operator
 import os
 
 import numpy as np
@@ -23,7 +26,7 @@ import torch
 from . import conv_ops, parallel, run_state
 from . import fused_step as fused_step_module
 from .graph import GraphedForward
-from .losses import GDL, IMAGE_LOSS_KINDS, CensusLoss, ImageLoss, LapLoss, SSIMLoss, TemporalLoss
+from .losses import GDL, CensusLoss, ImageLoss, LapLoss, LossSettings, SSIMLoss, TemporalLoss
 from .mcnet import MCNetFillInModel
 from .sn_discriminator import SNDiscriminator
 from .ablations import (BidirectionalSimpleAverageFillInModel, BidirectionalTimeWeightedAverageFillInModel,
@@ -45,26 +48,14 @@ def create_eval_environment(fill_in_model, checkpoints_dir, name, snapshot_file_
 
 def create_training_environment(fill_in_model, c_dim, checkpoints_dir, name, max_K, max_T, max_F, image_size, alpha,
                                 beta, lr, beta1, df_dim, Ip, disc_window_size, padding_size, device=None, graph_step=False,
-                                resumable=False, guard=None, fused_step=False, ema_decay=None, max_iter=100000, ssim_weight=0.0,
-                                image_loss='l2', charbonnier_eps=1e-3, lap_weight=0.0, lap_levels=5, temporal_weight=0.0,
-                                temporal_kind='charbonnier', temporal_eps=1e-3, census_weight=0.0, lr_D=None, lr_schedule=None,
-                                weight_decay=0.0):
-    if not ssim_weight >= 0.0:
-        raise ValueError('ssim_weight must not be negative, found %r' % (ssim_weight,))
-    if not lap_weight >= 0.0:
-        raise ValueError('lap_weight must not be negative, found %r' % (lap_weight,))
-    if image_loss not in IMAGE_LOSS_KINDS:
-        raise ValueError('image_loss must be one of %s, found %r' % (', '.join(IMAGE_LOSS_KINDS), image_loss))
-    if not (charbonnier_eps > 0.0 and charbonnier_eps != float('inf')):
-        raise ValueError('charbonnier_eps must be finite and > 0, found %r' % (charbonnier_eps,))
-    if not temporal_weight >= 0.0:
-        raise ValueError('temporal_weight must not be negative, found %r' % (temporal_weight,))
-    if temporal_kind not in IMAGE_LOSS_KINDS:
-        raise ValueError('temporal_kind must be one of %s, found %r' % (', '.join(IMAGE_LOSS_KINDS), temporal_kind))
-    if not (temporal_eps > 0.0 and temporal_eps != float('inf')):
-        raise ValueError('temporal_eps must be finite and > 0, found %r' % (temporal_eps,))
-    if not (census_weight >= 0.0 and census_weight != float('inf')):
-        raise ValueError('census_weight must be finite and not negative, found %r' % (census_weight,))
+                                resumable=False, guard=None, fused_step=False, ema_decay=None, max_iter=100000, losses=None,
+                                lr_D=None, lr_schedule=None, weight_decay=0.0, **loss_settings):
+    # losses: a losses.LossSettings (train.py's loss flags); its fields are also taken as keywords (ssim_weight=0.2).  Neither = the
+    # reference's loss
+    if losses is not None and loss_settings:
+        raise TypeError('create_training_environment: losses= and %s are two ways to say one thing' % ', '.join(sorted(loss_settings)))
+    losses = losses or LossSettings(**loss_settings)
+    losses.check()
     if guard is not None and graph_step:
         raise ValueError('a guarded update cannot be a captured one: a replayed update cannot leave out an optimizer step')
     if fused_step and graph_step:
@@ -79,23 +70,14 @@ def create_training_environment(fill_in_model, c_dim, checkpoints_dir, name, max
         raise ValueError(fused_step_module.needs_fused_step(lr_schedule, weight_decay))
     if isinstance(fill_in_model, (TAIFillInModel, TimeWeightedInterpolationFillInModel,
                                   BidirectionalSimpleAverageFillInModel, BidirectionalTimeWeightedAverageFillInModel)):
-        env = TAITrainingEnvironment(      # environments.py:29-31
-            fill_in_model, checkpoints_dir, name, image_size, c_dim, alpha, beta, lr, beta1,
-                                     df_dim, Ip, disc_window_size, max_K, max_T, max_F, padding_size, device=device,
-                                     graph_step=graph_step, ssim_weight=ssim_weight, image_loss=image_loss,
-                                     charbonnier_eps=charbonnier_eps, lap_weight=lap_weight, lap_levels=lap_levels,
-                                     temporal_weight=temporal_weight, temporal_kind=temporal_kind, temporal_eps=temporal_eps,
-                                     census_weight=census_weight)
+        environment = TAITrainingEnvironment      # environments.py:29-31
     elif isinstance(fill_in_model, MCNetFillInModel):
-        env = MCNetTrainingEnvironment(fill_in_model, checkpoints_dir, name, image_size, c_dim, alpha, beta, lr, beta1,
-                                       df_dim, Ip, disc_window_size, max_K, max_T, max_F, padding_size, device=device,
-                                       graph_step=graph_step, ssim_weight=ssim_weight, image_loss=image_loss,
-                                     charbonnier_eps=charbonnier_eps, lap_weight=lap_weight, lap_levels=lap_levels,
-                                     temporal_weight=temporal_weight, temporal_kind=temporal_kind, temporal_eps=temporal_eps,
-                                     census_weight=census_weight)
+        environment = MCNetTrainingEnvironment
     else:
         raise RuntimeError('Tried to create a training environment for object of unsupported type %s'
                            % type(fill_in_model).__name__)
+    env = environment(fill_in_model, checkpoints_dir, name, image_size, c_dim, alpha, beta, lr, beta1, df_dim, Ip, disc_window_size,
+                      max_K, max_T, max_F, padding_size, device=device, graph_step=graph_step, losses=losses)
     env.resumable = bool(resumable)
     env.guard = guard
     if lr_D is not None and hasattr(env, 'optimizer_D'):      # only another number handed to the second optimizer
@@ -178,6 +160,25 @@ class _parameters_frozen(object):
         for p in self.params:
             p.requires_grad_(True)
         return False
+
+
+# one term of loss_G (L2GDLDiscTrainingEnvironment.__init__ says what the fields mean)
+_Term = collections.namedtuple('_Term', 'name weight module together adds shows')
+
+
+def _one_by_one(module):
+    """``module(prediction, gt)`` behind the signature of the terms that take every prediction in one call."""
+    return lambda predictions, gt: tuple(module(p, gt) for p in predictions)
+
+
+def _sum(values):
+    """Left to right: loss_G is an fp32 fold, so the order of the addends is part of what an update computes."""
+    return functools.reduce(operator.add, values)
+
+
+def _further(values):
+    """The sum that goes into loss_G for the predictions behind ``pred``, value by value: Lp_forward + Lp_backward + gdl_forward + ..."""
+    return _sum(v for column in zip(*values) for v in column)
 
 
 class BaseVideoFillInEnvironment(object):
@@ -293,12 +294,21 @@ class BaseTrainingEnvironment(BaseVideoFillInEnvironment):
     def forward_train(self):
         self.gen_output = self.generator(self.T, self.preceding_frames, self.following_frames)
 
-    # attributes an update produces (tensors of the captured graph's pool when the update is replayed).  Every tensor with autograd
-    # history that an update leaves on the environment belongs here -- a new loss term's values included: train_step detaches these
-    # before a capture ends, and one that is missing outlives the capture and faults the HIP runtime when it is closed
-    _STEP_OUTPUTS = ('gen_output', 'loss_G', 'Lp', 'gdl', 'L_GAN', 'loss_d_fake', 'loss_d_real', 'loss_D', 'Lp_forward',
-                     'Lp_backward', 'gdl_forward', 'gdl_backward', 'ssim', 'ssim_forward', 'ssim_backward', 'lap', 'lap_forward', 'lap_backward',
-                     'temporal', 'temporal_forward', 'temporal_backward', 'census', 'census_forward', 'census_backward')
+    PREDICTIONS = ('pred',)    # the keys of ``gen_output`` the loss terms are applied to, ``pred`` first
+    _terms = ()                # the loss terms of an update (L2GDLDiscTrainingEnvironment builds the table)
+
+    def _term_values(self, printed=False):
+        """The attributes the loss terms write in an update, or those of them that are ``printed``: each value's name, with ``_forward``
+        and ``_backward`` behind it for the further predictions."""
+        return [name + key[len('pred'):] for term in self._terms
+                for name in (term.shows if printed else dict.fromkeys(term.adds + term.shows)) for key in self.PREDICTIONS]
+
+    # attributes an update produces (tensors of the captured graph's pool when the update is replayed): train_step detaches them before
+    # a capture ends, because a tensor with autograd history that outlives the capture faults the HIP runtime when it is closed.  Every
+    # value a loss term leaves on the environment is written under a name of the term table, so the list follows from the table
+    @property
+    def _STEP_OUTPUTS(self):
+        return ('gen_output', 'loss_G', 'L_GAN', 'loss_d_fake', 'loss_d_real', 'loss_D') + tuple(self._term_values())
 
     def train_step(self, preceding_frames, following_frames, gt_middle_frames):
         """One update on a batch: set_train_inputs + forward_train + optimize_parameters (src/train.py:147-169), with
@@ -516,38 +526,36 @@ class L2GDLDiscTrainingEnvironment(BaseTrainingEnvironment):
     loss_D = BCE(D(fake.detach()), window labels) + BCE(D(real), 1)."""
 
     def __init__(self, fill_in_model, checkpoints_dir, name, image_size, c_dim, alpha, beta, lr, beta1, df_dim, Ip,
-                 disc_t, max_K, max_T, max_F, padding_size, device=None, graph_step=False, ssim_weight=0.0, image_loss='l2',
-                 charbonnier_eps=1e-3, lap_weight=0.0, lap_levels=5, temporal_weight=0.0, temporal_kind='charbonnier', temporal_eps=1e-3,
-                 census_weight=0.0):
+                 disc_t, max_K, max_T, max_F, padding_size, device=None, graph_step=False, losses=None):
         super().__init__(fill_in_model, checkpoints_dir, name, lr, beta1, max_K, max_T, max_F, padding_size, device=device,
                          graph_step=graph_step)
-        # ssim_weight (train.py --ssim_weight G) > 0: loss_G gains G (1 - mean SSIM) per prediction (losses.SSIMLoss, one HIP launch for
-        # the loss and its gradient); 0 = the reference's loss: no module, no launch, no extra key in get_current_errors
-        self.ssim_weight = float(ssim_weight)
-        self.loss_ssim = SSIMLoss() if self.ssim_weight > 0 else None
-        # image_loss (train.py --image_loss) 'l1' / 'charbonnier': Lp and gdl of every prediction come from losses.ImageLoss on the model's
-        # own [B, T, C, H, W] layout (one HIP launch for the losses and their gradients, no time-major copies); 'l2' = the reference's
-        # MSELoss + GDL composition below: no module, no launch
-        self.loss_image = ImageLoss(image_loss, charbonnier_eps) if image_loss != 'l2' else None
-        # lap_weight (train.py --lap_weight G) > 0: loss_G gains G times the Laplacian-pyramid L1 distance per prediction (losses.LapLoss
-        # with lap_levels levels, one HIP launch for the loss and its gradient); 0 = no module, no launch, no extra key
-        self.lap_weight = float(lap_weight)
-        self.loss_lap = LapLoss(lap_levels) if self.lap_weight > 0 else None
-        # temporal_weight (train.py --temporal_weight G) > 0: loss_G gains G times the temporal-difference term of every prediction
-        # (losses.TemporalLoss: one HIP launch for all predictions of an update, each read in its own layout -- gen_output['pred'] is a
-        # time-major view and is not copied); 0 = no module, no launch, no extra key
-        self.temporal_weight = float(temporal_weight)
-        self.loss_temporal = TemporalLoss(temporal_kind, temporal_eps) if self.temporal_weight > 0 else None
-        # census_weight (train.py --census_weight G) > 0: loss_G gains G times the census (soft ternary) term of every prediction
-        # (losses.CensusLoss: one HIP launch for all predictions of an update, each read in its own layout); 0 = no module, no launch, no
-        # extra key
-        self.census_weight = float(census_weight)
-        self.loss_census = CensusLoss() if self.census_weight > 0 else None
+        losses = losses or LossSettings()
         self._fake_labels = {}
         self.loss_Lp = torch.nn.MSELoss()
         self.loss_gdl = GDL()
         self.loss_d = torch.nn.BCEWithLogitsLoss()
         self.alpha, self.beta, self.disc_t = alpha, beta, disc_t
+        self.ssim_weight, self.lap_weight = float(losses.ssim_weight), float(losses.lap_weight)
+        self.temporal_weight, self.census_weight = float(losses.temporal_weight), float(losses.census_weight)
+        # a term that is off builds nothing: no module, no launch, no key in get_current_errors.  'l2' is the reference's image loss
+        self.loss_image = ImageLoss(losses.image_loss, losses.charbonnier_eps) if losses.image_loss != 'l2' else None
+        self.loss_ssim = SSIMLoss() if self.ssim_weight > 0 else None
+        self.loss_lap = LapLoss(losses.lap_levels) if self.lap_weight > 0 else None
+        self.loss_temporal = TemporalLoss(losses.temporal_kind, losses.temporal_eps) if self.temporal_weight > 0 else None
+        self.loss_census = CensusLoss() if self.census_weight > 0 else None
+        # The terms of loss_G in the order compute_loss_G adds them.  ``module(predictions, gt)`` -> per prediction the values named by
+        # ``adds``, whose sum times ``weight`` goes into loss_G; ``shows``: the values get_current_errors prints.  ``together``: one call
+        # (one HIP launch for the losses and gradients, each tensor read in its own layout) takes every prediction of the update; else
+        # the module sees one prediction per call.  An ImageLoss carries the gradient in ``image`` and prints its detached Lp and gdl.
+        if self.loss_image is None:
+            self._terms = [_Term('image', alpha, self._mse_and_gdl, False, ('Lp', 'gdl'), ('Lp', 'gdl'))]
+        else:
+            self._terms = [_Term('image', alpha, self.loss_image, True, ('image',), ('Lp', 'gdl'))]
+        for term_name, weight, module, together in (('ssim', self.ssim_weight, self.loss_ssim, False), ('lap', self.lap_weight, self.loss_lap, False),
+                                                    ('temporal', self.temporal_weight, self.loss_temporal, True),
+                                                    ('census', self.census_weight, self.loss_census, True)):
+            if module is not None:
+                self._terms.append(_Term(term_name, weight, module if together else _one_by_one(module), together, (term_name,), (term_name,)))
         discriminator = SNDiscriminator((image_size[0] + padding_size[0], image_size[1] + padding_size[1]), c_dim,
                                         disc_t, df_dim, Ip)
         discriminator = move_to_devices(discriminator, self.device)
@@ -621,71 +629,48 @@ class L2GDLDiscTrainingEnvironment(BaseTrainingEnvironment):
         _, _, c, H, W = x.shape
         return inverse_transform(x.permute(1, 0, 2, 3, 4).contiguous().view(-1, c, H, W))
 
-    _IMAGE_LOSS_KEYS = ('pred',)          # the predictions the image loss is applied to, the first one being ``pred``
+    def _mse_and_gdl(self, predictions, gt):
+        """The reference's image loss (environments.py:363-372) -> (Lp, gdl) per prediction."""
+        gt = self._time_major_01(gt)
+        return tuple((self.loss_Lp(x, gt), self.loss_gdl(x, gt)) for x in [self._time_major_01(p) for p in predictions])
+
+    def _evaluate(self, term, keys):
+        """One call of the term's module on the predictions ``keys``; its values stay on the environment under their names -> per
+        prediction the values loss_G adds."""
+        values = [v if isinstance(v, tuple) else (v,) for v in term.module(tuple(self.gen_output[k] for k in keys), self.gt_middle_frames)]
+        for i, key in enumerate(keys):
+            named = list(zip(term.adds, values[i]))
+            if term.shows != term.adds:                 # an ImageLoss: the detached terms of the same launch
+                named += zip(term.shows, term.module.last_terms[i])
+            for name, v in named:
+                setattr(self, name + key[len('pred'):], v)
+        return values
 
     def compute_loss_G(self):
         super().compute_loss_G()
-        if self.loss_image is not None:
-            # every prediction in one launch; the terms are detached values for the printed line, the losses carry the gradient
-            image_losses = self.loss_image(tuple(self.gen_output[k] for k in self._IMAGE_LOSS_KEYS), self.gt_middle_frames)
-            self.Lp, self.gdl = self.loss_image.last_terms[0]
-        else:
-            gt = self._time_major_01(self.gt_middle_frames)
-            outputs = self._time_major_01(self.gen_output['pred'])
-            self.Lp = self.loss_Lp(outputs, gt)
-            self.gdl = self.loss_gdl(outputs, gt)
-        fake = torch.cat([self.preceding_frames, self.gen_output['pred'], self.following_frames], dim=1)
-        # The reference lets this backward pass fill the discriminator's .grad as well and throws those values away
-        # (optimizer_D.zero_grad() comes before they are ever read, environments.py:348-355): here the discriminator's
-        # parameters are taken out of the graph for this evaluation, which skips a third of its weight-gradient work.
-        with _parameters_frozen(self.discriminator):
-            h = self.discriminator(fake)
-        self.L_GAN = self.loss_d(h, torch.ones_like(h))
-        if self.loss_image is not None:
-            self.loss_G = self.loss_G + self.alpha * image_losses[0] + self.beta * self.L_GAN          # point + gdl, summed in float64
-            self._add_further_image_losses(image_losses[1:])
-        else:
-            self.loss_G = self.loss_G + self.alpha * (self.Lp + self.gdl) + self.beta * self.L_GAN
-        if self.loss_ssim is not None:
-            # on the model's own [B, T, C, H, W] layout: the mean over planes does not care about their order
-            self.ssim = self.loss_ssim(self.gen_output['pred'], self.gt_middle_frames)
-            self.loss_G = self.loss_G + self.ssim_weight * self.ssim
-        if self.loss_lap is not None:
-            self.lap = self.loss_lap(self.gen_output['pred'], self.gt_middle_frames)
-            self.loss_G = self.loss_G + self.lap_weight * self.lap
-        if self.loss_temporal is not None:
-            temporal = self.loss_temporal(tuple(self.gen_output[k] for k in self._IMAGE_LOSS_KEYS), self.gt_middle_frames)
-            self.temporal = temporal[0]
-            self.loss_G = self.loss_G + self.temporal_weight * self.temporal
-            self._add_further_temporal_losses(temporal[1:])
-        if self.loss_census is not None:
-            census = self.loss_census(tuple(self.gen_output[k] for k in self._IMAGE_LOSS_KEYS), self.gt_middle_frames)
-            self.census = census[0]
-            self.loss_G = self.loss_G + self.census_weight * self.census
-            self._add_further_census_losses(census[1:])
-
-    def _add_further_census_losses(self, losses):
-        """The census terms of ``_IMAGE_LOSS_KEYS[1:]`` (they came from the same launch as ``pred``'s): none here."""
-
-    def _add_further_temporal_losses(self, losses):
-        """The temporal terms of ``_IMAGE_LOSS_KEYS[1:]`` (they came from the same launch as ``pred``'s): none here."""
-
-    def _add_further_image_losses(self, losses):
-        """The image losses of ``_IMAGE_LOSS_KEYS[1:]`` (they came from the same launch as ``pred``'s): none here."""
+        for term in self._terms:
+            values = self._evaluate(term, self.PREDICTIONS if term.together else self.PREDICTIONS[:1])
+            self.loss_G = self.loss_G + term.weight * _sum(values[0])
+            if term.name == 'image':
+                fake = torch.cat([self.preceding_frames, self.gen_output['pred'], self.following_frames], dim=1)
+                # The reference lets this backward pass fill the discriminator's .grad as well and throws those values away
+                # (optimizer_D.zero_grad() comes before they are ever read, environments.py:348-355): here the discriminator's
+                # parameters are taken out of the graph for this evaluation, which skips a third of its weight-gradient work.
+                with _parameters_frozen(self.discriminator):
+                    h = self.discriminator(fake)
+                self.L_GAN = self.loss_d(h, torch.ones_like(h))
+                self.loss_G = self.loss_G + self.beta * self.L_GAN
+            if values[1:]:
+                self.loss_G = self.loss_G + term.weight * _further(values[1:])
+        # the modules that see one prediction per call come to the further predictions behind every term's ``pred``
+        for term in self._terms:
+            if not term.together and self.PREDICTIONS[1:]:
+                self.loss_G = self.loss_G + term.weight * _further(self._evaluate(term, self.PREDICTIONS[1:]))
 
     def get_current_errors(self):
         d = super().get_current_errors()
-        d.update({'G_Lp': float(self.Lp.item()), 'G_gdl': float(self.gdl.item()),
-                  'D_real': float(self.loss_d_real.item()), 'D_fake': float(self.loss_d_fake.item()),
-                  'G_GAN': float(self.L_GAN.item())})
-        if self.loss_ssim is not None:
-            d['G_ssim'] = float(self.ssim.item())
-        if self.loss_lap is not None:
-            d['G_lap'] = float(self.lap.item())
-        if self.loss_temporal is not None:
-            d['G_temporal'] = float(self.temporal.item())
-        if self.loss_census is not None:
-            d['G_census'] = float(self.census.item())
+        d.update({'D_real': float(self.loss_d_real.item()), 'D_fake': float(self.loss_d_fake.item()), 'G_GAN': float(self.L_GAN.item())})
+        d.update(('G_' + name, float(getattr(self, name).item())) for name in self._term_values(printed=True))
         return d
 
     def train(self):
@@ -712,50 +697,4 @@ class TAITrainingEnvironment(L2GDLDiscTrainingEnvironment):
                     self._ktf_rng.randint(2, self.max_F + 1))
         return self.max_K, self.max_T, self.max_F
 
-    _IMAGE_LOSS_KEYS = ('pred', 'pred_forward', 'pred_backward')
-
-    def compute_loss_G(self):
-        super().compute_loss_G()
-        if self.loss_image is None:
-            gt = self._time_major_01(self.gt_middle_frames)
-            out_f = self._time_major_01(self.gen_output['pred_forward'])
-            out_b = self._time_major_01(self.gen_output['pred_backward'])
-            self.Lp_forward = self.loss_Lp(out_f, gt)
-            self.Lp_backward = self.loss_Lp(out_b, gt)
-            self.gdl_forward = self.loss_gdl(out_f, gt)
-            self.gdl_backward = self.loss_gdl(out_b, gt)
-            self.loss_G = self.loss_G + self.alpha * (self.Lp_forward + self.Lp_backward + self.gdl_forward + self.gdl_backward)
-        if self.loss_ssim is not None:
-            self.ssim_forward = self.loss_ssim(self.gen_output['pred_forward'], self.gt_middle_frames)
-            self.ssim_backward = self.loss_ssim(self.gen_output['pred_backward'], self.gt_middle_frames)
-            self.loss_G = self.loss_G + self.ssim_weight * (self.ssim_forward + self.ssim_backward)
-        if self.loss_lap is not None:
-            self.lap_forward = self.loss_lap(self.gen_output['pred_forward'], self.gt_middle_frames)
-            self.lap_backward = self.loss_lap(self.gen_output['pred_backward'], self.gt_middle_frames)
-            self.loss_G = self.loss_G + self.lap_weight * (self.lap_forward + self.lap_backward)
-
-    def _add_further_image_losses(self, losses):
-        (self.Lp_forward, self.gdl_forward), (self.Lp_backward, self.gdl_backward) = self.loss_image.last_terms[1:]
-        self.loss_G = self.loss_G + self.alpha * (losses[0] + losses[1])
-
-    def _add_further_temporal_losses(self, losses):
-        self.temporal_forward, self.temporal_backward = losses
-        self.loss_G = self.loss_G + self.temporal_weight * (self.temporal_forward + self.temporal_backward)
-
-    def _add_further_census_losses(self, losses):
-        self.census_forward, self.census_backward = losses
-        self.loss_G = self.loss_G + self.census_weight * (self.census_forward + self.census_backward)
-
-    def get_current_errors(self):
-        d = super().get_current_errors()
-        d.update({'G_Lp_forward': float(self.Lp_forward.item()), 'G_gdl_forward': float(self.gdl_forward.item()),
-                  'G_Lp_backward': float(self.Lp_backward.item()), 'G_gdl_backward': float(self.gdl_backward.item())})
-        if self.loss_ssim is not None:
-            d.update({'G_ssim_forward': float(self.ssim_forward.item()), 'G_ssim_backward': float(self.ssim_backward.item())})
-        if self.loss_lap is not None:
-            d.update({'G_lap_forward': float(self.lap_forward.item()), 'G_lap_backward': float(self.lap_backward.item())})
-        if self.loss_temporal is not None:
-            d.update({'G_temporal_forward': float(self.temporal_forward.item()), 'G_temporal_backward': float(self.temporal_backward.item())})
-        if self.loss_census is not None:
-            d.update({'G_census_forward': float(self.census_forward.item()), 'G_census_backward': float(self.census_backward.item())})
-        return d
+    PREDICTIONS = ('pred', 'pred_forward', 'pred_backward')

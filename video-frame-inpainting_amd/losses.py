@@ -96,14 +96,53 @@ class _FusedLoss(torch.autograd.Function):
         return (None, None, None) + tuple(None if m is None else (grad_losses if one else grad_losses[i]) * m for i, m in enumerate(ctx.maps))
 
 
+def _check_kind(what, kind):
+    if kind not in IMAGE_LOSS_KINDS:
+        raise ValueError('%s must be one of %s, found %r' % (what, ', '.join(IMAGE_LOSS_KINDS), kind))
+
+
+def _check_eps(what, eps):
+    if not (eps > 0.0 and eps != float('inf')):
+        raise ValueError('%s must be finite and > 0, found %r' % (what, eps))
+
+
+def _check_levels(what, levels):
+    if not (isinstance(levels, int) and 1 <= levels <= LAP_MAX_LEVELS):
+        raise ValueError('%s must be an integer from 1 to %d, found %r' % (what, LAP_MAX_LEVELS, levels))
+
+
 def _kind_and_eps(name, kind, eps):
     """(kind, eps) of ImageLoss and TemporalLoss, checked."""
-    if kind not in IMAGE_LOSS_KINDS:
-        raise ValueError('%s: kind must be one of %s, found %r' % (name, ', '.join(IMAGE_LOSS_KINDS), kind))
+    _check_kind(name + ': kind', kind)
     eps = float(eps)
-    if not (eps > 0.0 and eps != float('inf')):
-        raise ValueError('%s: eps must be finite and > 0, found %r' % (name, eps))
+    _check_eps(name + ': eps', eps)
     return kind, eps
+
+
+class LossSettings(collections.namedtuple('LossSettings', 'ssim_weight image_loss charbonnier_eps lap_weight lap_levels temporal_weight '
+                                                          'temporal_kind temporal_eps census_weight',
+                                          defaults=(0.0, 'l2', 1e-3, 0.0, 5, 0.0, 'charbonnier', 1e-3, 0.0))):
+    """train.py's loss flags, each field under its flag's name; the defaults are the reference's loss.  What
+    ``environments.create_training_environment`` takes as ``losses``."""
+    __slots__ = ()
+
+    @classmethod
+    def from_options(cls, opt):
+        return cls(*(getattr(opt, field) for field in cls._fields))
+
+    def check(self):
+        """Raises ValueError naming the flag whose value is refused."""
+        for flag in ('ssim_weight', 'lap_weight', 'temporal_weight'):
+            if not getattr(self, flag) >= 0.0:
+                raise ValueError('--%s must not be negative, found %r' % (flag, getattr(self, flag)))
+        if not (self.census_weight >= 0.0 and self.census_weight != float('inf')):
+            raise ValueError('--census_weight must be finite and not negative, found %r' % (self.census_weight,))
+        _check_kind('--image_loss', self.image_loss)
+        _check_eps('--charbonnier_eps', self.charbonnier_eps)
+        if self.lap_weight > 0.0:                                 # the levels of a pyramid that is not built are not looked at
+            _check_levels('--lap_levels', self.lap_levels)
+        _check_kind('--temporal_kind', self.temporal_kind)
+        _check_eps('--temporal_eps', self.temporal_eps)
 
 
 def _predictions(name, preds):
@@ -320,8 +359,7 @@ class LapLoss(nn.Module):
 
     def __init__(self, levels=5):
         super().__init__()
-        if not (isinstance(levels, int) and 1 <= levels <= LAP_MAX_LEVELS):
-            raise ValueError('LapLoss: levels must be an integer from 1 to %d, found %r' % (LAP_MAX_LEVELS, levels))
+        _check_levels('LapLoss: levels', levels)
         self.levels = levels
         self.last_terms = None
         self.plane_terms = None
